@@ -22,6 +22,12 @@ post-aggregate verifications are extra work not counted in it.  Weak scaling: ev
 its own V validators (validator sharding); with N > 1 ranks each step ends with the
 library's RCCL all-gather of verdicts and aggregates over xGMI (hbls_allgather_device).
 
+A plain run sets up, warms up, times --steps slots and prints the line (value, ms_per_step, the
+slot's event times); --dump-outputs DIR also writes the last timed slot's outputs as .npy files
+(the inputs are derived from fixed seeds, so two builds can be compared output for output).
+The parity check of the timed outputs, the roofline and the CPU baseline described below, and the
+host-buffer, key-table, first-error, VerifyAggregate and concurrent-caller legs run only with --full.
+
 roofline: integer VALU: the dominant kernel's algorithmic Fp products (textbook
 count, charon_amd/opcounts.py) x 300 multiply-adds, over its HIP-event time in the timed region,
 against the measured v_mad_u64_u32 peak.
@@ -597,6 +603,28 @@ def roofline_from_timing(recs, steps, units):
     return dom, per
 
 
+DUMP_BUDGET = 60 * 1000 * 1000  # bytes of array data (--dump-outputs allows 64 MB with the .npy headers)
+
+
+def dump_outputs(path, arrays, rank: int = 0):
+    """--dump-outputs: every output of the last timed step as <name>.npy (float32, exact for the
+    status and signature bytes), rank r > 0 as <name>.rank<r>.npy.  `arrays` maps a name to a 2-D
+    array of rows; where all of them exceed DUMP_BUDGET every array keeps its share of the budget
+    as a fixed sample of rows (seed 0, ascending), the same rows in every run and every build."""
+    os.makedirs(path, exist_ok=True)
+    total = 4 * sum(a.size for a in arrays.values())
+    written = {}
+    for name, a in arrays.items():
+        rows = a.shape[0]
+        if total > DUMP_BUDGET:
+            keep = max(1, int(rows * DUMP_BUDGET / total))
+            a = a[np.sort(np.random.default_rng(0).choice(rows, size=keep, replace=False))]
+        f = os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy")
+        np.save(f, np.ascontiguousarray(a, dtype=np.float32))
+        written[name] = {"rows": int(a.shape[0]), "of": int(rows), "row_len": int(a.shape[1])}
+    return written
+
+
 def launch_ranks(n: int, argv) -> int:
     """`bench.py --gpus N` without a launcher: run N ranks of this script as child processes, one
     per GPU, with the environment torch.distributed.run would give them (RANK, LOCAL_RANK,
@@ -684,6 +712,14 @@ def main(argv=None):
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=5)
     ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run every other measurement and check: parity of the timed "
+                         "outputs, per-kernel roofline, host-buffer entry points, key tables, first-error and "
+                         "aggregate verification, concurrent callers, CPU baseline (each with its own option "
+                         "below); without it only the headline is measured and those options are ignored")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="write what the last timed step computed (statuses, aggregates, signing roots) as "
+                         "DIR/<name>.npy in float32, at most 64 MB in all")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS))
     ap.add_argument("--validators", type=int, default=0, help="override validators per GPU")
     ap.add_argument("--cpu-seconds", type=float, default=12.0, help="bounded CPU-baseline sample (0: skip)")
@@ -717,9 +753,16 @@ def main(argv=None):
                          "and prints the merged line (tests the launcher on a CPU host); 2: the same with "
                          "the last rank failing")
     args = ap.parse_args(argv)
+    if not args.full:
+        # a plain run: set up, warm up, time the steps, dump, print -- every other leg is --full's
+        args.cpu_seconds = 0.0
+        args.callers = args.aggregate_verify = args.key_tables = args.host_api = 0
 
     if args.gpus < 1:
         print(f"bench.py: --gpus {args.gpus}: need at least one", file=sys.stderr)
+        return 2
+    if args.steps < 1 or args.warmup < 0:
+        print(f"bench.py: --steps {args.steps} --warmup {args.warmup}: need at least one timed step", file=sys.stderr)
         return 2
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         # no launcher: start the N ranks here, before anything in this process touches the GPU
@@ -901,44 +944,61 @@ def main(argv=None):
     if timed_events:
         _chk(L, L.hbls_timing(0))
 
-    # parity of the timed outputs: every partial verifies, every aggregate is byte-identical to the
-    # root-key signature (tbls_test.go:72-97 property) and verifies under the DV key
-    # the output sets the timed steps wrote (a short run may leave some of the in-flight sets unused)
-    used = [outs[k % n_sets] for k in sorted({k % n_sets for k in range(args.warmup, args.warmup + args.steps)})] \
-        if not staged else outs[:1]
-    if "exp_v" in d:  # C5: every status bit-exact against construction
-        clean = d["exp_agg"] == 0
-        parity = {"verify_statuses_exact": all(np.array_equal(o["vst"].cpu().numpy(), d["exp_v"]) for o in used),
-                  "ta_statuses_exact": all(np.array_equal(o["tst"].cpu().numpy(), d["exp_ta"]) for o in used),
-                  "ta_equals_root_signature_where_clean": all(np.array_equal(
-                      o["tout"].cpu().numpy().reshape(V, 96)[clean], d["root_sigs"].reshape(V, 96)[clean])
-                      for o in used)}
+    def timed_parity():
+        # parity of the timed outputs: every partial verifies, every aggregate is byte-identical to the
+        # root-key signature (tbls_test.go:72-97 property) and verifies under the DV key
+        # the output sets the timed steps wrote (a short run may leave some of the in-flight sets unused)
+        used = [outs[k % n_sets] for k in sorted({k % n_sets for k in range(args.warmup, args.warmup + args.steps)})] \
+            if not staged else outs[:1]
+        if "exp_v" in d:  # C5: every status bit-exact against construction
+            clean = d["exp_agg"] == 0
+            parity = {"verify_statuses_exact": all(np.array_equal(o["vst"].cpu().numpy(), d["exp_v"]) for o in used),
+                      "ta_statuses_exact": all(np.array_equal(o["tst"].cpu().numpy(), d["exp_ta"]) for o in used),
+                      "ta_equals_root_signature_where_clean": all(np.array_equal(
+                          o["tout"].cpu().numpy().reshape(V, 96)[clean], d["root_sigs"].reshape(V, 96)[clean])
+                          for o in used)}
+            if not staged:
+                parity["aggregate_verify_statuses_exact"] = all(
+                    np.array_equal(o["ast"].cpu().numpy(), d["exp_agg"]) for o in used)
+        else:
+            parity = {"verify_all_ok": all(bool((o["vst"] == 0).all().item()) for o in used),
+                      "ta_all_ok": all(bool((o["tst"] == 0).all().item()) for o in used),
+                      "ta_equals_root_signature": all(np.array_equal(o["tout"].cpu().numpy(), d["root_sigs"])
+                                                      for o in used)}
+            if not staged:
+                parity["aggregate_verify_all_ok"] = all(bool((o["ast"] == 0).all().item()) for o in used)
+        if xw and "exp_v" in d:  # every rank's block equals that rank's construction: check our own
+            parity["allgather_ok"] = bool(
+                np.array_equal(gathered("vbits")[rank * NB:(rank + 1) * NB].cpu().numpy(),
+                               np.packbits(d["exp_v"] == 0, bitorder="little")) and
+                np.array_equal(gathered("tst")[rank * V:(rank + 1) * V].cpu().numpy(), d["exp_ta"]) and
+                np.array_equal(gathered("ast")[rank * V:(rank + 1) * V].cpu().numpy(), d["exp_agg"]))
+        elif xw:
+            want = torch.from_numpy(np.packbits(np.ones(NP, dtype=bool), bitorder="little")).to(dev)
+            gv = gathered("vbits")
+            parity["allgather_ok"] = bool(all(torch.equal(gv[r * NB:(r + 1) * NB], want) for r in range(world))
+                                          and (gathered("tst") == 0).all().item()
+                                          and (gathered("ast") == 0).all().item())
+            # rank r's block of the gathered aggregates is rank r's root signatures: check our own block
+            clean = d["exp_agg"] == 0 if "exp_v" in d else np.ones(V, dtype=bool)
+            parity["allgather_own_block"] = bool(np.array_equal(
+                gathered("tout")[rank * V * 96:(rank + 1) * V * 96].cpu().numpy().reshape(V, 96)[clean],
+                d["root_sigs"].reshape(V, 96)[clean]))
+        return parity
+
+    dumped = None
+    if args.dump_outputs:
+        # what a caller of the timed path holds after the last timed step: that slot's output set
+        o = outs[0] if staged else outs[(step_no[0] - 1) % n_sets]
+        arrays = {"verify_status": o["vst"].cpu().numpy().reshape(NP, 1),
+                  "aggregates": o["tout"].cpu().numpy().reshape(V, 96),
+                  "aggregate_status": o["tst"].cpu().numpy().reshape(V, 1)}
         if not staged:
-            parity["aggregate_verify_statuses_exact"] = all(
-                np.array_equal(o["ast"].cpu().numpy(), d["exp_agg"]) for o in used)
-    else:
-        parity = {"verify_all_ok": all(bool((o["vst"] == 0).all().item()) for o in used),
-                  "ta_all_ok": all(bool((o["tst"] == 0).all().item()) for o in used),
-                  "ta_equals_root_signature": all(np.array_equal(o["tout"].cpu().numpy(), d["root_sigs"])
-                                                  for o in used)}
-        if not staged:
-            parity["aggregate_verify_all_ok"] = all(bool((o["ast"] == 0).all().item()) for o in used)
-    if xw and "exp_v" in d:  # every rank's block equals that rank's construction: check our own
-        parity["allgather_ok"] = bool(
-            np.array_equal(gathered("vbits")[rank * NB:(rank + 1) * NB].cpu().numpy(),
-                           np.packbits(d["exp_v"] == 0, bitorder="little")) and
-            np.array_equal(gathered("tst")[rank * V:(rank + 1) * V].cpu().numpy(), d["exp_ta"]) and
-            np.array_equal(gathered("ast")[rank * V:(rank + 1) * V].cpu().numpy(), d["exp_agg"]))
-    elif xw:
-        want = torch.from_numpy(np.packbits(np.ones(NP, dtype=bool), bitorder="little")).to(dev)
-        gv = gathered("vbits")
-        parity["allgather_ok"] = bool(all(torch.equal(gv[r * NB:(r + 1) * NB], want) for r in range(world))
-                                      and (gathered("tst") == 0).all().item() and (gathered("ast") == 0).all().item())
-        # rank r's block of the gathered aggregates is rank r's root signatures: check our own block
-        clean = d["exp_agg"] == 0 if "exp_v" in d else np.ones(V, dtype=bool)
-        parity["allgather_own_block"] = bool(np.array_equal(
-            gathered("tout")[rank * V * 96:(rank + 1) * V * 96].cpu().numpy().reshape(V, 96)[clean],
-            d["root_sigs"].reshape(V, 96)[clean]))
+            arrays["aggregate_verify_status"] = o["ast"].cpu().numpy().reshape(V, 1)
+            arrays["signing_roots"] = o["msg"].cpu().numpy().reshape(M, 32)
+        dumped = dump_outputs(args.dump_outputs, arrays, rank)
+
+    parity = timed_parity() if args.full else {}
 
     items = world * (NP + V)
     ms_per_step = elapsed / args.steps * 1e3
@@ -1104,7 +1164,9 @@ def main(argv=None):
                      {"slot": round(k_ms[0], 3), "allgather": round(k_ms[1], 3)}),
         "verify_whole_effective_Tops_vs_r01_work": round(verify_effective, 3),
         "kernels": None,
-        "parity": parity, "roofline": None, "cpu_baseline": None,
+        "parity": parity if args.full else None, "roofline": None, "cpu_baseline": None,
+        "full": bool(args.full),
+        **({"dumped_outputs": dumped} if dumped is not None else {}),
     }
 
     if args.host_api and rank == 0 and world == 1:
@@ -1185,9 +1247,10 @@ def main(argv=None):
         _chk(L, L.hbls_stats(st, 6))
         out["fallback_stats"] = dict(zip(("items", "groups", "fallback_items", "last_chunk_groups_checked",
                                           "slot_checks", "slot_checks_failed"), list(st)))
-    out["kernels"], out["roofline"] = kernel_roofline()
+    if args.full:
+        out["kernels"], out["roofline"] = kernel_roofline()
 
-    if rank == 0 and world == 1 and "exp_v" in d and not staged:
+    if args.full and rank == 0 and world == 1 and "exp_v" in d and not staged:
         out["first_error"] = first_error_verify(L, d, d_pk, d_sig, d_midx, d_vgoff, dev, sp)
         parity["first_error_index_exact"] = out["first_error"]["first_index_exact"]
 

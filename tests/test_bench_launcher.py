@@ -85,3 +85,38 @@ def test_torchrun_launch_stdout_is_the_line():
     assert len(out) == 1, p.stdout
     line = json.loads(out[0])
     assert line["n_gpus"] == 2 and sorted(r["rank"] for r in line["ranks"]) == [0, 1]
+
+
+def test_dump_outputs_writes_float32_and_samples_a_fixed_set_over_the_budget(tmp_path, monkeypatch):
+    # --dump-outputs: whole arrays under the budget; over it every array keeps its share as the
+    # same seeded rows in every run (two builds are compared file for file)
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    a = {"status": (np.arange(1000, dtype=np.uint8) % 7).reshape(1000, 1),
+         "aggregates": np.arange(96 * 500, dtype=np.uint32).astype(np.uint8).reshape(500, 96)}
+    w = bench.dump_outputs(str(tmp_path / "whole"), a)
+    for k, v in a.items():
+        got = np.load(tmp_path / "whole" / f"{k}.npy")
+        assert got.dtype == np.float32 and np.array_equal(got, v.astype(np.float32))
+        assert w[k] == {"rows": v.shape[0], "of": v.shape[0], "row_len": v.shape[1]}
+    total = 4 * sum(v.size for v in a.values())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", total // 4)
+    w1 = bench.dump_outputs(str(tmp_path / "s1"), a)
+    bench.dump_outputs(str(tmp_path / "s2"), a, rank=1)
+    size = 0
+    for k, v in a.items():
+        g1, g2 = np.load(tmp_path / "s1" / f"{k}.npy"), np.load(tmp_path / "s2" / f"{k}.rank1.npy")
+        assert np.array_equal(g1, g2) and g1.dtype == np.float32
+        assert g1.shape == (v.shape[0] // 4, v.shape[1]) and w1[k]["rows"] == v.shape[0] // 4
+        size += g1.nbytes
+    assert size <= total // 4
+    # the sampled rows are rows of the array, in ascending order
+    rows = np.load(tmp_path / "s1" / "status.npy")[:, 0]
+    idx = np.sort(np.random.default_rng(0).choice(1000, size=250, replace=False))
+    assert np.array_equal(rows, a["status"][idx, 0].astype(np.float32))
+
+
+def test_full_and_dump_outputs_are_options():
+    p = subprocess.run([sys.executable, BENCH, "--help"], env=_env(), capture_output=True, text=True, timeout=120)
+    assert p.returncode == 0 and "--full" in p.stdout and "--dump-outputs" in p.stdout

@@ -271,7 +271,9 @@ def test_bench_two_ranks_rehearsal(workload):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items()
            if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT", "LOCAL_WORLD_SIZE")}
-    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--share-device", "1", "--workload", workload,
+    # --full: the parity of the timed outputs and of the gathered blocks is one of its checks
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--full", "--gpus", "2", "--share-device", "1",
+           "--workload", workload,
            "--validators", "3000" if workload == "c5" else "2000", "--steps", "2", "--warmup", "1", "--cpu-seconds", "0",
            "--callers", "0", "--aggregate-verify", "0", "--key-tables", "0", "--host-api", "0"]
     p = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=280)

@@ -30,7 +30,7 @@ smoke() {
 bench() {
   local wl=$1
   shift
-  timeout -k 10 600 python -u bench.py --workload "$wl" "$@" > "$O/bench_${wl}_$TAG.json" 2> "$O/bench_${wl}_$TAG.err"
+  timeout -k 10 600 python -u bench.py --full --workload "$wl" "$@" > "$O/bench_${wl}_$TAG.json" 2> "$O/bench_${wl}_$TAG.err"
 }
 lines() {
   bench c3 &&
@@ -40,12 +40,12 @@ lines() {
 }
 trace() {
   (cd /tmp && export TMPDIR=/tmp &&
-   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o run --output-format csv -- python3 "$B" "$@" \
+   timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$O/prof_$TAG" -o run --output-format csv -- python3 "$B" --full "$@" \
      > "$O/bench_prof_$TAG.json" 2> "$O/bench_prof_$TAG.err")
 }
 pmc() {
   local P="$O/pmc_$TAG"
-  local A="--workload c3 --steps 1 --warmup 1 --cpu-seconds 0 --callers 0 --aggregate-verify 0 --key-tables 0 --host-api 0"
+  local A="--full --workload c3 --steps 1 --warmup 1 --cpu-seconds 0 --callers 0 --aggregate-verify 0 --key-tables 0 --host-api 0"
   (cd /tmp && export TMPDIR=/tmp &&
    timeout -k 10 300 rocprofv3 --kernel-trace --stats -d "$P/trace" -o run --output-format csv -- python3 "$B" $A > "$P.trace.log" 2>&1 &&
    timeout -s KILL 300 rocprofv3 --pmc SQ_INSTS_VALU SQ_ACTIVE_INST_VALU SQ_BUSY_CYCLES SQ_WAVE_CYCLES SQ_WAVES SQ_INSTS_SALU SQ_WAIT_INST_ANY SQ_WAIT_ANY -d "$P/sq" -o run --output-format csv -- python3 "$B" $A > "$P.sq.log" 2>&1 &&
@@ -65,7 +65,7 @@ peak() {  # the roofline peak pinned by counters (tools/microbench/int_rates_pmc
 attack() {
   local f
   for f in 0.05 0.10; do
-    timeout -k 10 600 python -u bench.py --workload c5 --bad-frac $f --cpu-seconds 0 --callers 0 --key-tables 0 \
+    timeout -k 10 600 python -u bench.py --full --workload c5 --bad-frac $f --cpu-seconds 0 --callers 0 --key-tables 0 \
       --host-api 0 > "$O/bench_c5_bad${f}_$TAG.json" 2> "$O/bench_c5_bad${f}_$TAG.err" || return 1
   done
 }
@@ -83,7 +83,7 @@ ab() {
   for rep in 1 2; do
     for spec in "$@"; do
       local lab=${spec%%=*} lib=${spec#*=}
-      HBLS_LIBRARY="$lib" timeout -k 10 400 python -u bench.py --workload "$wl" ${AB_ARGS:-$QUIET --key-tables 0} \
+      HBLS_LIBRARY="$lib" timeout -k 10 400 python -u bench.py --full --workload "$wl" ${AB_ARGS:-$QUIET --key-tables 0} \
         > "$O/ab_${TAG}_${wl}_${lab}_$rep.json" 2> "$O/ab_${TAG}_${wl}_${lab}_$rep.err" || return 1
     done
   done

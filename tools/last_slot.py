@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Per-kernel durations of the LAST slot in a rocprofv3 kernel trace of bench.py: the serialised
-roofline slot that bench.py runs after its timed region (library timing mode 2), to compare with
+roofline slot that bench.py --full runs after its timed region (library timing mode 2), to compare with
 the bench line's `kernels` (alone) figures.  Usage: last_slot.py run_kernel_trace.csv"""
 import collections
 import csv
