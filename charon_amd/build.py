@@ -1,6 +1,7 @@
-"""Build libhipbls.so (gfx950) in-tree, plus the test-only CPU harness.
+"""Build libhipbls.so (gfx950) in-tree, plus the test-only CPU harness, C client and device block
+harness.
 
-    python -m charon_amd.build            # product library + test harness
+    python -m charon_amd.build            # product library + test harnesses
 The product library is compiled by hipcc for --offload-arch=gfx950 only.
 """
 
@@ -139,6 +140,96 @@ def build_c_client(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+DEVBLOCKS_PREFIX = "hbls-devblocks:"
+DEVBLOCKS_FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC"]
+# the translation units of one build: (source, its defines, object name); the lane-group file once
+# per group kind (Grp, Grp6, Grp18), each well below pipeline.hip's compile time
+DEVBLOCKS_UNITS = [("devblocks_leaf.hip", [], "leaf")] + \
+    [("devblocks_grp.hip", [f"-DDB_GK={k}"], f"grp{k}") for k in range(3)]
+# the two builds: fp.h's default HB_ARG_LANES (64: vbatch.hip, threshold.hip, msm.hip,
+# hashsplit.hip) and pipeline.hip's 128
+DEVBLOCKS_BUILDS = {"64": [], "128": ["-DHB_ARG_LANES=128"]}
+
+
+def devblocks_path(build: str, root: str = "") -> str:
+    return os.path.join(root or ROOT, "tests", "native", f"libhbls_devblocks{build}.so")
+
+
+def devblocks_build_id(build: str = "64", root: str = "") -> str:
+    """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
+    harness, tests/test_gpu_blocks.py): sha256 (16 hex digits) over the harness sources, every
+    header of charon_amd/csrc and the flags of that build -- what its `db_build_id()` returns."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    files = sorted(os.path.join(native, f) for f in os.listdir(native)
+                   if f.startswith("devblocks") and f.endswith((".hip", ".h"))) + \
+        sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+    h = hashlib.sha256()
+    for f in files:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS + DEVBLOCKS_BUILDS[build] + [d for u in DEVBLOCKS_UNITS for d in u[1]]).encode())
+    return DEVBLOCKS_PREFIX + h.hexdigest()[:16]
+
+
+def embedded_devblocks_id(path: str) -> str:
+    """The harness id inside a built device block harness, read from its bytes (no loading)."""
+    import re
+    with open(path, "rb") as f:
+        m = re.search(rb"hbls-devblocks:[0-9a-f]{16}", f.read())
+    return m.group(0).decode() if m else ""
+
+
+def build_devblocks(force: bool = False, verbose: bool = True) -> dict:
+    """Both builds of the device block harness, {"64": path, "128": path}.  A harness whose
+    embedded id equals this tree's is reused; any other -- a header touched, other flags -- is
+    rebuilt.  The translation units of both builds compile in parallel (as build_library's); a
+    unit's time is printed, so that one slower than pipeline.hip shows (split it then)."""
+    ids = {b: devblocks_build_id(b) for b in DEVBLOCKS_BUILDS}
+    paths = {b: devblocks_path(b) for b in DEVBLOCKS_BUILDS}
+    todo = [b for b in DEVBLOCKS_BUILDS
+            if force or not os.path.exists(paths[b]) or embedded_devblocks_id(paths[b]) != ids[b]]
+    if not todo:
+        if verbose:
+            print(f"reused {', '.join(paths.values())}")
+        return paths
+    objdir = os.path.join(HERE, "lib", "devblocks")
+    os.makedirs(objdir, exist_ok=True)
+    t0 = time.time()
+    jobs = []
+    for b in todo:
+        for src, defs, name in DEVBLOCKS_UNITS:
+            obj = os.path.join(objdir, f"{name}_{b}.o")
+            cmd = [HIPCC] + DEVBLOCKS_FLAGS + DEVBLOCKS_BUILDS[b] + defs + \
+                [f'-DDB_BUILD_ID="{ids[b]}"', "-c", os.path.join(ROOT, "tests", "native", src), "-o", obj]
+            jobs.append((b, name, obj, subprocess.Popen(cmd)))
+    pending, took = list(jobs), {}
+    while pending:  # note when each unit finishes
+        for j in list(pending):
+            if j[3].poll() is not None:
+                took[(j[0], j[1])] = time.time() - t0
+                pending.remove(j)
+        if time.time() - t0 > 3000:
+            for j in pending:
+                j[3].kill()
+            raise RuntimeError("hipcc timed out on the device block harness")
+        time.sleep(0.2)
+    if any(j[3].returncode != 0 for j in jobs):
+        raise RuntimeError("hipcc failed on the device block harness")
+    for b in todo:
+        objs = [j[2] for j in jobs if j[0] == b]
+        subprocess.run([HIPCC, "--offload-arch=gfx950", "-shared", "-fPIC", "-o", paths[b] + ".tmp"] + objs +
+                       ["-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=600)
+        os.replace(paths[b] + ".tmp", paths[b])
+    if verbose:
+        units = ", ".join(f"{src}/{b} {s:.0f}s" for (b, src), s in sorted(took.items()))
+        print(f"built {', '.join(paths[b] for b in todo)} in {time.time() - t0:.1f}s ({units})")
+    return paths
+
+
 SANITIZED_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
                    "-fno-sanitize-recover=undefined", "-std=c++17", "-pthread", "-shared", "-fPIC"]
 
@@ -164,7 +255,20 @@ def main(argv=None):
     force = "--force" in (argv or sys.argv[1:])
     build_library(force)
     build_hostcheck(force)
-    build_c_client(force)
+    build_test_extras(force)
+
+
+def build_test_extras(force: bool = False, verbose: bool = True) -> list:
+    """The test-only artefacts the product does not depend on (the C client of the ABI, the device
+    block harness): a failure to build one is printed and returned, never raised."""
+    failed = []
+    for fn in (build_c_client, build_devblocks):
+        try:
+            fn(force, verbose)
+        except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile
+            print(f"WARNING: {fn.__name__} failed ({type(e).__name__}: {e}); the tests that need it will fail")
+            failed.append(fn.__name__)
+    return failed
 
 
 if __name__ == "__main__":

@@ -1,0 +1,400 @@
+"""Python-integer side of tests/test_gpu_blocks.py: the raw-limb formats of the device block harness
+(tests/native/devblocks*.hip), the map between the oracle's Fp12 (oracle/bls12381.py: polynomials in
+w) and pair3.h's lane form, and the case generators.  No GPU here: tests/test_blocks_ref.py checks
+this module on the CPU (the map against hc_pairing, the generators against lazy28.py's model), so
+that a wrong map or an inadmissible input cannot pass for a kernel bug."""
+import itertools
+import random
+
+from charon_amd.tools import lazy28
+from oracle import bls12381 as B
+
+P = B.P
+RBITS = 392
+RM = (1 << RBITS) % P          # the Montgomery representative of 1 (R = 2^392)
+RINV = pow(RM, -1, P)          # a Montgomery product is a b RINV
+M28 = (1 << 28) - 1
+TOP = 2 * P - 1
+
+
+# ---- raw limbs ------------------------------------------------------------------------------
+def words(x):
+    """12 little-endian uint32 of a stored value (< 2^384)"""
+    assert 0 <= x < (1 << 384)
+    return [(x >> (32 * i)) & 0xFFFFFFFF for i in range(12)]
+
+
+def from_words(w):
+    return sum(int(v) << (32 * i) for i, v in enumerate(w))
+
+
+def limbs(x):
+    """the normalised 14 x 28-bit limbs of a lazy value (< 2^392; limb 13 takes what is left)"""
+    assert 0 <= x < (1 << 392)
+    return [(x >> (28 * i)) & M28 for i in range(13)] + [x >> 364]
+
+
+def lvalue(l):
+    return sum(int(v) << (28 * i) for i, v in enumerate(l))
+
+
+def mont(x, upper=False):
+    """the stored representative of the field element x: x R mod p, or that plus p"""
+    return x * RM % P + (P if upper else 0)
+
+
+def unmont(raw):
+    return raw * RINV % P
+
+
+# ---- stored-word edge values (all below 2p) --------------------------------------------------
+def _runs():
+    ones32 = sum(0xFFFFFFFF << (32 * i) for i in range(11))
+    mid32 = sum(0xFFFFFFFF << (32 * i) for i in range(3, 9))
+    ones28 = (1 << 364) - 1
+    top_word, top_limb = (2 * P) >> 352, (2 * P) >> 364
+    return [((top_word - 1) << 352) | ones32,            # words 0..10 all ones
+            ones32,                                       # the same below p, top word 0
+            (0x1234 << 352) | mid32 | 0x89ABCDEF,         # a run of all-ones words in the middle
+            ((top_limb - 1) << 364) | ones28,             # 28-bit limbs 0..12 all ones
+            ones28,
+            (1 << 364) | (ones28 ^ M28)]                  # limb 0 zero below a run of all-ones limbs
+
+
+EDGES = [0, 1, 2, P - 2, P - 1, P, P + 1, TOP, TOP - 1, (1 << 381) - 1, 1 << 380, 2 * P - (1 << 200),
+         RM, RM * RM % P] + _runs()
+assert all(0 <= v < 2 * P for v in EDGES) and len(set(EDGES)) == len(EDGES)
+
+
+def fp_pairs(seed=11, n_random=300):
+    """(a, b) for the one- and two-operand Fp operations: every pair of edge values, then random"""
+    rng = random.Random(seed)
+    return [(a, b) for a in EDGES for b in EDGES] + \
+        [(rng.randrange(2 * P), rng.randrange(2 * P)) for _ in range(n_random)]
+
+
+def fp2_quads(seed=12, n_random=300):
+    """(a0, a1, b0, b1) for the Fp2 product / square and fp_dot2 (a0 b0 +- a1 b1): the operand
+    list of tests/test_hostcheck.py::test_fp2_mul_lazy_bounds over the longer edge list, the
+    combinations that decide the sign correction of the real part -- (x, x, x, x): exactly 0;
+    every choice of 0 / 2p - 1 for the four operands, among them (0, 2p-1, 0, 2p-1), the most
+    negative, and (2p-1, 0, 2p-1, 0), the most positive, and both with the operand pairs
+    swapped -- and random values below 2p"""
+    rng = random.Random(seed)
+    q = [(x, y, u, v) for x in EDGES[::2] for y in EDGES[1::2] for u in (TOP, 0, P) for v in (TOP, 1, P - 1)]
+    q += [(x, x, x, x) for x in EDGES]
+    q += list(itertools.product((0, TOP), repeat=4))
+    q += [(x, P - 1, P - 1, x) for x in EDGES] + [(x, 1, 1, x + 1 if x + 1 < 2 * P else x) for x in EDGES]
+    q += [tuple(rng.randrange(2 * P) for _ in range(4)) for _ in range(n_random)]
+    return q
+
+
+def inv_values(seed=30):
+    """fp_inv wave 1: 64 distinct raw values"""
+    rng = random.Random(seed)
+    v = [0, 1, 2, 3, P - 2, P - 1, (P + 1) // 2, P, P + 1, TOP] + [1 << k for k in range(0, 381, 17)]
+    v += [(1 << 380) - 1, (1 << 380) + 1]
+    v = list(dict.fromkeys(v))
+    while len(v) < 64:
+        x = rng.randrange(2 * P)
+        if x not in v:
+            v.append(x)
+    assert len(v) == 64
+    return v
+
+
+# ---- Fp12: the oracle's polynomial basis <-> pair3.h's lanes ----------------------------------
+# oracle: f = sum_k c_k w^k, k < 12, with w^12 = 2 w^6 - 2, i.e. u = w^6 - 1.  tower.h / pair3.h:
+# f = sum_i z_i w^i, i < 6, z_i = a_i + b_i u in Fp2, so c_i = a_i - b_i and c_{i+6} = b_i (the map of
+# tests/test_hostcheck.py::test_pairing_matches_oracle), and lane k of a group holds
+# A_k = (z_k, z_{k+3}) as the Fp4 x + y s.
+def poly_to_lanes(c):
+    z = [((c[i] + c[i + 6]) % P, c[i + 6] % P) for i in range(6)]
+    return [(z[k][0], z[k][1], z[k + 3][0], z[k + 3][1]) for k in range(3)]
+
+
+def lanes_to_poly(lanes):
+    z = [None] * 6
+    for k in range(3):
+        x0, x1, y0, y1 = lanes[k]
+        z[k], z[k + 3] = (x0, x1), (y0, y1)
+    c = [0] * 12
+    for i in range(6):
+        c[i], c[i + 6] = (z[i][0] - z[i][1]) % P, z[i][1] % P
+    return c
+
+
+def lanes_tower_order(lanes):
+    """the twelve Fp in hc_pairing's order: c0.c0, c0.c1, c0.c2, c1.c0, c1.c1, c1.c2 = z0, z2, z4, z1, z3, z5"""
+    z = {k: lanes[k][:2] for k in range(3)}
+    z.update({k + 3: lanes[k][2:] for k in range(3)})
+    return [v for i in (0, 2, 4, 1, 3, 5) for v in z[i]]
+
+
+def raw_to_poly(raw_lanes):
+    """the Fp12 element whose stored lane form is raw_lanes (3 x 4 raw values below 2p)"""
+    return lanes_to_poly([tuple(unmont(v) for v in lane) for lane in raw_lanes])
+
+
+def poly_to_raw(c, upper=False):
+    return [tuple(mont(v, upper) for v in lane) for lane in poly_to_lanes(c)]
+
+
+def line_poly(a0, a1, b1):
+    """a0 + a1 v + b1 v w (v = w^2) for Fp2 values: z0 = a0, z2 = a1, z3 = b1"""
+    return lanes_to_poly([(a0[0], a0[1], b1[0], b1[1]), (0, 0, 0, 0), (a1[0], a1[1], 0, 0)])
+
+
+def p12_conj(c):
+    """f^(p^6): the automorphism of order two, w -> -w (tests/test_blocks_ref.py compares it with
+    the power)"""
+    return [(-v) % P if k & 1 else v % P for k, v in enumerate(c)]
+
+
+FEXP3 = 3 * B.FINAL_EXP                       # the device chain computes f^(3 (p^12 - 1) / r)
+CYC_EXP = (P ** 6 - 1) * (P ** 2 + 1)         # into the cyclotomic subgroup
+
+
+def group_values(seed=21, n_random=3):
+    """[(name, raw lanes)]: random values, one in both representatives, all coordinates p - 1 and
+    all 2p - 1"""
+    rng = random.Random(seed)
+    out = [("random%d" % i, [tuple(rng.randrange(2 * P) for _ in range(4)) for _ in range(3)]) for i in range(n_random)]
+    out.append(("one", poly_to_raw(B.P12_ONE)))
+    out.append(("one_upper", poly_to_raw(B.P12_ONE, upper=True)))
+    out.append(("all_p-1", [(P - 1,) * 4] * 3))
+    out.append(("all_2p-1", [(TOP,) * 4] * 3))
+    return out
+
+
+def is_one_values():
+    """one in both representatives, and one changed in a single coordinate of a single role (the
+    coordinate 1 changed to 0 and to 2, the others from 0 to 1 and to their upper representative's
+    neighbour p + 1), for each of the six Fp2 coordinates (both halves)"""
+    out = [("one", poly_to_raw(B.P12_ONE), True), ("one_upper", poly_to_raw(B.P12_ONE, upper=True), True),
+           ("one_mixed", [(RM + P, 0, P, 0), (P, 0, 0, P), (0, P, P, 0)], True)]
+    for k in range(3):
+        for j in range(4):
+            for delta, upper in ((1, False), (1, True), (P - 1, False)):
+                lanes = [list(l) for l in poly_to_lanes(B.P12_ONE)]
+                lanes[k][j] = (lanes[k][j] + delta) % P
+                raw = [tuple(mont(v, upper) for v in lane) for lane in lanes]
+                out.append(("one+%d@%d.%d%s" % (delta if delta == 1 else -1, k, j, "u" if upper else ""), raw, False))
+    return out
+
+
+# ---- lazy limbs -------------------------------------------------------------------------------
+# Patterns are built the way ec28.h / pair28.h build them, and every operand set is passed through
+# lazy28.py's model as a degenerate Bound (the concrete limbs, value + 1) before it may be used.
+LAZY_X = [0, 1, 2, P - 2, P - 1, RM, 1 << 380, (1 << 364) - 1, ((P >> 364) << 364) - 1]
+
+
+def bound(l):
+    return lazy28.Bound(l, lvalue(l) + 1)
+
+
+def l_add(a, b):
+    return [x + y for x, y in zip(a, b)]
+
+
+def l_shl(a, s):
+    return [x << s for x in a]
+
+
+def l_sub(a, b, site):
+    """ec28.h l_sub<S, T>: a + (K - b) limb by limb, (S, T) = lazy28.KSITE[site]"""
+    k = lazy28.kconst(*lazy28.KSITE[site])
+    lazy28.sub(bound(a), bound(b), site)  # asserts that K dominates b
+    return [x + (kk - y) for x, kk, y in zip(a, k, b)]
+
+
+def sub_kmax(site, vmax):
+    """the largest k < vmax for which K of `site` dominates every normalised value below (k + 1) p"""
+    k13 = lazy28.kconst(*lazy28.KSITE[site])[13]
+    ks = [k for k in range(vmax) if ((k + 1) * P) >> 364 <= k13]
+    return max(ks) if ks else None
+
+
+def all_ones(k):
+    """the normalised value below (k + 1) p with limbs 0..12 all ones"""
+    return limbs(((((k + 1) * P) >> 364) << 364) - 1)
+
+
+def _sites(prefixes):
+    """one site per distinct constant (S, T) among KSITE's sites of these prefixes"""
+    seen = {}
+    for s, st in lazy28.KSITE.items():
+        if s[0] in prefixes and s != "2N":
+            seen.setdefault(st, s)
+    return list(seen.values())
+
+
+FIELD_SITES = {"Fp": _sites("1"), "Fp2": _sites("234")}
+
+
+def kinds(field):
+    return ["N", "ADD", "SHL1", "SHL2"] + ["SUB:" + s for s in FIELD_SITES[field] if sub_kmax(s, lazy28.VMAX[field]) is not None]
+
+
+def operand(kind, field, pick, pick_sub=None):
+    """one operand of `kind`; pick(kmax) returns the normalised limbs of some x + k p, k <= kmax
+    (pick_sub: the same for a subtrahend)"""
+    vmax = lazy28.VMAX[field]
+    if kind == "N":
+        return pick(vmax - 1)
+    if kind == "ADD":
+        return l_add(pick(vmax - 1), pick(vmax - 1))
+    if kind in ("SHL1", "SHL2"):
+        return l_shl(pick(vmax - 1), int(kind[3]))
+    site = kind[4:]
+    return l_sub(pick(vmax - 1), (pick_sub or pick)(sub_kmax(site, vmax)), site)
+
+
+def worst(kind, field):
+    """the pattern's largest limbs: all-ones operands, a subtrahend of zero"""
+    return operand(kind, field, all_ones, lambda kmax: [0] * 14)
+
+
+def col_max(a, b):
+    """the largest column sum of a_j b_(k-j) (the products' own terms), for ranking patterns"""
+    return max(sum(a[j] * b[k - j] for j in range(max(0, k - 13), min(k, 13) + 1)) for k in range(27))
+
+
+def admits(fn, *args):
+    """does lazy28's model admit this operand set?  Used ONLY to choose which pattern kinds the
+    generators combine (on their worst cases) -- a generated case is never dropped: it is asserted."""
+    try:
+        fn(*args)
+        return True
+    except AssertionError:
+        return False
+
+
+def _picker(rng):
+    def pick(kmax):
+        x = rng.choice(LAZY_X) if rng.random() < 0.4 else rng.randrange(P)
+        k = rng.choice((0, kmax)) if rng.random() < 0.5 else rng.randrange(kmax + 1)
+        return limbs(x + k * P)
+    return pick
+
+
+def _model_f2mul(a0, a1, b0, b1):
+    lazy28.f2_mul((bound(a0), bound(a1)), (bound(b0), bound(b1)), "2N")
+
+
+def _model_f2sqr(site):
+    return lambda a0, a1: lazy28.f2_sqr((bound(a0), bound(a1)), site)
+
+
+def mul_cases(field="Fp", seed=41, per_pair=2):
+    """(a, b) for l_mul / l_mul2 / p_mul2: every pair of pattern kinds whose worst case the model
+    admits, random and edge values in them; first the admitted worst-case pair with the largest
+    column sum"""
+    rng = random.Random(seed)
+    ks = kinds(field)
+    ok = [(ka, kb) for ka in ks for kb in ks if admits(lazy28.mul, bound(worst(ka, field)), bound(worst(kb, field)))]
+    best = max(ok, key=lambda p: col_max(worst(p[0], field), worst(p[1], field)))
+    cases = [(worst(best[0], field), worst(best[1], field))]
+    pick = _picker(rng)
+    for ka, kb in ok:
+        cases.append((worst(ka, field), worst(kb, field)))
+        cases += [(operand(ka, field, pick), operand(kb, field, pick)) for _ in range(per_pair)]
+    for a, b in cases:
+        lazy28.mul(bound(a), bound(b))
+    return cases
+
+
+def sqr_cases(field="Fp", seed=42, per_kind=8):
+    rng = random.Random(seed)
+    ok = [k for k in kinds(field) if admits(lazy28.sqr, bound(worst(k, field)))]
+    best = max(ok, key=lambda k: col_max(worst(k, field), worst(k, field)))
+    cases = [worst(best, field)]
+    pick = _picker(rng)
+    for k in ok:
+        cases.append(worst(k, field))
+        cases += [operand(k, field, pick) for _ in range(per_kind)]
+    for a in cases:
+        lazy28.sqr(bound(a))
+    return cases
+
+
+def f2mul_cases(seed=43, per_pair=3):
+    """(a0, a1, b0, b1) for f2l_mul / fm / fm3 / fm2 (real = a0 b0 + (K - a1) b1, K = KSITE["2N"]):
+    pattern kinds per operand (both coefficients of an operand the same kind, as the formulas
+    produce them), chosen and checked as mul_cases"""
+    rng = random.Random(seed)
+    ks = kinds("Fp2")
+    w = {k: worst(k, "Fp2") for k in ks}
+    ok = [(ka, kb) for ka in ks for kb in ks if admits(_model_f2mul, w[ka], w[ka], w[kb], w[kb])]
+    k2n = lazy28.kconst(*lazy28.KSITE["2N"])
+
+    def cmax(p):
+        a, b = w[p[0]], w[p[1]]
+        na = [kk - x for kk, x in zip(k2n, a)]
+        return max(sum(a[j] * b[k - j] + na[j] * b[k - j] for j in range(max(0, k - 13), min(k, 13) + 1)) for k in range(27))
+    best = max(ok, key=cmax)
+    cases = [(w[best[0]], w[best[0]], w[best[1]], w[best[1]])]
+    pick = _picker(rng)
+    for ka, kb in ok:
+        cases.append((w[ka], w[ka], w[kb], w[kb]))
+        cases += [(operand(ka, "Fp2", pick), operand(ka, "Fp2", pick), operand(kb, "Fp2", pick), operand(kb, "Fp2", pick))
+                  for _ in range(per_pair)]
+    zero = [0] * 14
+    cases += [(w["N"], zero, w["N"], zero), (zero, w["N"], zero, w["N"]), (zero, zero, w["N"], w["N"])]
+    for c in cases:
+        _model_f2mul(*c)
+    return cases
+
+
+SQR_SITES = {(36, 1): "2Q", (78, 1): "3Q", (9, 2): "4Q"}  # the instantiations of f2l_sqr_k / fs / fs3
+assert all(lazy28.KSITE[s] == st for st, s in SQR_SITES.items())
+
+
+def f2sqr_cases(st, seed=44, per_kind=40):
+    """(a0, a1) for f2l_sqr_k<S, T> / fs<S, T> / fs3<S, T>: (a0 + a1)(a0 + K - a1), (2 a0) a1"""
+    site = SQR_SITES[st]
+    model = _model_f2sqr(site)
+    rng = random.Random(seed + st[0])
+    # a1 is a subtrahend of the site's K: operands x + k p only up to the k that K dominates
+    kcap = sub_kmax(site, lazy28.VMAX["Fp2"])
+    ks = kinds("Fp2")
+    zero = [0] * 14
+    w = {k: operand(k, "Fp2", lambda kmax: all_ones(min(kmax, kcap)), lambda kmax: zero) for k in ks}
+    ok = [k for k in ks if admits(model, w[k], w[k])]
+    kk = lazy28.kconst(*st)
+    best = max(ok, key=lambda k: col_max(l_add(w[k], w[k]), [x + (c - y) for x, c, y in zip(w[k], kk, w[k])]))
+    cases = [(w[best], w[best])]
+    rpick = _picker(rng)
+
+    def pick(kmax):
+        return rpick(min(kmax, kcap))
+    for k in ok:
+        cases.append((w[k], w[k]))
+        cases += [(operand(k, "Fp2", pick), operand(k, "Fp2", pick)) for _ in range(per_kind)]
+    cases += [(w["N"], zero), (zero, w["N"]), (zero, zero)]
+    for c in cases:
+        model(*c)
+    return cases
+
+
+def dot_cases(seed=45):
+    """(x0, x1, y0, y1) for l_dot = x0 y0 + x1 y1, as fm(F2Half) / F2Hex feed it from an admitted
+    Fp2 product: (a0, K - a1, b0, b1) for the real part and (a0, a1, b1, b0) for the other"""
+    k2n = lazy28.kconst(*lazy28.KSITE["2N"])
+    out = []
+    for a0, a1, b0, b1 in f2mul_cases(seed):
+        out.append((a0, [k - x for k, x in zip(k2n, a1)], b0, b1))
+        out.append((a0, a1, b1, b0))
+    return out
+
+
+R392_INV = pow(1 << RBITS, -1, P)
+
+
+def check_lazy(r, want_num, cap):
+    """a product's output r (14 limbs): normalised, congruent to want_num / R, and below the bound
+    lazy28.py's model gives it (cap = the operands' integer numerator: r <= cap / R + p)"""
+    assert len(r) == 14 and all(0 <= int(v) < (1 << 28) for v in r[:13]), r
+    v = lvalue(r)
+    assert v % P == want_num * R392_INV % P
+    assert v < cap // (1 << RBITS) + P + 1

@@ -1,0 +1,70 @@
+// TEST-ONLY: what the two translation units of the device block harness share (devblocks_leaf.hip,
+// devblocks_grp.hip): the product headers included exactly as the product's fast translation units
+// include them, and the checked allocate / copy / launch / synchronise / copy-back helpers.
+//
+// The harness is built twice (charon_amd/build.py build_devblocks): with fp.h's default
+// HB_ARG_LANES (64: vbatch.hip, threshold.hip, msm.hip, hashsplit.hip) and with -DHB_ARG_LANES=128
+// (pipeline.hip).  In the 128 build the leaf kernels run 128-thread workgroups, so wave 1 uses the
+// LDS argument slots 64..127 (pipeline.hip k_lml's consumer wave).
+#pragma once
+#define HB_FAST_FPMUL 1
+#include "../../charon_amd/csrc/lines.h"
+#include "../../charon_amd/csrc/pair3.h"
+#include "../../charon_amd/csrc/pair6.h"
+
+// threads per workgroup of the leaf kernels: the build's HB_ARG_LANES (fp.h defines its default in
+// the device pass only, so the default is named here for the host pass and compared below)
+#if defined(HB_ARG_LANES)
+#define DB_BLOCK HB_ARG_LANES
+#else
+#define DB_BLOCK 64
+#endif
+#if defined(__HIP_DEVICE_COMPILE__)
+static_assert(DB_BLOCK == HB_ARG_LANES, "one LDS argument slot per thread of a workgroup");
+#endif
+
+// Return codes of every entry point: 0, or the first failing step
+enum {
+  DB_E_ARG = -1,     // n < 1, a null pointer
+  DB_E_ALLOC = -2,   // hipMalloc
+  DB_E_UPLOAD = -3,  // hipMemcpy host -> device
+  DB_E_CLEAR = -4,   // hipMemset of the output
+  DB_E_LAUNCH = -5,  // the launch itself (hipGetLastError)
+  DB_E_SYNC = -6,    // hipDeviceSynchronize: the kernel's own error
+  DB_E_DOWNLOAD = -7,  // hipMemcpy device -> host
+  DB_E_OP = -10,     // no such operation (for this lane group)
+};
+
+struct DbDev {  // device buffers of one call, freed when it returns
+  void* p[8] = {};
+  int n = 0;
+  ~DbDev() {
+    for (int i = 0; i < n; i++) (void)hipFree(p[i]);
+  }
+  // a device copy of `bytes` bytes of src (src == nullptr: zero-filled)
+  int make(void** out, const void* src, size_t bytes) {
+    if (n >= 8) return DB_E_ARG;
+    if (hipMalloc(out, bytes ? bytes : 4) != hipSuccess) return DB_E_ALLOC;
+    p[n++] = *out;
+    if (src) {
+      if (bytes && hipMemcpy(*out, src, bytes, hipMemcpyHostToDevice) != hipSuccess) return DB_E_UPLOAD;
+    } else if (bytes && hipMemset(*out, 0, bytes) != hipSuccess) {
+      return DB_E_CLEAR;
+    }
+    return 0;
+  }
+};
+#define DB_MAKE(dev, ptr, src, bytes)                                   \
+  do {                                                                  \
+    const int db_rc_ = (dev).make((void**)&(ptr), (src), (bytes));      \
+    if (db_rc_) return db_rc_;                                          \
+  } while (0)
+
+static inline int db_finish() {  // after the launch
+  if (hipGetLastError() != hipSuccess) return DB_E_LAUNCH;
+  if (hipDeviceSynchronize() != hipSuccess) return DB_E_SYNC;
+  return 0;
+}
+static inline int db_fetch(void* dst, const void* src, size_t bytes) {
+  return hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? 0 : DB_E_DOWNLOAD;
+}

@@ -1,7 +1,8 @@
-// TEST-ONLY device harness: runs building blocks of the gfx950 kernels (charon_amd/csrc/*.h,
-// compiled exactly as the product's fast translation units) one lane per case, so
-// tests/test_gpu_blocks.py can compare them with the host harness and the oracle.  The product
-// library never loads this.
+// TEST-ONLY device harness: runs the endomorphism ladders and Jacobian additions of the gfx950
+// kernels (charon_amd/csrc/*.h, compiled exactly as the product's fast translation units) one lane
+// per case.  Built by hand (build_devcheck.sh); no test loads it.  The block
+// harness that tests/test_gpu_blocks.py compares with the oracle is devblocks*.hip, next to this
+// file, built by charon_amd/build.py build_devblocks().  The product library never loads this.
 #define HB_FAST_FPMUL 1
 #include "../../charon_amd/csrc/layout.h"
 #include "../../charon_amd/csrc/rlc.h"

@@ -1,0 +1,96 @@
+"""tests/blocks_ref.py, the Python side of tests/test_gpu_blocks.py, checked on the CPU: the map
+between the oracle's Fp12 and pair3.h's lane form against hc_pairing (so that a wrong map cannot
+pass for a kernel bug), the conjugation shortcut against the power, and the lazy-limb case
+generators against lazy28.py's model and the host build of the same products."""
+import ctypes
+import random
+
+import pytest
+
+import blocks_ref as R
+from charon_amd.tools import lazy28
+from oracle import bls12381 as B
+
+
+@pytest.fixture(scope="module")
+def hc():
+    from charon_amd.build import build_hostcheck
+    return ctypes.CDLL(build_hostcheck(verbose=False))
+
+
+def test_lane_map_matches_hc_pairing(hc):
+    """e(P, Q)^3 of the oracle, taken through poly_to_lanes, is what hc_pairing returns in tower
+    order; the map inverts; raw lanes carry the Montgomery factor"""
+    rng = random.Random(5)
+    a, b = rng.randrange(1, B.R), rng.randrange(1, B.R)
+    Pt, Q = B.g1_mul(B.G1_GEN, a), B.g2_mul(B.G2_GEN, b)
+    o = ctypes.create_string_buffer(576)
+    assert hc.hc_pairing(B.g1_compress(Pt), B.g2_compress(Q), o) == 0
+    ours = [int.from_bytes(o.raw[48 * i:48 * i + 48], "big") for i in range(12)]
+    e = B.pairing(Pt, Q)
+    e3 = B._p12_mul(B._p12_mul(e, e), e)
+    lanes = R.poly_to_lanes(e3)
+    assert R.lanes_tower_order(lanes) == ours
+    assert R.lanes_to_poly(lanes) == e3
+    assert R.raw_to_poly(R.poly_to_raw(e3)) == e3 and R.raw_to_poly(R.poly_to_raw(e3, upper=True)) == e3
+    # the exponents of the GPU test: f^CYC_EXP lies in the cyclotomic subgroup (order p^4 - p^2 + 1),
+    # and FEXP3 is the cube of the oracle's final exponentiation
+    f = [rng.randrange(B.P) for _ in range(12)]
+    assert B._p12_pow(B._p12_pow(f, R.CYC_EXP), B.P ** 4 - B.P ** 2 + 1) == B.P12_ONE
+    assert B._p12_pow(f, R.FEXP3) == B._p12_pow(B.final_exponentiation(f), 3)
+
+
+def test_lane_form_of_one_line_and_conjugate():
+    rng = random.Random(6)
+    assert R.poly_to_lanes(B.P12_ONE) == [(1, 0, 0, 0), (0, 0, 0, 0), (0, 0, 0, 0)]
+    assert R.poly_to_raw(B.P12_ONE, upper=True)[0] == (R.RM + B.P, B.P, B.P, B.P)
+    f = [rng.randrange(B.P) for _ in range(12)]
+    assert R.p12_conj(f) == B._p12_pow(f, B.P ** 6)
+    # a0 + a1 v + b1 v w with v = w^2: the oracle's own embedding of Fp2 times powers of w
+    a0, a1, b1 = [(rng.randrange(B.P), rng.randrange(B.P)) for _ in range(3)]
+    w = [0, 1] + [0] * 10
+    w2 = B._p12_mul(w, w)
+    w3 = B._p12_mul(w2, w)
+    want = B._p12_add(B._fp2_to_p12(a0), B._p12_add(B._p12_mul(B._fp2_to_p12(a1), w2), B._p12_mul(B._fp2_to_p12(b1), w3)))
+    assert R.line_poly(a0, a1, b1) == want
+    # every is-one case but the first three differs from one
+    for name, raw, one in R.is_one_values():
+        assert (R.raw_to_poly(raw) == B.P12_ONE) == one, name
+        assert all(v < 2 * B.P for lane in raw for v in lane)
+
+
+def test_stored_edge_values():
+    assert all(v < 2 * B.P for v in R.EDGES)
+    for want in (0, 1, 2, B.P - 2, B.P - 1, B.P, B.P + 1, 2 * B.P - 1, 2 * B.P - 2, (1 << 381) - 1, 1 << 380,
+                 2 * B.P - (1 << 200), R.RM, R.RM * R.RM % B.P):
+        assert want in R.EDGES
+    assert any(R.words(v)[:11] == [0xFFFFFFFF] * 11 for v in R.EDGES)
+    assert any(R.limbs(v)[:13] == [R.M28] * 13 for v in R.EDGES)
+    q = R.fp2_quads()
+    for c in ((0, R.TOP, 0, R.TOP), (R.TOP, 0, R.TOP, 0), (R.TOP, 0, 0, R.TOP), (0, R.TOP, R.TOP, 0), (R.P,) * 4):
+        assert c in q
+    assert len(set(R.inv_values())) == 64 and {0, B.P, B.P + 1, R.TOP, (B.P + 1) // 2} <= set(R.inv_values())
+    assert R.from_words(R.words(R.TOP)) == R.TOP and R.lvalue(R.limbs(20 * B.P - 1)) == 20 * B.P - 1
+
+
+def test_lazy_generators_are_admitted():
+    """Every generated operand set passes lazy28.py's model (the generators assert it; a rejected
+    one raises here), covers normalised values up to VMAX - 1 multiples of p and un-normalised
+    patterns, and starts with an admitted worst case above 3/4 of the 64-bit accumulator;
+    check_lazy accepts Python's own Montgomery product of such operands."""
+    mul, sqr = R.mul_cases("Fp"), R.sqr_cases("Fp")
+    assert R.col_max(*mul[0]) > 3 << 62 and R.col_max(sqr[0], sqr[0]) > 3 << 62
+    assert any(R.lvalue(a) >= 19 * B.P and max(a) <= R.M28 for a, _ in mul)
+    assert any(max(a) > R.M28 for a, _ in mul) and any(max(a) > R.M28 for a in sqr)
+    with pytest.raises(AssertionError):  # the model does reject: two operands shifted by 3
+        big = R.l_shl(R.all_ones(19), 3)
+        lazy28.mul(R.bound(big), R.bound(big))
+    f2m = R.f2mul_cases()
+    assert any(R.lvalue(c[0]) >= 15 * B.P for c in f2m)
+    for st in R.SQR_SITES:
+        assert len(R.f2sqr_cases(st)) > 40
+    assert len(R.dot_cases()) == 2 * len(f2m)
+    for a, b in mul[:50]:
+        va, vb = R.lvalue(a), R.lvalue(b)
+        m = (-va * vb * pow(B.P, -1, 1 << 392)) % (1 << 392)
+        R.check_lazy(R.limbs((va * vb + m * B.P) >> 392), va * vb, va * vb)

@@ -78,3 +78,37 @@ def test_stale_cpu_harness_is_refused(tmp_path):
     # other flags or defines are another harness
     assert build.hostcheck_build_id(("HB_HOST_MUL28",)) != hid
     assert build.hostcheck_build_id(flags=build.SANITIZED_FLAGS) != hid
+
+
+def test_devblocks_id_tracks_headers_and_harness(tmp_path):
+    """The device block harness (tests/native/devblocks*, tests/test_gpu_blocks.py) carries the
+    hash of its sources, every csrc header and its build's flags (db_build_id): touching a header
+    or a harness source changes it, an unrelated file does not, and the two builds differ.  A
+    harness built here carries its tree's id."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    assert "devblocks_leaf.hip" in mine and "devblocks_grp.hip" in mine and "devblocks.h" in mine
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    ids = {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS}
+    assert ids == {b: build.devblocks_build_id(b) for b in build.DEVBLOCKS_BUILDS}
+    assert len(set(ids.values())) == 2 and all(i.startswith(build.DEVBLOCKS_PREFIX) for i in ids.values())
+    # unrelated files: a product translation unit, the CPU harness, the public header, a new file
+    for rel in ("charon_amd/csrc/pipeline.hip", "tests/native/hostcheck.cpp", "include/hipbls.h"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    (tmp_path / "tests" / "native" / "other.hip").write_text("// other\n")
+    assert build.devblocks_build_id("64", root=root) == ids["64"]
+    for rel in ("charon_amd/csrc/pair28.h", "charon_amd/csrc/fp.h", "tests/native/devblocks_grp.hip",
+                "tests/native/devblocks.h"):
+        before = build.devblocks_build_id("128", root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id("128", root=root) != before, rel
+    assert build.devblocks_build_id("64", root=root) != ids["64"]
+    for b in build.DEVBLOCKS_BUILDS:  # what build() left in the tree, if it is there, is this tree's
+        path = build.devblocks_path(b)
+        if os.path.exists(path) and build.embedded_devblocks_id(path).startswith(build.DEVBLOCKS_PREFIX):
+            assert os.path.basename(path) == f"libhbls_devblocks{b}.so"
