@@ -37,7 +37,7 @@ EXPORTS = (
     "hbls_decompress_pubkeys_device", "hbls_pubkey_cache_add", "hbls_pubkey_cache_clear", "hbls_pubkey_cache_size",
     "hbls_debug_split", "hbls_build_id", "hbls_sig_cache", "hbls_duty_signing_roots",
     "hbls_single_max", "hbls_dec_pair_max", "hbls_tune", "hbls_verify_batch_first_error",
-    "hbls_verify_device_first_error",
+    "hbls_verify_device_first_error", "hbls_key_learn_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -135,6 +135,7 @@ def _declare(lib):
         "hbls_pubkey_cache_add": ([P, SZ], ctypes.c_int),
         "hbls_pubkey_cache_clear": ([], ctypes.c_int),
         "hbls_pubkey_cache_size": ([], SZ),
+        "hbls_key_learn_stats": ([P, SZ, P], ctypes.c_int),
         "hbls_debug_split": ([U32], ctypes.c_int),
         "hbls_slot_device": ([ctypes.POINTER(HblsSlot), P], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
@@ -210,6 +211,16 @@ def timing_read(L, max_n: int = 1 << 16):
     n = ctypes.c_size_t(0)
     check(L.hbls_timing_read(names, ms, max_n, ctypes.byref(n)))
     return [(names[i].decode(), float(ms[i])) for i in range(n.value)]
+
+
+def key_learn_stats(L, max_devices: int = 32):
+    """Per device of the mask: {size, capacity, hits, misses} of the learned key cache
+    (hbls_key_learn_stats; waits for the library's enqueued work)."""
+    out = (ctypes.c_uint64 * (4 * max_devices))()
+    n = ctypes.c_size_t(0)
+    check(L.hbls_key_learn_stats(out, max_devices, ctypes.byref(n)))
+    return [dict(zip(("size", "capacity", "hits", "misses"), (int(v) for v in out[4 * k:4 * k + 4])))
+            for k in range(n.value)]
 
 
 def check(rc: int):

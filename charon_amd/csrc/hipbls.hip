@@ -315,6 +315,7 @@ enum WsId {
   W_MCNT, W_MOFF, W_MCUR, W_MORDER, W_MENT, W_MBUCKET, W_MPART, W_MPART2, W_MTOT, W_PBUF1, W_PBUF2, W_PBUF3, W_SFAIL,  // slot-wide check
   W_MLEV,                                                                          // its evaluated Miller lines
   W_PFIN, W_TBUF, W_F1, W_F1BAD, W_F1S, W_FIRST,                                                                  // final exponentiations' factors
+  W_KLMISS, W_KLCNT,  // learned key cache: the call's missing keys (partials' keys, then DV keys) and their two counts
   W_COUNT_
 };
 
@@ -335,6 +336,7 @@ struct Ws {
   hipEvent_t ev_pk = nullptr;  // the partials' keys decompressed (side 0, before the DV keys)
   hipEvent_t ev_dec = nullptr;  // the partials' signatures decompressed (side 1, before their subgroup checks)
   hipEvent_t ev_h = nullptr;  // host calls: the hashing done (before the messages' lines)
+  hipEvent_t ev_dflt = nullptr;  // hbls_slot_device: the device's default stream when the call was made
 };
 
 // host-call staging buffers (inputs and outputs of the host-buffer entry points)
@@ -414,6 +416,23 @@ struct Dev {
   // kc_n entries indexed, kc_tcap slots (a power of two >= 2 kc_n)
   DevBuf kc_keys, kc_hidx;
   size_t kc_n = 0, kc_tcap = 0;
+  // learned key cache (vbatch.hip k_pk_lookup / k_pk_learn; kl_table, kl_keys below): what the device
+  // entry points have decompressed, found again by the keys' bytes.  kl_cap entries allocated and
+  // emptied (0: not yet, or dropped by a reset); kl_ctr stays for the device's lifetime.
+  DevBuf kl_keys, kl_ent, kl_st, kl_idx, kl_ctr;
+  size_t kl_cap = 0, kl_tcap = 0;
+  // ORDERING INVARIANT of the learned key cache.  Every kernel that touches the table runs on the
+  // side stream 0 of some workspace set, enqueued under `mu`, in the order
+  //     wait(kl_ev); k_pk_lookup ...; k_pk_learn ...; record(kl_ev)
+  // so the table's reads and writes are totally ordered across calls, whatever streams and
+  // workspace sets the calls use: lookup 1, learn 1, lookup 2, learn 2, ...  Visibility comes from
+  // kernel boundaries alone; no kernel ever runs beside a writer of what it reads, and no
+  // cross-kernel memory-ordering argument is needed.  (Slots enqueued back to back from cold
+  // therefore decompress each key once.)  Anything that rewrites the table from the host side
+  // (kl_reset) first drains the library's streams under `mu`.  Keep every new reader or writer
+  // inside this chain.
+  hipEvent_t kl_ev = nullptr;  // after the last call's k_pk_learn
+  bool kl_ev_set = false;
   // decompressed-signature cache (vbatch.hip k_sc_write / k_sc_index / k_sc_get): filled by host-buffer Verify
   // batches, read by host-buffer ThresholdAggregate batches; enqueued under `mu` like everything
   // else.  A put runs on its host-call context's own put stream, off the Verify call's critical
@@ -451,6 +470,12 @@ struct Dev {
 // of two; 0 = off).  2^21 (two C3 slots of partials): 2 M x 305 B = 640 MB per device.
 std::atomic<size_t> g_sc_cap{size_t(1) << 21};
 uint64_t g_sc_k0 = 0x243f6a8885a308d3ull, g_sc_k1 = 0x13198a2e03707344ull;  // keyed hash (getrandom at init)
+// HBLS_KEY_LEARN / hbls_tune: entries of each device's learned key cache (0 = off).  2^21: the
+// smallest power of two above the largest per-GPU key set of BASELINE.json (C3: 1.0 M pubshares +
+// 0.1 M DV keys); 2 M x 149 B = 312 MB plus a 16 MB index per device, allocated by the first call
+// that uses it.
+std::atomic<size_t> g_key_learn{size_t(1) << 21};
+constexpr size_t KEY_LEARN_MAX = size_t(1) << 30;
 
 std::mutex g_init_mu;
 std::vector<Dev*> g_devs;  // in device-mask order (hbls_debug_split: each ordinal repeated); g_devs_mu
@@ -566,9 +591,11 @@ int dev_create(int ord, Dev** out) {
     HCHK(hipEventCreateWithFlags(&w.ev_h, hipEventDisableTiming));
     HCHK(hipEventCreateWithFlags(&w.ev_pk, hipEventDisableTiming));
     HCHK(hipEventCreateWithFlags(&w.ev_dec, hipEventDisableTiming));
+    HCHK(hipEventCreateWithFlags(&w.ev_dflt, hipEventDisableTiming));
     HCHK(hipStreamCreateWithPriority(&d->hc[k_ws].s, hipStreamNonBlocking, prio_lo));
     HCHK(hipEventCreateWithFlags(&d->hc[k_ws].ev, hipEventDisableTiming));
   }
+  HCHK(hipEventCreateWithFlags(&d->kl_ev, hipEventDisableTiming));
   HCHK(hipHostMalloc((void**)&d->res_host, N_RES * sizeof(SlotRes), hipHostMallocDefault));
   for (unsigned k = 0; k < N_RES; k++) HCHK(hipEventCreateWithFlags(&d->res_ev[k], hipEventDisableTiming));
   *out = d;
@@ -609,6 +636,7 @@ int init_mask(uint32_t mask) {
   g_hash_one_lane = env_size("HBLS_HASH_ONE_LANE", g_hash_one_lane.load());
   g_hash_split = env_size("HBLS_HASH_SPLIT", 1) != 0;
   g_fe18_max = env_size("HBLS_FE18_MAX", g_fe18_max.load());
+  g_key_learn = std::min(env_size("HBLS_KEY_LEARN", g_key_learn.load()), KEY_LEARN_MAX);
   g_ws_sets = (int)std::min<size_t>(N_WS_MAX, std::max<size_t>(1, env_size("HBLS_WS_SETS", 3)));
   {
     size_t sc = env_size("HBLS_SIG_CACHE", g_sc_cap.load());
@@ -869,6 +897,77 @@ int ta_tail(Dev& d, Ws& w, const HmEntry* pts, const uint32_t* src, const uint8_
   return 0;
 }
 
+// Every launch the library enqueued on its own streams (the library stream, the host-call
+// contexts' and the workspaces' side streams) has completed -- not the whole device: caller, torch
+// and RCCL streams keep running.  Caller holds d.mu, so nothing new is enqueued meanwhile.
+int drain_lib_streams(Dev& d) {
+  HCHK(hipStreamSynchronize(d.stream));
+  for (int k = 0; k < N_WS_MAX; k++) {
+    if (d.hc[k].s) HCHK(hipStreamSynchronize(d.hc[k].s));
+    for (int j = 0; j < N_SIDE; j++)
+      if (d.ws[k].side[j]) HCHK(hipStreamSynchronize(d.ws[k].side[j]));
+  }
+  return 0;
+}
+
+// ---- learned key cache (Dev::kl_*; kernels in vbatch.hip).  All under d.mu.
+// Empty the table (hbls_pubkey_cache_clear, a new HBLS_KEY_LEARN): its readers and writers all
+// run on workspace side streams, drained first; the next call that uses the cache allocates and
+// zeroes it again.  The hit and miss counters keep counting.
+int kl_reset(Dev& d, bool release) {
+  if (!d.kl_cap && !release) return 0;
+  HCHK(hipSetDevice(d.ord));
+  if (drain_lib_streams(d)) return -1;
+  d.kl_cap = d.kl_tcap = 0;
+  d.kl_ev_set = false;
+  if (release)
+    for (DevBuf* b : {&d.kl_keys, &d.kl_ent, &d.kl_st, &d.kl_idx}) {
+      if (b->p) HCHK(hipFree(b->p));
+      *b = DevBuf{};
+    }
+  return 0;
+}
+// The table at the current capacity, allocated and emptied on stream ss (a side stream 0, inside
+// the ordering chain of Dev::kl_ev) when there is none; t->cap == 0: the cache is off.
+int kl_table(Dev& d, hipStream_t ss, KeyLearnTab* t) {
+  *t = KeyLearnTab{};
+  const size_t cap = g_key_learn.load();
+  if (!cap) return 0;
+  if (d.kl_cap != cap) {
+    if (kl_reset(d, false)) return -1;
+    size_t tcap = 2;  // a power of two >= 2 cap: load <= 1/2
+    while (tcap < 2 * cap) tcap *= 2;
+    void* p;
+    const bool first = d.kl_ctr.p == nullptr;
+    if (ensure_buf(d.kl_keys, 48 * cap, &p) || ensure_buf(d.kl_ent, cap * sizeof(G1AEntry), &p) ||
+        ensure_buf(d.kl_st, cap, &p) || ensure_buf(d.kl_idx, tcap * sizeof(uint32_t), &p) ||
+        ensure_buf(d.kl_ctr, sizeof(KeyLearnCtr), &p))
+      return -1;
+    if (first) HCHK(hipMemsetAsync(d.kl_ctr.p, 0, sizeof(KeyLearnCtr), ss));
+    HCHK(hipMemsetAsync(d.kl_idx.p, 0, tcap * sizeof(uint32_t), ss));
+    HCHK(hipMemsetAsync(&((KeyLearnCtr*)d.kl_ctr.p)->size, 0, sizeof(uint32_t), ss));
+    d.kl_cap = cap;
+    d.kl_tcap = tcap;
+  }
+  t->keys = (uint8_t*)d.kl_keys.p;
+  t->ent = (G1AEntry*)d.kl_ent.p;
+  t->st = (uint8_t*)d.kl_st.p;
+  t->idx = (uint32_t*)d.kl_idx.p;
+  t->ctr = (KeyLearnCtr*)d.kl_ctr.p;
+  t->cap = (uint32_t)d.kl_cap;
+  t->tcap = (uint32_t)d.kl_tcap;
+  return 0;
+}
+// The keys of one array through the cache on ss: hits copied, the misses listed at miss[0 ..
+// *mcount) and decompressed there (labelled k_pk_miss, not k_dec_pk: with every key cached these
+// launches are empty, and a per-key rate computed from them would mean nothing)
+int kl_keys(Dev& d, const KeyLearnTab& t, const uint8_t* pks, size_t n, G1AEntry* out, uint8_t* st, uint32_t* miss,
+            uint32_t* mcount, hipStream_t ss) {
+  TIMED(d, "k_pk_lookup", ss, launch_pk_lookup(t, pks, (uint32_t)n, g_sc_k0, g_sc_k1, out, st, miss, mcount, ss));
+  TIMED(d, "k_pk_miss", ss, launch_pk_miss(pks, (uint32_t)n, miss, mcount, out, st, ss));
+  return 0;
+}
+
 // defer_hm / defer_msgs: the caller hashed the defer_msgs messages at defer_hm (the call's messages
 // or a contiguous range of them) without their Miller lines (callers whose messages have about one
 // verification group each, batched final exponentiation sizes): the slot-wide check evaluates each
@@ -993,7 +1092,25 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
   HCHK(hipEventRecord(w.ev_fork, s));
   for (int k = 0; k < 2; k++) HCHK(hipStreamWaitEvent(w.side[k], w.ev_fork, 0));
   // public keys: from the caller's decompressed-key tables when given (static per cluster lock:
-  // decompressed and subgroup-checked once), else decompressed here
+  // decompressed and subgroup-checked once); device calls without tables through the learned key
+  // cache (hits copied, misses decompressed and, behind the key side, learned); else decompressed
+  // here
+  // (the lookup loads a key as three 16-byte words: a caller's array that is not 16-byte aligned
+  // takes the plain decompression)
+  const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
+  const bool learn_pk = !kc && !(fold && fold->pk_table) && n && al16(dpk);
+  const bool learn_dv = !kc && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
+  KeyLearnTab kl{};
+  uint32_t *kmiss = nullptr, *kcnt = nullptr;
+  if (learn_pk || learn_dv) {
+    // the ordering chain of Dev::kl_ev: behind the last call's k_pk_learn
+    if (d.kl_ev_set) HCHK(hipStreamWaitEvent(w.side[0], d.kl_ev, 0));
+    if (kl_table(d, w.side[0], &kl)) return -1;
+    if (kl.cap) {
+      if (wsbuf(w, W_KLMISS, n + n_agg, &kmiss) || wsbuf(w, W_KLCNT, 2, &kcnt)) return -1;
+      HCHK(hipMemsetAsync(kcnt, 0, 2 * sizeof(uint32_t), w.side[0]));
+    }
+  }
   if (fold && fold->pk_table) {
     vpk = const_cast<G1AEntry*>(fold->pk_table);
     vpkst = const_cast<uint8_t*>(fold->pk_table_st);
@@ -1002,6 +1119,8 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
           launch_pk_cached(dpk, (uint32_t)n, (const uint8_t*)d.kc_keys.p, (const G1AEntry*)d.kc_tab.p,
                            (const uint8_t*)d.kc_st.p, (const uint32_t*)d.kc_hidx.p, (uint32_t)d.kc_tcap, g_sc_k0,
                            g_sc_k1, vpk, vpkst, w.side[0]));
+  } else if (learn_pk && kl.cap) {
+    if (kl_keys(d, kl, dpk, n, vpk, vpkst, kmiss, kcnt, w.side[0])) return -1;
   } else {
     TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(dpk, (uint32_t)n, vpk, vpkst, w.side[0]));
   }
@@ -1009,12 +1128,29 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
   if (n_agg && fold->dv_pk_table) {
     apk = const_cast<G1AEntry*>(fold->dv_pk_table);
     apkst = const_cast<uint8_t*>(fold->dv_pk_table_st);
+  } else if (learn_dv && kl.cap) {
+    if (kl_keys(d, kl, fold->dv_pks, n_agg, apk, apkst, kmiss + n, kcnt + 1, w.side[0])) return -1;
   } else if (n_agg) {
     TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(fold->dv_pks, (uint32_t)n_agg, apk, apkst, w.side[0]));
   }
   TIMED(d, "k_dec_sig_pt", w.side[1], launch_dec_sig_pt(dsig, (uint32_t)n, vsig, vsigst, w.side[1], nullptr, w.ev_dec));
   HCHK(hipEventRecord(w.ev_side[0], w.side[0]));
   HCHK(hipEventRecord(w.ev_side[1], w.side[1]));
+  // the misses into the table, behind everything that waits for the keys; the next call's lookup
+  // (on any workspace set) waits for kl_ev, and so does the end of this call: k_pk_learn reads the
+  // caller's key bytes and this set's buffers
+  const bool learned = kl.cap != 0;
+  if (learned) {
+    if (learn_pk)
+      TIMED(d, "k_pk_learn", w.side[0],
+            launch_pk_learn(kl, dpk, (uint32_t)n, kmiss, kcnt, g_sc_k0, g_sc_k1, vpk, vpkst, w.side[0]));
+    if (learn_dv)
+      TIMED(d, "k_pk_learn", w.side[0],
+            launch_pk_learn(kl, fold->dv_pks, (uint32_t)n_agg, kmiss + n, kcnt + 1, g_sc_k0, g_sc_k1, apk, apkst,
+                            w.side[0]));
+    HCHK(hipEventRecord(d.kl_ev, w.side[0]));
+    d.kl_ev_set = true;
+  }
 
   // the slot's ThresholdAggregate on side 3 (needs the decompressed partials when it reuses them)
   const bool ta = fold && fold->n_groups;
@@ -1484,6 +1620,7 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
   if (ta && !n_agg) {  // the aggregation ran beside the verification: join it
     HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));
   }
+  if (learned) HCHK(hipStreamWaitEvent(s, d.kl_ev, 0));  // (recorded by this call: d.mu is still held)
   if (stats_on()) {  // HBLS_STATS=1: count the fallback items (synchronises; tests and diagnosis)
     uint32_t c = 0;
     HCHK(hipMemcpyAsync(&c, count, sizeof(c), hipMemcpyDeviceToHost, s));
@@ -1638,12 +1775,7 @@ int kc_fill(Dev& d, const uint8_t* keys, size_t first, size_t m) {
   // any entry is rewritten or the table moves -- not the whole device: caller, torch and RCCL
   // streams keep running.  No new reader can be enqueued meanwhile (they look indices up under
   // d.mu, held here); cache adds are rare (cluster locks).
-  HCHK(hipStreamSynchronize(d.stream));
-  for (int k = 0; k < N_WS_MAX; k++) {
-    if (d.hc[k].s) HCHK(hipStreamSynchronize(d.hc[k].s));
-    for (int j = 0; j < N_SIDE; j++)
-      if (d.ws[k].side[j]) HCHK(hipStreamSynchronize(d.ws[k].side[j]));
-  }
+  if (drain_lib_streams(d)) return -1;
   const size_t tot = first + m;
   if (d.kc_tab.cap < tot * sizeof(G1AEntry) || d.kc_st.cap < tot) {  // grow, keeping the old entries
     DevBuf nt, ns;
@@ -2789,6 +2921,7 @@ int hbls_pubkey_cache_clear(void) {
     std::lock_guard<std::mutex> dl(dp->mu);
     dp->kc_n = 0;
     dp->kc_tcap = 0;  // the next fill builds a fresh index
+    if (kl_reset(*dp, false)) return -1;  // the learned keys too
   }
   std::lock_guard<std::mutex> lk(g_kc_mu);
   g_kc_map.clear();
@@ -2800,6 +2933,29 @@ int hbls_pubkey_cache_clear(void) {
 size_t hbls_pubkey_cache_size(void) {
   std::lock_guard<std::mutex> lk(g_kc_mu);
   return g_kc_n;
+}
+
+int hbls_key_learn_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
+  if (ensure_init()) return -1;
+  if (!out || !n_devices) return set_err("hbls_key_learn_stats: null arguments");
+  size_t k = 0;
+  for (Dev* d : devs()) {
+    if (k == max_devices) break;
+    std::lock_guard<std::mutex> lk(d->mu);
+    HCHK(hipSetDevice(d->ord));
+    KeyLearnCtr c{};
+    if (d->kl_ctr.p) {  // the counters of everything enqueued so far
+      if (drain_lib_streams(*d)) return -1;
+      HCHK(hipMemcpy(&c, d->kl_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    out[4 * k + 0] = d->kl_cap ? std::min<uint64_t>(c.size, d->kl_cap) : 0;
+    out[4 * k + 1] = g_key_learn.load();
+    out[4 * k + 2] = c.hits;
+    out[4 * k + 3] = c.misses;
+    k++;
+  }
+  *n_devices = k;
+  return 0;
 }
 
 // Test switch of the in-process multi-device split: every device of the mask is driven through
@@ -2904,6 +3060,15 @@ int hbls_slot_device(const hbls_slot* a, void* stream) {
                    "aggregation group");
   std::lock_guard<std::mutex> lk(d->mu);
   Ws& w = ws_acquire(*d, s);
+  // The slot starts writing the caller's hm at once, on a side stream: the staged hashing keeps
+  // its hand-over values in hm's line area (hashsplit.hip).  A caller that prepared its buffers on
+  // the device's default stream (a zero fill of hm, say) and passes a non-blocking stream has not
+  // ordered that work before this call; a blocking stream would have.  The call therefore runs
+  // behind what the default stream holds now: one event, nothing to wait for when it is idle.
+  if (s) {
+    HCHK(hipEventRecord(w.ev_dflt, nullptr));
+    HCHK(hipStreamWaitEvent(s, w.ev_dflt, 0));
+  }
   HCHK(hipEventRecord(w.ev_fork, s));
   // messages: hash + Miller lines (side 2)
   hipStream_t sh = w.side[2];
@@ -2983,6 +3148,17 @@ int hbls_tune(const char* name, size_t value, size_t* previous) {
       // chunking of large verifications (tests run them at small sizes: several chunks per call)
       {"HBLS_GROUP_CHUNK", &g_gcap},            {"HBLS_FALLBACK_CHUNK", &g_fbcap},
       {"HBLS_GROUP_MAX", &g_gmax}};
+  if (strcmp(name, "HBLS_KEY_LEARN") == 0) {  // a new capacity starts from an empty table (0: freed)
+    value = std::min(value, KEY_LEARN_MAX);
+    const size_t old = g_key_learn.exchange(value);
+    if (previous) *previous = old;
+    if (old != value)
+      for (Dev* d : devs()) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        if (kl_reset(*d, value == 0)) return -1;
+      }
+    return 0;
+  }
   for (const auto& k : knobs)
     if (strcmp(k.first, name) == 0) {
       const size_t old = k.second->exchange(value);

@@ -226,6 +226,26 @@ void launch_kc_index(const uint8_t* keys, uint32_t first, uint32_t m, uint32_t* 
 void launch_pk_cached(const uint8_t* pks, uint32_t n, const uint8_t* keys, const G1AEntry* tabe, const uint8_t* tst,
                       const uint32_t* tab, uint32_t tcap, uint64_t k0, uint64_t k1, G1AEntry* out, uint8_t* st,
                       hipStream_t s);
+// Learned key cache (vbatch.hip k_pk_lookup, k_pk_miss_dec, k_pk_miss_subgroup, k_pk_learn): one
+// table per device; its counters live on the device (hbls_key_learn_stats reads them).
+struct KeyLearnCtr {
+  unsigned long long hits, misses;  // keys looked up, cumulative
+  uint32_t size, pad;               // entries taken (the last wave of a filling call may count past cap)
+};
+struct KeyLearnTab {
+  uint8_t* keys;  // 48 bytes per entry
+  G1AEntry* ent;
+  uint8_t* st;
+  uint32_t* idx;  // tcap slots: entry + 1, 0 = empty
+  KeyLearnCtr* ctr;
+  uint32_t cap, tcap;
+};
+void launch_pk_lookup(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, uint64_t k0, uint64_t k1, G1AEntry* out,
+                      uint8_t* st, uint32_t* miss, uint32_t* mcount, hipStream_t s);
+void launch_pk_miss(const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount, G1AEntry* out,
+                    uint8_t* st, hipStream_t s);
+void launch_pk_learn(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount,
+                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, hipStream_t s);
 // Chunk plans and the multi-scalar random linear combination (vbatch.hip k_plan_*, k_rlc_msm).
 constexpr uint32_t RLC_CHUNK = 16;  // items per lane of k_rlc_msm
 struct RlcMsmArgs {

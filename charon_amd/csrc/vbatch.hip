@@ -45,10 +45,8 @@ __global__ KB void k_item_group(const uint32_t* __restrict__ grp_off, uint32_t n
 // One lane per partial: decompress + subgroup-check the public key (herumi.go:290
 // PublicKey.Deserialize).  A rejected key is replaced by g1 so later stages run the same
 // arithmetic on well-formed values; its status byte decides the verdict.
-__global__ KB_OCC(HB_OCC_DECPK) void k_dec_pk(const uint8_t* __restrict__ pks, uint32_t n, G1AEntry* __restrict__ out,
-                            uint8_t* __restrict__ st) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void dec_pk_lane(const uint8_t* __restrict__ pks, uint32_t i, G1AEntry* __restrict__ out,
+                                            uint8_t* __restrict__ st) {
   G1A p;
   uint8_t bad = g1_decompress(p, pks + 48ull * i, false);  // the subgroup check: k_g1_subgroup
   if (bad) p = g1_generator();
@@ -60,13 +58,17 @@ __global__ KB_OCC(HB_OCC_DECPK) void k_dec_pk(const uint8_t* __restrict__ pks, u
   out[i] = e;
   st[i] = bad;
 }
+__global__ KB_OCC(HB_OCC_DECPK) void k_dec_pk(const uint8_t* __restrict__ pks, uint32_t n, G1AEntry* __restrict__ out,
+                            uint8_t* __restrict__ st) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  dec_pk_lane(pks, i, out, st);
+}
 
 // The subgroup check of k_dec_pk's points, a kernel of its own like k_g2_subgroup (the fused
 // kernel spilled the square root's window table beside the ladder).  The ladders run in lazily
 // reduced 28-bit limbs (ec28.h g1_in_subgroup28 / g2_in_subgroup28_l).
-__global__ KB_OCC(HB_OCC_SUBG) void k_g1_subgroup(uint32_t n, G1AEntry* __restrict__ pts, uint8_t* __restrict__ st) {
-  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
+__device__ __forceinline__ void g1_subgroup_lane(uint32_t i, G1AEntry* __restrict__ pts, uint8_t* __restrict__ st) {
   const G1AEntry e = pts[i];
   if (st[i] || e.inf) return;
   if (!g1_in_subgroup28(G1A{e.x, e.y, false})) {
@@ -79,6 +81,11 @@ __global__ KB_OCC(HB_OCC_SUBG) void k_g1_subgroup(uint32_t n, G1AEntry* __restri
     pts[i] = z;
     st[i] = 1;
   }
+}
+__global__ KB_OCC(HB_OCC_SUBG) void k_g1_subgroup(uint32_t n, G1AEntry* __restrict__ pts, uint8_t* __restrict__ st) {
+  uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  g1_subgroup_lane(i, pts, st);
 }
 
 // One lane per signature: decompress + subgroup-check (herumi.go:295 / :257 Sign.Deserialize),
@@ -324,6 +331,105 @@ __global__ KB_OCC(HB_OCC_DECPK) void k_pk_cached(const uint8_t* __restrict__ pks
   e.pad[0] = e.pad[1] = e.pad[2] = 0;
   out[i] = e;
   st[i] = bad;
+}
+
+// ---- learned key cache (Dev::kl_*, hipbls.hip kl_table / kl_keys): the device entry points' own memory of
+// the keys they have decompressed -- a charon node's pubshares and DV keys are fixed by its cluster
+// lock, so after the first slot every key is a hit.  KeyLearnTab: `cap` entries (compressed bytes,
+// the final entry and status as k_dec_pk + k_g1_subgroup leave them), appended in order of
+// ctr->size and never removed, and an open-addressing index of tcap >= 2 cap slots (entry + 1,
+// 0 = empty) probed linearly from kc_hash of the bytes.  A hit compares all 48 bytes, so a status
+// is a pure function of the key's bytes.  The host orders the kernels of consecutive calls
+// (lookup, learn, lookup, learn, ...), so no kernel here runs beside a writer of what it reads.
+__device__ __forceinline__ bool kc_key_eq(const uint4* a, const uint4* b) {
+  bool eq = true;
+  HB_UNROLL for (int j = 0; j < 3; j++) eq = eq && a[j].x == b[j].x && a[j].y == b[j].y && a[j].z == b[j].z && a[j].w == b[j].w;
+  return eq;
+}
+// One lane per key: a hit copies the entry and status, a miss appends the key's position to
+// miss[] (one atomicAdd on *mcount per wave).  No decompression here: the misses are compacted so
+// that a wave never waits for a few missing lanes' square roots and ladders.
+__global__ __launch_bounds__(64) void k_pk_lookup(KeyLearnTab t, const uint8_t* __restrict__ pks, uint32_t n,
+                                                  uint64_t k0, uint64_t k1, G1AEntry* __restrict__ out,
+                                                  uint8_t* __restrict__ st, uint32_t* __restrict__ miss,
+                                                  uint32_t* __restrict__ mcount) {
+  const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = i < n;
+  bool hit = false;
+  if (in) {
+    uint4 kb[3];
+    kc_key_load(pks + 48ull * i, kb);
+    const uint32_t home = kc_hash(kb, k0, k1) & (t.tcap - 1);
+    for (uint32_t q = 0; q < t.tcap; q++) {  // load factor <= 1/2: an empty slot ends the probe
+      const uint32_t v = t.idx[(home + q) & (t.tcap - 1)];
+      if (v == 0) break;
+      uint4 ke[3];
+      kc_key_load(t.keys + 48ull * (v - 1), ke);
+      if (kc_key_eq(ke, kb)) {
+        out[i] = t.ent[v - 1];
+        st[i] = t.st[v - 1];
+        hit = true;
+        break;
+      }
+    }
+  }
+  const uint64_t mm = __ballot(in && !hit), hm = __ballot(hit);
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = 0;
+  if (lane == 0) {
+    if (mm) {
+      base = atomicAdd(mcount, (uint32_t)__popcll(mm));
+      atomicAdd(&t.ctr->misses, (unsigned long long)__popcll(mm));
+    }
+    if (hm) atomicAdd(&t.ctr->hits, (unsigned long long)__popcll(hm));
+  }
+  base = __shfl(base, 0);
+  if (in && !hit) miss[base + __popcll(mm & ((1ull << lane) - 1))] = i;
+}
+// The misses, one lane per listed key (the count is read on the device: at most n lanes run, all
+// but *mcount of them exit at once): k_dec_pk's and k_g1_subgroup's arithmetic on keys miss[j]
+__global__ KB_OCC(HB_OCC_DECPK) void k_pk_miss_dec(const uint8_t* __restrict__ pks, const uint32_t* __restrict__ miss,
+                                                   const uint32_t* __restrict__ mcount, G1AEntry* __restrict__ out,
+                                                   uint8_t* __restrict__ st) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= *mcount) return;
+  dec_pk_lane(pks, miss[j], out, st);
+}
+__global__ KB_OCC(HB_OCC_SUBG) void k_pk_miss_subgroup(const uint32_t* __restrict__ miss,
+                                                       const uint32_t* __restrict__ mcount, G1AEntry* __restrict__ pts,
+                                                       uint8_t* __restrict__ st) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  if (j >= *mcount) return;
+  g1_subgroup_lane(miss[j], pts, st);
+}
+// The misses' final entries into the table: a lane takes the next entry (one atomicAdd on the
+// size per wave), writes the bytes, the entry and the status, then claims an index slot.  A full
+// table takes nothing more (no eviction).  A key listed twice in one call takes two entries; the
+// lookup finds whichever comes first on its probe path, and both hold the same value.
+__global__ __launch_bounds__(64) void k_pk_learn(KeyLearnTab t, const uint8_t* __restrict__ pks,
+                                                 const uint32_t* __restrict__ miss, const uint32_t* __restrict__ mcount,
+                                                 uint64_t k0, uint64_t k1, const G1AEntry* __restrict__ pts,
+                                                 const uint8_t* __restrict__ st) {
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool in = j < *mcount;
+  const uint64_t am = __ballot(in);
+  if (!am) return;
+  const uint32_t lane = threadIdx.x & 63u;
+  uint32_t base = t.cap;
+  // (the size is read first so that calls against a full table leave it where it is)
+  if (lane == 0 && t.ctr->size < t.cap) base = atomicAdd(&t.ctr->size, (uint32_t)__popcll(am));
+  base = __shfl(base, 0);
+  const uint32_t e = base + __popcll(am & ((1ull << lane) - 1));
+  if (!in || base >= t.cap || e >= t.cap) return;
+  const uint32_t i = miss[j];
+  uint4 kb[3];
+  kc_key_load(pks + 48ull * i, kb);
+  HB_UNROLL for (int q = 0; q < 3; q++) ((uint4*)(t.keys + 48ull * e))[q] = kb[q];
+  t.ent[e] = pts[i];
+  t.st[e] = st[i];
+  const uint32_t home = kc_hash(kb, k0, k1) & (t.tcap - 1);
+  for (uint32_t q = 0; q < t.tcap; q++)  // load factor <= 1/2: a free slot exists
+    if (atomicCAS(&t.idx[(home + q) & (t.tcap - 1)], 0u, e + 1) == 0u) return;
 }
 
 // the random coefficient r = a + b lambda of entry `item` (SHA-256 of key || item, one block)
@@ -745,6 +851,22 @@ void launch_pk_cached(const uint8_t* pks, uint32_t n, const uint8_t* keys, const
   if (n)
     hipLaunchKernelGGL(k_pk_cached, dim3(blocks_for(n)), dim3(BLOCK), 0, s, pks, n, keys, tabe, tst, tab, tcap, k0, k1,
                        out, st);
+}
+void launch_pk_lookup(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, uint64_t k0, uint64_t k1, G1AEntry* out,
+                      uint8_t* st, uint32_t* miss, uint32_t* mcount, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_pk_lookup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, n, k0, k1, out, st, miss, mcount);
+}
+// (the subgroup checks one lane per key whatever HBLS_DEC_PAIR_MAX says: the lane-pair layout is
+// for calls whose few keys are all the device has to do, and here most keys are hits)
+void launch_pk_miss(const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount, G1AEntry* out,
+                    uint8_t* st, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pk_miss_dec, dim3(blocks_for(n)), dim3(BLOCK), 0, s, pks, miss, mcount, out, st);
+  hipLaunchKernelGGL(k_pk_miss_subgroup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, miss, mcount, out, st);
+}
+void launch_pk_learn(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount,
+                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, hipStream_t s) {
+  if (n) hipLaunchKernelGGL(k_pk_learn, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, miss, mcount, k0, k1, pts, st);
 }
 void launch_dec_sig_pt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip,
                        hipEvent_t decoded) {

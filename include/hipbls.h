@@ -144,8 +144,28 @@ int hbls_duty_signing_roots(int kind, const uint8_t* data, const uint64_t* off, 
  * lock at startup (cluster/lock.go; the keys never change while it runs).  Statuses and verdicts
  * are unchanged: an undecodable cached key still yields HBLS_BAD_PUBKEY. */
 int hbls_pubkey_cache_add(const uint8_t* pks, size_t n);
-int hbls_pubkey_cache_clear(void);
+int hbls_pubkey_cache_clear(void); /* also empties the learned key cache below */
 size_t hbls_pubkey_cache_size(void);
+/* Learned key cache of the device entry points (hbls_slot_device, hbls_verify_device,
+ * hbls_verify_device_first_error without key tables): each device remembers the public keys those
+ * calls decompressed -- compressed bytes -> decompressed entry and status, found again by a keyed
+ * hash and a compare of all 48 bytes -- and later calls copy the entries instead of repeating the
+ * square root and the subgroup ladder; only keys not seen before are decompressed, then learned.
+ * Nothing for the caller to manage: a node's pubshares and DV keys are fixed by its cluster lock
+ * (cluster/lock.go), so from its second slot on every key is found.  Statuses and outputs are
+ * byte-identical with or without it (a status is a function of the key's bytes alone).  The table
+ * holds HBLS_KEY_LEARN entries (environment at init, or hbls_tune; default 2^21, about 0.33 GB per
+ * device, allocated by the first call that uses it; 0 = off), is append-only and never evicts: a
+ * full table keeps what it has and further new keys are decompressed in every call.  Consecutive
+ * calls are ordered on the device (a call's lookup runs after the previous call's inserts), so
+ * slots enqueued back to back from a cold start decompress each key once.  Not used by calls that
+ * pass pk_table / dv_pk_table, by the host-buffer calls (hbls_pubkey_cache_add serves those), by
+ * hbls_decompress_pubkeys_device or by VerifyAggregate.
+ * hbls_key_learn_stats: for each device of the mask (at most max_devices; *n_devices receives the
+ * number written) four values: out[4k] entries held, out[4k+1] capacity, out[4k+2] keys found and
+ * out[4k+3] keys decompressed, both cumulative since init.  Waits for the library's enqueued work
+ * on each device. */
+int hbls_key_learn_stats(uint64_t* out, size_t max_devices, size_t* n_devices);
 /* Decompressed-signature cache (new, no herumi counterpart): hbls_verify_batch keeps the
  * decompressed, subgroup-checked points of the partials it verified (a ring of `entries` per
  * device, keyed by all 96 bytes), and hbls_threshold_aggregate_batch takes its members from it
@@ -236,7 +256,10 @@ int hbls_verify_aggregate_device(const uint8_t* pks, const uint32_t* grp_off, si
  *     verify each aggregate under the validator's DV public key (sigagg.go:117) into
  *     agg_vstatus, folded into group g's combined check.  agg_vstatus[g] is the aggregation
  *     status when no aggregate was produced.
- * Semantics per item as hbls_verify_batch / hbls_threshold_aggregate_batch. */
+ * Semantics per item as hbls_verify_batch / hbls_threshold_aggregate_batch.
+ * Ordering: the call's work runs behind what `stream` holds and, because it starts writing hm on
+ * its own side streams at once, also behind what the device's default stream holds when the call
+ * is made (buffers filled there need no extra synchronisation, as with a blocking stream). */
 typedef struct hbls_slot {
   const uint8_t* msgs;
   const uint64_t* msg_off;
@@ -263,7 +286,8 @@ typedef struct hbls_slot {
   /* Optional decompressed-key tables (hbls_decompress_pubkeys_device): when non-NULL the slot
    * reads entry i of pk_table (status pk_table_st[i]) instead of decompressing pks[i], and
    * entry g of dv_pk_table instead of dv_pks[g].  Pubshares are static per cluster lock, so a
-   * node decompresses and subgroup-checks them once (SURVEY.md 8e pubshare cache). */
+   * node decompresses and subgroup-checks them once (SURVEY.md 8e pubshare cache).  Without
+   * tables the learned key cache (hbls_key_learn_stats above) does the same by itself. */
   const void* pk_table;
   const uint8_t* pk_table_st;
   const void* dv_pk_table;
@@ -314,8 +338,9 @@ size_t hbls_dec_pair_max(size_t items);
  * "HBLS_HASH_SPLIT" (0: the unstaged hashing kernels), "HBLS_FE18_MAX", "HBLS_TA_PAIR_MAX",
  * "HBLS_DEC_PAIR_MAX"; the chunking of large verifications "HBLS_GROUP_CHUNK" (groups per pairing
  * chunk), "HBLS_FALLBACK_CHUNK" (items per fallback pass), "HBLS_GROUP_MAX" (items per group of a
- * host call).  *previous (if not NULL) receives the old value.  Returns 0, or -1 for an unknown
- * name. */
+ * host call); "HBLS_KEY_LEARN" (entries of the learned key cache, 0 = off: a new value empties the
+ * table after waiting for the library's enqueued work).  *previous (if not NULL) receives the old
+ * value.  Returns 0, or -1 for an unknown name. */
 int hbls_tune(const char* name, size_t value, size_t* previous);
 /* Tuning: the random linear combination's public-key side groups a verification group's items
  * into shared-doubling chunks sized to keep about `lanes` lanes busy (at most 16 items per chunk;
