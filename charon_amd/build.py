@@ -149,6 +149,23 @@ DEVBLOCKS_UNITS = [("devblocks_leaf.hip", [], "leaf")] + \
 # the two builds: fp.h's default HB_ARG_LANES (64: vbatch.hip, threshold.hip, msm.hip,
 # hashsplit.hip) and pipeline.hip's 128
 DEVBLOCKS_BUILDS = {"64": [], "128": ["-DHB_ARG_LANES=128"]}
+# The curve layer (tests/test_gpu_curve.py) is a harness of its own, libhbls_devblockscurve.so, with
+# an id of its own: the curve kernels use fp.h's default HB_ARG_LANES only, and the block harnesses
+# above neither change nor rebuild when a curve source does.  Its units: the point operations of G1
+# and G2, the ladders, and the bucket MSM, whose unit compiles the product's msm.hip itself
+# (DEVBLOCKS_PRODUCT_SOURCES: hashed into the id).
+DEVBLOCKS_CURVE = "curve"
+DEVBLOCKS_CURVE_UNITS = [("devblocks_curve.hip", [f"-DDB_CV={k}"], f"cv{k}") for k in (1, 2, 3)] + \
+    [("devblocks_msm.hip", [], "msm")]
+DEVBLOCKS_PRODUCT_SOURCES = ["msm.hip"]
+
+
+def devblocks_units(build: str) -> list:
+    return DEVBLOCKS_CURVE_UNITS if build == DEVBLOCKS_CURVE else DEVBLOCKS_UNITS
+
+
+def devblocks_flags(build: str) -> list:
+    return [] if build == DEVBLOCKS_CURVE else DEVBLOCKS_BUILDS[build]
 
 
 def devblocks_path(build: str, root: str = "") -> str:
@@ -157,21 +174,32 @@ def devblocks_path(build: str, root: str = "") -> str:
 
 def devblocks_build_id(build: str = "64", root: str = "") -> str:
     """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
-    harness, tests/test_gpu_blocks.py): sha256 (16 hex digits) over the harness sources, every
-    header of charon_amd/csrc and the flags of that build -- what its `db_build_id()` returns."""
+    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py): sha256 (16 hex digits) over the
+    harness sources, every header of charon_amd/csrc and the flags of that build -- what its
+    `db_build_id()` returns.  The block builds ("64", "128") hash every tests/native/devblocks* file
+    but the curve harness's sources; the curve harness hashes its own sources, the shared
+    devblocks*.h and the product sources its units compile themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
     import hashlib
     root = root or ROOT
     csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    files = sorted(os.path.join(native, f) for f in os.listdir(native)
-                   if f.startswith("devblocks") and f.endswith((".hip", ".h"))) + \
+    curve_src = {u[0] for u in DEVBLOCKS_CURVE_UNITS}
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    if build == DEVBLOCKS_CURVE:
+        mine = [f for f in mine if f.endswith(".h")] + sorted(curve_src)
+    else:
+        mine = [f for f in mine if f not in curve_src]
+    files = [os.path.join(native, f) for f in mine] + \
         sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+    if build == DEVBLOCKS_CURVE:
+        files += [os.path.join(csrc, f) for f in DEVBLOCKS_PRODUCT_SOURCES]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.relpath(f, root).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())
         h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS + DEVBLOCKS_BUILDS[build] + [d for u in DEVBLOCKS_UNITS for d in u[1]]).encode())
+    tag = [DEVBLOCKS_CURVE] if build == DEVBLOCKS_CURVE else []
+    h.update(" ".join(DEVBLOCKS_FLAGS + devblocks_flags(build) + [d for u in devblocks_units(build) for d in u[1]] + tag).encode())
     return DEVBLOCKS_PREFIX + h.hexdigest()[:16]
 
 
@@ -183,14 +211,16 @@ def embedded_devblocks_id(path: str) -> str:
     return m.group(0).decode() if m else ""
 
 
-def build_devblocks(force: bool = False, verbose: bool = True) -> dict:
-    """Both builds of the device block harness, {"64": path, "128": path}.  A harness whose
-    embedded id equals this tree's is reused; any other -- a header touched, other flags -- is
-    rebuilt.  The translation units of both builds compile in parallel (as build_library's); a
-    unit's time is printed, so that one slower than pipeline.hip shows (split it then)."""
-    ids = {b: devblocks_build_id(b) for b in DEVBLOCKS_BUILDS}
-    paths = {b: devblocks_path(b) for b in DEVBLOCKS_BUILDS}
-    todo = [b for b in DEVBLOCKS_BUILDS
+def build_devblocks(force: bool = False, verbose: bool = True, builds=None) -> dict:
+    """The builds of the device block harness, {"64": path, "128": path} (builds: others, e.g.
+    [DEVBLOCKS_CURVE]).  A harness whose embedded id equals this tree's is reused; any other -- a
+    header touched, other flags -- is rebuilt.  The translation units of all builds compile in
+    parallel (as build_library's); a unit's time is printed, so that one slower than pipeline.hip
+    shows (split it then)."""
+    builds = list(builds if builds is not None else DEVBLOCKS_BUILDS)
+    ids = {b: devblocks_build_id(b) for b in builds}
+    paths = {b: devblocks_path(b) for b in builds}
+    todo = [b for b in builds
             if force or not os.path.exists(paths[b]) or embedded_devblocks_id(paths[b]) != ids[b]]
     if not todo:
         if verbose:
@@ -201,9 +231,9 @@ def build_devblocks(force: bool = False, verbose: bool = True) -> dict:
     t0 = time.time()
     jobs = []
     for b in todo:
-        for src, defs, name in DEVBLOCKS_UNITS:
+        for src, defs, name in devblocks_units(b):
             obj = os.path.join(objdir, f"{name}_{b}.o")
-            cmd = [HIPCC] + DEVBLOCKS_FLAGS + DEVBLOCKS_BUILDS[b] + defs + \
+            cmd = [HIPCC] + DEVBLOCKS_FLAGS + devblocks_flags(b) + defs + \
                 [f'-DDB_BUILD_ID="{ids[b]}"', "-c", os.path.join(ROOT, "tests", "native", src), "-o", obj]
             jobs.append((b, name, obj, subprocess.Popen(cmd)))
     pending, took = list(jobs), {}
@@ -228,6 +258,16 @@ def build_devblocks(force: bool = False, verbose: bool = True) -> dict:
         units = ", ".join(f"{src}/{b} {s:.0f}s" for (b, src), s in sorted(took.items()))
         print(f"built {', '.join(paths[b] for b in todo)} in {time.time() - t0:.1f}s ({units})")
     return paths
+
+
+def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
+    """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
+    return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
+
+
+def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
+    """The block harnesses and the curve harness, their units compiled side by side"""
+    return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + [DEVBLOCKS_CURVE])
 
 
 SANITIZED_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",
@@ -262,7 +302,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_devblocks):
+    for fn in (build_c_client, build_devblocks_all):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -398,3 +398,143 @@ def check_lazy(r, want_num, cap):
     v = lvalue(r)
     assert v % P == want_num * R392_INV % P
     assert v < cap // (1 << RBITS) + P + 1
+
+
+# ---- curve layer (tests/native/devblocks_curve.hip, devblocks_msm.hip; tests/test_gpu_curve.py) ----
+# A group element is the oracle's: an affine tuple (x, y) of field elements (Fp: int, Fp2: (c0, c1))
+# or None.  A raw point is (slots, inf): six raw integers X.c0, X.c1, Y.c0, Y.c1, Z.c0, Z.c1 (G1 fills
+# the c0 slots), each the Montgomery representative plus a multiple of p, and the `inf` flag.
+FIELD_OPS = {1: B._FpOps, 2: B._Fp2Ops}
+CURVE_B = {1: B.B_G1, 2: B.B_G2}
+PT_WORDS, PT_INF = 88, 84
+
+
+def fcoords(field, v):
+    """the Fp coordinates of a field element, as a pair (c0, c1)"""
+    return (v, 0) if field == 1 else tuple(v)
+
+
+def felem(field, c0, c1):
+    return c0 % P if field == 1 else (c0 % P, c1 % P)
+
+
+def frand(field, rng, nonzero=True):
+    while True:
+        v = rng.randrange(P) if field == 1 else (rng.randrange(P), rng.randrange(P))
+        if not nonzero or v not in (0, (0, 0)):
+            return v
+
+
+def jac_coords(field, pt, lam):
+    """the Jacobian representative (X, Y, Z) = (x lam^2, y lam^3, lam) of an affine point; infinity
+    as (1, 1, 0), what ec.h jac_infinity holds"""
+    F = FIELD_OPS[field]
+    if pt is None:
+        return F.one, F.one, F.zero
+    l2 = F.mul(lam, lam)
+    return F.mul(pt[0], l2), F.mul(pt[1], F.mul(l2, lam)), lam
+
+
+def raw_slots(field, coords, ks=0):
+    """raw integers of three field elements: mont(c) + k p, k from ks (an int, or six of them)"""
+    ks = [ks] * 6 if isinstance(ks, int) else list(ks)
+    flat = [c for v in coords for c in fcoords(field, v)]
+    return [mont(c) + k * P for c, k in zip(flat, ks)]
+
+
+def affine_of(field, slots, inf=False):
+    """the group element of raw Jacobian slots (any multiples of p on top): None if flagged or Z = 0"""
+    F = FIELD_OPS[field]
+    X, Y, Z = (felem(field, unmont(slots[2 * k]), unmont(slots[2 * k + 1])) for k in range(3))
+    if inf or Z == F.zero:
+        return None
+    zi = F.inv(Z)
+    zi2 = F.mul(zi, zi)
+    return F.mul(X, zi2), F.mul(Y, F.mul(zi2, zi))
+
+
+def pack_point(slots, inf, lazy):
+    """one 88-word point record: 14 limbs (lazy) or 12 words per slot"""
+    rec = [0] * PT_WORDS
+    for k, v in enumerate(slots):
+        w = limbs(v) if lazy else words(v)
+        rec[14 * k:14 * k + len(w)] = w
+    rec[PT_INF] = 1 if inf else 0
+    return rec
+
+
+def unpack_point(rec, lazy):
+    """(slots, inf, normalised) of an output record"""
+    rec = [int(v) for v in rec]
+    if lazy:
+        sl = [lvalue(rec[14 * k:14 * k + 14]) for k in range(6)]
+        normalised = all(v <= M28 for k in range(6) for v in rec[14 * k:14 * k + 13])
+    else:
+        sl = [from_words(rec[14 * k:14 * k + 12]) for k in range(6)]
+        normalised = True
+    return sl, rec[PT_INF] != 0, normalised
+
+
+def entry_words(field, coords, inf=None, upper=False):
+    """the stored words of a product record (layout.h): the field elements' Montgomery words in
+    order, then -- for the affine records G1AEntry / HmEntry -- the inf flag and three words of padding"""
+    out = []
+    for v in coords:
+        for c in fcoords(field, v)[:field]:
+            out += words(mont(c, upper))
+    if inf is not None:
+        out += [1 if inf else 0, 0, 0, 0]
+    return out
+
+
+def affine_entry(field, pt, upper=False):
+    """G1AEntry (28 words) / HmEntry (52 words) of a group element"""
+    F = FIELD_OPS[field]
+    return entry_words(field, (F.zero, F.zero) if pt is None else pt, inf=pt is None, upper=upper)
+
+
+def jac_entry(field, pt, lam=None, upper=False):
+    """G1JEntry (36 words) / G2JEntry (72 words): the representative with Z = lam (default 1)"""
+    return entry_words(field, jac_coords(field, pt, FIELD_OPS[field].one if lam is None else lam), upper=upper)
+
+
+def entry_affine(field, w):
+    """the group element of a Jacobian record's words"""
+    vals = [from_words(w[12 * k:12 * k + 12]) for k in range(3 * field)]
+    slots = vals if field == 2 else [vals[0], 0, vals[1], 0, vals[2], 0]
+    return affine_of(field, slots)
+
+
+def load_torsion():
+    """tests/golden/torsion_points.json as {1: [...], 2: [...]} of (kind, q, order, group element)"""
+    import json
+    import os
+    doc = json.load(open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "torsion_points.json")))
+    out = {}
+    for field, g, dec in ((1, "g1", B.g1_decompress), (2, "g2", B.g2_decompress)):
+        out[field] = [(e["kind"], int(e["q"]), int(e["order"]), dec(bytes.fromhex(e["point"]), subgroup_check=False))
+                      for e in doc[g]["points"]]
+    return out
+
+
+def ec_add(field, a, b):
+    return B.ec_add(a, b, FIELD_OPS[field])
+
+
+def ec_mul(field, a, k):
+    return B.ec_mul(a, k, FIELD_OPS[field])
+
+
+def ec_neg(field, a):
+    return B.ec_neg(a, FIELD_OPS[field])
+
+
+def msm_reference(points, coefs):
+    """sum_i [a_i] s_i + [b_i] (-psi^2 s_i) with the oracle's group law, term by term"""
+    total = None
+    for pt, (a, b) in zip(points, coefs):
+        if pt is None:
+            continue
+        total = B.g2_add(total, B.g2_mul(pt, a))
+        total = B.g2_add(total, B.g2_mul(B.g2_neg(B.g2_psi(B.g2_psi(pt))), b))
+    return total

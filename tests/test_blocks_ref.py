@@ -94,3 +94,50 @@ def test_lazy_generators_are_admitted():
         va, vb = R.lvalue(a), R.lvalue(b)
         m = (-va * vb * pow(B.P, -1, 1 << 392)) % (1 << 392)
         R.check_lazy(R.limbs((va * vb + m * B.P) >> 392), va * vb, va * vb)
+
+
+@pytest.mark.parametrize("field", [1, 2])
+def test_curve_point_formats(field):
+    """the raw point formats of the curve harness: every representative of a group element (any Z,
+    any admitted multiple of p on top, lazy limbs or stored words) decodes to that element, the
+    product records have layout.h's sizes, and infinity is Z = 0 mod p or the flag"""
+    rng = random.Random(70 + field)
+    g = B.G1_GEN if field == 1 else B.G2_GEN
+    pt = R.ec_mul(field, g, 0xABCDEF)
+    vmax = lazy28.VMAX["Fp" if field == 1 else "Fp2"]
+    for lazy, kmax in ((True, vmax - 1), (False, 1)):
+        for _ in range(4):
+            lam = R.frand(field, rng)
+            slots = R.raw_slots(field, R.jac_coords(field, pt, lam), [rng.randrange(kmax + 1) for _ in range(6)])
+            assert all(v < (kmax + 1) * B.P for v in slots)
+            got, inf, normalised = R.unpack_point(R.pack_point(slots, False, lazy), lazy)
+            assert got == slots and not inf and normalised and R.affine_of(field, got) == pt
+    for k in (0, 1):
+        assert R.affine_of(field, R.raw_slots(field, R.jac_coords(field, None, None), k)) is None
+    assert R.affine_of(field, R.raw_slots(field, R.jac_coords(field, pt, R.FIELD_OPS[field].one)), inf=True) is None
+    assert len(R.affine_entry(field, pt)) == (28, 52)[field - 1] and R.affine_entry(field, None)[-4] == 1
+    assert len(R.jac_entry(field, pt)) == 36 * field
+    assert R.entry_affine(field, R.jac_entry(field, pt, R.frand(field, rng), upper=True)) == pt
+    assert R.entry_affine(field, R.jac_entry(field, None, upper=True)) is None
+
+
+def test_msm_reference_is_linear():
+    """-psi^2 is an endomorphism: the term-by-term MSM reference equals the sum taken in scalars over
+    a base point (what tests/test_gpu_curve.py uses for its larger inputs)"""
+    q = B.g2_mul(B.G2_GEN, 987654321)
+    img = B.g2_neg(B.g2_psi(B.g2_psi(q)))
+    ms, coefs = [3, 5, 3, 70000], [(0x10001, 0xFFFF0000), (7, 0), (0, 9), (0xFFFFFFFF, 0x80000001)]
+    want = B.g2_add(B.g2_mul(q, sum(m * a for m, (a, _) in zip(ms, coefs))),
+                    B.g2_mul(img, sum(m * b for m, (_, b) in zip(ms, coefs))))
+    assert R.msm_reference([B.g2_mul(q, m) for m in ms], coefs) == want
+    assert R.msm_reference([q, None], [(0, 0), (5, 5)]) is None
+
+
+def test_torsion_fixture_loads():
+    t = R.load_torsion()
+    assert {q for _, q, _, _ in t[1]} >= {3, 11} and {q for _, q, _, _ in t[2]} >= {13, 23}
+    for field in (1, 2):
+        for kind, q, order, pt in t[field]:
+            assert B.ec_is_on_curve(pt, R.FIELD_OPS[field], R.CURVE_B[field])
+            if kind in ("T", "-T"):
+                assert order == q

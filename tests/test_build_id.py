@@ -112,3 +112,46 @@ def test_devblocks_id_tracks_headers_and_harness(tmp_path):
         path = build.devblocks_path(b)
         if os.path.exists(path) and build.embedded_devblocks_id(path).startswith(build.DEVBLOCKS_PREFIX):
             assert os.path.basename(path) == f"libhbls_devblocks{b}.so"
+
+
+def test_curve_harness_id_is_its_own(tmp_path):
+    """The curve harness (tests/native/devblocks_curve.hip, devblocks_msm.hip; tests/test_gpu_curve.py)
+    carries an id of its own: its sources, the shared devblocks.h, every csrc header and the product
+    source its MSM unit compiles itself (msm.hip) change it; an unrelated file does not.  The block
+    harnesses' ids do not move with a curve source or msm.hip, so they are neither stale nor rebuilt
+    when only the curve layer's harness changes -- and every devblocks*.hip belongs to one of them."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    curve = build.DEVBLOCKS_CURVE
+    assert {u[0] for u in build.devblocks_units(curve)} == {"devblocks_curve.hip", "devblocks_msm.hip"}
+    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve] for u in build.devblocks_units(b)} == \
+        {f for f in mine if f.endswith(".hip")}  # every source is built
+    cid = build.devblocks_build_id(curve, root=root)
+    assert cid == build.devblocks_build_id(curve) and cid.startswith(build.DEVBLOCKS_PREFIX)
+    blocks = {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS}
+    assert cid not in blocks.values()
+    for rel in ("charon_amd/csrc/pipeline.hip", "tests/native/hostcheck.cpp", "include/hipbls.h",
+                "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    assert build.devblocks_build_id(curve, root=root) == cid
+    blocks = {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS}
+    for rel in ("tests/native/devblocks_curve.hip", "tests/native/devblocks_msm.hip", "charon_amd/csrc/msm.hip"):
+        before = build.devblocks_build_id(curve, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(curve, root=root) != before, rel
+        assert {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS} == blocks, rel
+    for rel in ("tests/native/devblocks.h", "charon_amd/csrc/ec28.h", "charon_amd/csrc/fp.h"):
+        before = build.devblocks_build_id(curve, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(curve, root=root) != before, rel
+    path = build.devblocks_path(curve)
+    assert os.path.basename(path) == "libhbls_devblockscurve.so"
+    if os.path.exists(path):  # what build() left in the tree is this tree's
+        assert build.embedded_devblocks_id(path) == build.devblocks_build_id(curve)

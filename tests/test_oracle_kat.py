@@ -88,3 +88,47 @@ def test_off_subgroup_fixture():
         x = (int.from_bytes(b[48:], "big"), int.from_bytes(bytes([b[0] & 0x1F]) + b[1:48], "big"))
         y = B.f2_sqrt(B.f2_add(B.f2_mul(B.f2_sqr(x), x), B.B_G2))
         assert y is not None and not B.g2_in_subgroup((x, y))
+
+
+def _torsion_entries():
+    import json
+    import os
+    doc = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "torsion_points.json")))
+    return [(g, e) for g in ("g1", "g2") for e in doc[g]["points"]]
+
+
+def test_torsion_fixture_covers_every_cofactor_prime():
+    """tests/golden/torsion_points.json: the recorded factorisations multiply to the cofactors (h1
+    the oracle's, h2 from the curve parameter), and every prime of each has T, -T and G+T."""
+    import json
+    import os
+    doc = json.load(open(os.path.join(os.path.dirname(__file__), "golden", "torsion_points.json")))
+    x = B.X_PARAM
+    h2 = (x ** 8 - 4 * x ** 7 + 5 * x ** 6 - 4 * x ** 4 + 6 * x ** 3 - 4 * x ** 2 - 4 * x + 13) // 9
+    for g, h in (("g1", B.H1), ("g2", h2)):
+        prod = 1
+        for q, e in doc[g]["factors"]:
+            prod *= int(q) ** e
+        assert prod == h == int(doc[g]["cofactor"])
+        for q, _ in doc[g]["factors"]:
+            kinds = sorted(e["kind"] for e in doc[g]["points"] if e["q"] == q and e["kind"] != "T2")
+            assert kinds == ["-T", "G+T", "T"], (g, q)
+        assert sorted(e["q"] for e in doc[g]["points"] if e["kind"] == "T2") == sorted(doc[g]["q2_found"])
+
+
+@pytest.mark.parametrize("g,e", _torsion_entries(), ids=lambda v: v if isinstance(v, str) else v["kind"] + "/" + v["q"][:9])
+def test_torsion_fixture(g, e):
+    """every entry: on the curve, of exactly the recorded order ([order] pt = O, [order / q] pt != O),
+    outside the subgroup, and refused by the decompressor"""
+    dec, mul, insub = (B.g1_decompress, B.g1_mul, B.g1_in_subgroup) if g == "g1" else \
+        (B.g2_decompress, B.g2_mul, B.g2_in_subgroup)
+    raw = bytes.fromhex(e["point"])
+    pt = dec(raw, subgroup_check=False)  # raises unless x is on the curve
+    assert pt is not None
+    q, order = int(e["q"]), int(e["order"])
+    assert order % q == 0
+    assert mul(pt, order) is None
+    assert mul(pt, order // q) is not None
+    assert not insub(pt)
+    with pytest.raises(B.DecodeError):
+        dec(raw)
