@@ -157,15 +157,24 @@ DEVBLOCKS_BUILDS = {"64": [], "128": ["-DHB_ARG_LANES=128"]}
 DEVBLOCKS_CURVE = "curve"
 DEVBLOCKS_CURVE_UNITS = [("devblocks_curve.hip", [f"-DDB_CV={k}"], f"cv{k}") for k in (1, 2, 3)] + \
     [("devblocks_msm.hip", [], "msm")]
-DEVBLOCKS_PRODUCT_SOURCES = ["msm.hip"]
+# Hash-to-curve (tests/test_gpu_hash.py) is a third harness, libhbls_devblockshash.so, on the same
+# terms: the fast-convention unit in two parts (1: the stages, compiling the product's hashsplit.hip
+# itself; 2: the leaves) and the standard-convention unit (as hash.hip is compiled).
+DEVBLOCKS_HASH = "hash"
+DEVBLOCKS_HASH_UNITS = [("devblocks_h2c.hip", [f"-DDB_H2C={k}"], f"h2c{k}") for k in (1, 2)] + \
+    [("devblocks_h2c_std.hip", [], "h2cstd")]
+# the product sources a harness's units compile themselves, hashed into that harness's id
+DEVBLOCKS_PRODUCT_SOURCES = {DEVBLOCKS_CURVE: ["msm.hip"], DEVBLOCKS_HASH: ["hashsplit.hip"]}
+# the harnesses with a library and an id of their own, next to the block builds
+DEVBLOCKS_OWN = {DEVBLOCKS_CURVE: DEVBLOCKS_CURVE_UNITS, DEVBLOCKS_HASH: DEVBLOCKS_HASH_UNITS}
 
 
 def devblocks_units(build: str) -> list:
-    return DEVBLOCKS_CURVE_UNITS if build == DEVBLOCKS_CURVE else DEVBLOCKS_UNITS
+    return DEVBLOCKS_OWN.get(build, DEVBLOCKS_UNITS)
 
 
 def devblocks_flags(build: str) -> list:
-    return [] if build == DEVBLOCKS_CURVE else DEVBLOCKS_BUILDS[build]
+    return [] if build in DEVBLOCKS_OWN else DEVBLOCKS_BUILDS[build]
 
 
 def devblocks_path(build: str, root: str = "") -> str:
@@ -174,31 +183,32 @@ def devblocks_path(build: str, root: str = "") -> str:
 
 def devblocks_build_id(build: str = "64", root: str = "") -> str:
     """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
-    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py): sha256 (16 hex digits) over the
-    harness sources, every header of charon_amd/csrc and the flags of that build -- what its
-    `db_build_id()` returns.  The block builds ("64", "128") hash every tests/native/devblocks* file
-    but the curve harness's sources; the curve harness hashes its own sources, the shared
-    devblocks*.h and the product sources its units compile themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
+    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py): sha256 (16 hex
+    digits) over the harness sources, every header of charon_amd/csrc and the flags of that build --
+    what its `db_build_id()` returns.  The block builds ("64", "128") hash every
+    tests/native/devblocks* file but the sources of the curve and hash harnesses; each of those two
+    hashes its own sources, the shared devblocks*.h and the product sources its units compile
+    themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
     import hashlib
     root = root or ROOT
     csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    curve_src = {u[0] for u in DEVBLOCKS_CURVE_UNITS}
+    own_src = {u[0] for units in DEVBLOCKS_OWN.values() for u in units}
     mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
-    if build == DEVBLOCKS_CURVE:
-        mine = [f for f in mine if f.endswith(".h")] + sorted(curve_src)
+    if build in DEVBLOCKS_OWN:
+        mine = [f for f in mine if f.endswith(".h")] + sorted({u[0] for u in DEVBLOCKS_OWN[build]})
     else:
-        mine = [f for f in mine if f not in curve_src]
+        mine = [f for f in mine if f not in own_src]
     files = [os.path.join(native, f) for f in mine] + \
         sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
-    if build == DEVBLOCKS_CURVE:
-        files += [os.path.join(csrc, f) for f in DEVBLOCKS_PRODUCT_SOURCES]
+    if build in DEVBLOCKS_OWN:
+        files += [os.path.join(csrc, f) for f in DEVBLOCKS_PRODUCT_SOURCES[build]]
     h = hashlib.sha256()
     for f in files:
         h.update(os.path.relpath(f, root).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())
         h.update(b"\0")
-    tag = [DEVBLOCKS_CURVE] if build == DEVBLOCKS_CURVE else []
+    tag = [build] if build in DEVBLOCKS_OWN else []
     h.update(" ".join(DEVBLOCKS_FLAGS + devblocks_flags(build) + [d for u in devblocks_units(build) for d in u[1]] + tag).encode())
     return DEVBLOCKS_PREFIX + h.hexdigest()[:16]
 
@@ -265,9 +275,14 @@ def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
 
 
+def build_devblocks_hash(force: bool = False, verbose: bool = True) -> str:
+    """The hash-to-curve harness (tests/test_gpu_hash.py), built and reused as build_devblocks' builds."""
+    return build_devblocks(force, verbose, builds=[DEVBLOCKS_HASH])[DEVBLOCKS_HASH]
+
+
 def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
-    """The block harnesses and the curve harness, their units compiled side by side"""
-    return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + [DEVBLOCKS_CURVE])
+    """The block harnesses, the curve harness and the hash harness, their units compiled side by side"""
+    return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + list(DEVBLOCKS_OWN))
 
 
 SANITIZED_FLAGS = ["-O1", "-g", "-fno-omit-frame-pointer", "-fsanitize=address,undefined",

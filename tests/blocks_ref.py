@@ -529,6 +529,90 @@ def ec_neg(field, a):
     return B.ec_neg(a, FIELD_OPS[field])
 
 
+# ---- hash-to-curve (tests/native/devblocks_h2c.hip, devblocks_h2c_std.hip; tests/test_gpu_hash.py) ----
+# the exponents of fp.h's four window schedules, from the formulas of their comments
+# (charon_amd/tools/gen_consts.py writes the tables from the same four) -- never decoded from the tables
+POW_EXP = {"P_MINUS_2": P - 2, "SQRT": (P + 1) // 4, "P_M3_4": (P - 3) // 4, "LEGENDRE": (P - 1) // 2}
+
+
+def pow_expected(a, e):
+    """the value fp_pow_win's stored result must be congruent to: (a / R)^e R = a^e R^(1 - e)"""
+    return pow(a, e, P) * pow(RINV, e - 1, P) % P
+
+
+def reps2(v):
+    """the four stored forms (c0 | c0 + p, c1 | c1 + p) of the Fp2 element v"""
+    return [(mont(v[0], k0), mont(v[1], k1)) for k0 in (False, True) for k1 in (False, True)]
+
+
+def fp2_words(raw):
+    return words(raw[0]) + words(raw[1])
+
+
+# message lengths: the block count of xmd_b0 (1 + (len + 47 + 8) // 64 after Z_pad) changes between
+# 8 / 9, 72 / 73, 136 / 137 and 200 / 201; 0x80 is the last byte of a block at 16 and 80
+H2C_LENGTHS = [0, 1, 7, 8, 9, 15, 16, 17, 31, 32, 33, 63, 64, 72, 73, 80, 81, 136, 137, 200, 300]
+XMD_TAIL = (256).to_bytes(2, "big") + b"\x00" + B.DST_POP + bytes([len(B.DST_POP)])
+
+
+def xmd_b0_blocks(n):
+    return (n + len(XMD_TAIL) + 8) // 64 + 1
+
+
+def h2c_messages(seed=5, per_length=3, extra=(9, 73, 137, 16, 80)):
+    """66 distinct messages, every length of H2C_LENGTHS three times (the empty one once, five lengths
+    once more), ordered so that neighbours -- neighbouring lanes of a wave -- differ in xmd_b0's
+    block count"""
+    rng = random.Random(seed)
+    pool = [bytes(rng.randrange(256) for _ in range(n)) if n else b"" for n in H2C_LENGTHS for _ in range(per_length)]
+    pool += [bytes(rng.randrange(256) for _ in range(n)) for n in extra]
+    pool = list(dict.fromkeys(pool))  # the empty message once
+    by = {}
+    for m in pool:
+        by.setdefault(xmd_b0_blocks(len(m)), []).append(m)
+    out, prev = [], None
+    while any(by.values()):  # the fullest class that differs from the previous message's
+        k = max((c for c in by if by[c] and c != prev), key=lambda c: len(by[c]))
+        out.append(by[k].pop())
+        prev = k
+    assert all(xmd_b0_blocks(len(a)) != xmd_b0_blocks(len(b)) for a, b in zip(out, out[1:]))
+    assert {len(m) for m in out} == set(H2C_LENGTHS) and len(out) >= 65
+    return out
+
+
+def sswu_gx1_is_square(u):
+    """whether g(x1) of RFC 9380's simplified SWU on E2' is a square at u (the map then takes x1)"""
+    A, Bc, Z = B.SSWU_A, B.SSWU_B, B.SSWU_Z
+    zu2 = B.f2_mul(Z, B.f2_sqr(u))
+    tv1 = B.f2_add(B.f2_sqr(zu2), zu2)
+    if B.f2_is_zero(tv1):
+        x1 = B.f2_mul(Bc, B.f2_inv(B.f2_mul(Z, A)))
+    else:
+        x1 = B.f2_mul(B.f2_mul(B.f2_neg(Bc), B.f2_inv(A)), B.f2_add(B.F2_ONE, B.f2_inv(tv1)))
+    return B.f2_is_square(B.f2_add(B.f2_add(B.f2_mul(B.f2_sqr(x1), x1), B.f2_mul(A, x1)), Bc))
+
+
+def sswu_inputs(seed=1, n_random=40):
+    """[(name, u, stored form (raw c0, raw c1))] for the map: u = 0 in its four stored forms, small
+    and extreme values, u and -u, each coordinate in [p, 2p), random u"""
+    rng = random.Random(seed)
+    out = [("zero%d" % k, (0, 0), r) for k, r in enumerate(reps2((0, 0)))]
+    small = [(1, 0), (0, 1), (1, 1), (P - 1, 0), (0, P - 1), (2, 0)]
+    out += [("small%d" % k, u, reps2(u)[0]) for k, u in enumerate(small)]
+    rnd = [(rng.randrange(P), rng.randrange(P)) for _ in range(n_random)]
+    for k, u in enumerate(rnd):
+        out.append(("random%d" % k, u, reps2(u)[0]))
+    for k, u in enumerate(rnd[:6]):
+        out.append(("neg%d" % k, B.f2_neg(u), reps2(B.f2_neg(u))[0]))
+    for k, u in enumerate(rnd[6:9] + small[:3]):
+        out += [("upper%d.%d" % (k, j), u, r) for j, r in enumerate(reps2(u)[1:], 1)]
+    return out
+
+
+def sswu_reference(u):
+    return B.iso3_map(B.map_to_curve_sswu(u))
+
+
 def msm_reference(points, coefs):
     """sum_i [a_i] s_i + [b_i] (-psi^2 s_i) with the oracle's group law, term by term"""
     total = None

@@ -6,11 +6,18 @@
 // HB_ARG_LANES (64: vbatch.hip, threshold.hip, msm.hip, hashsplit.hip) and with -DHB_ARG_LANES=128
 // (pipeline.hip).  In the 128 build the leaf kernels run 128-thread workgroups, so wave 1 uses the
 // LDS argument slots 64..127 (pipeline.hip k_lml's consumer wave).
+//
+// A unit that defines DB_STD_CONVENTION first (devblocks_h2c_std.hip) gets the product headers as
+// hash.hip includes them instead: no HB_FAST_FPMUL, the building blocks separate functions.
 #pragma once
+#if defined(DB_STD_CONVENTION)
+#include "../../charon_amd/csrc/layout.h"
+#else
 #define HB_FAST_FPMUL 1
 #include "../../charon_amd/csrc/lines.h"
 #include "../../charon_amd/csrc/pair3.h"
 #include "../../charon_amd/csrc/pair6.h"
+#endif
 
 // threads per workgroup of the leaf kernels: the build's HB_ARG_LANES (fp.h defines its default in
 // the device pass only, so the default is named here for the host pass and compared below)
@@ -59,6 +66,13 @@ struct DbDev {  // device buffers of one call, freed when it returns
     const int db_rc_ = (dev).make((void**)&(ptr), (src), (bytes));      \
     if (db_rc_) return db_rc_;                                          \
   } while (0)
+
+// every message i = (off[i], len[i]) inside an uploaded buffer of msgs_bytes bytes
+static inline bool db_ranges_ok(int n, size_t msgs_bytes, const uint64_t* off, const uint32_t* len) {
+  for (int i = 0; i < n; i++)
+    if (off[i] > msgs_bytes || (uint64_t)len[i] > msgs_bytes - off[i]) return false;
+  return true;
+}
 
 static inline int db_finish() {  // after the launch
   if (hipGetLastError() != hipSuccess) return DB_E_LAUNCH;

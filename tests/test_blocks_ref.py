@@ -141,3 +141,25 @@ def test_torsion_fixture_loads():
             assert B.ec_is_on_curve(pt, R.FIELD_OPS[field], R.CURVE_B[field])
             if kind in ("T", "-T"):
                 assert order == q
+
+
+def test_hash_helpers():
+    """the generators of tests/test_gpu_hash.py: the message list (every length, neighbours of
+    different block counts, enough for a 65-message launch), the exponents and expected value of
+    fp_pow_win, the four stored forms, and the map's inputs on both branches"""
+    msgs = R.h2c_messages()
+    assert len(msgs) == len(set(msgs)) >= 65 and {len(m) for m in msgs} == set(R.H2C_LENGTHS)
+    assert [R.xmd_b0_blocks(n) for n in (8, 9, 72, 73, 136, 137)] == [1, 2, 2, 3, 3, 4]
+    assert len(R.XMD_TAIL) == 47 and (16 + 47 + 1) % 64 == 0 and (80 + 47 + 1) % 64 == 0  # 0x80 ends a block
+    for name, e in R.POW_EXP.items():
+        for a in (R.mont(12345), R.mont(12345, True), 0):
+            assert R.unmont(R.pow_expected(a, e)) == pow(R.unmont(a), e, R.P), name
+    assert 4 * R.POW_EXP["SQRT"] - 1 == R.P == 4 * R.POW_EXP["P_M3_4"] + 3 == 2 * R.POW_EXP["LEGENDRE"] + 1
+    v = (5, R.P - 7)
+    assert len(set(R.reps2(v))) == 4 and all((R.unmont(a), R.unmont(b)) == v for a, b in R.reps2(v))
+    inputs = R.sswu_inputs()
+    rnd = [u for name, u, _ in inputs if name.startswith("random")]
+    squares = sum(R.sswu_gx1_is_square(u) for u in rnd)
+    assert len(rnd) == 40 and squares >= 8 and len(rnd) - squares >= 8
+    assert all((R.unmont(raw[0]), R.unmont(raw[1])) == u and max(raw) < 2 * R.P for _, u, raw in inputs)
+    assert B.ec_is_on_curve(R.sswu_reference((0, 0)), B._Fp2Ops, B.B_G2)

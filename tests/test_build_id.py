@@ -128,14 +128,15 @@ def test_curve_harness_id_is_its_own(tmp_path):
         shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
     curve = build.DEVBLOCKS_CURVE
     assert {u[0] for u in build.devblocks_units(curve)} == {"devblocks_curve.hip", "devblocks_msm.hip"}
-    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve] for u in build.devblocks_units(b)} == \
+    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH] for u in build.devblocks_units(b)} == \
         {f for f in mine if f.endswith(".hip")}  # every source is built
     cid = build.devblocks_build_id(curve, root=root)
     assert cid == build.devblocks_build_id(curve) and cid.startswith(build.DEVBLOCKS_PREFIX)
     blocks = {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS}
     assert cid not in blocks.values()
     for rel in ("charon_amd/csrc/pipeline.hip", "tests/native/hostcheck.cpp", "include/hipbls.h",
-                "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip"):
+                "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip",
+                "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip", "charon_amd/csrc/hashsplit.hip"):
         with open(tmp_path / rel, "a") as f:
             f.write("\n// touched\n")
     assert build.devblocks_build_id(curve, root=root) == cid
@@ -155,3 +156,59 @@ def test_curve_harness_id_is_its_own(tmp_path):
     assert os.path.basename(path) == "libhbls_devblockscurve.so"
     if os.path.exists(path):  # what build() left in the tree is this tree's
         assert build.embedded_devblocks_id(path) == build.devblocks_build_id(curve)
+
+
+def test_hash_harness_id_is_its_own(tmp_path):
+    """The hash harness (tests/native/devblocks_h2c.hip, devblocks_h2c_std.hip; tests/test_gpu_hash.py)
+    on the same terms: its sources, the shared devblocks.h, every csrc header and the product source
+    its stage unit compiles itself (hashsplit.hip) change its id; an unrelated file, a block or curve
+    source or msm.hip does not.  The ids of the block and curve harnesses do not move with a hash
+    source or hashsplit.hip, the three kinds of id differ, and build_devblocks_all builds all of them."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    hsh, curve = build.DEVBLOCKS_HASH, build.DEVBLOCKS_CURVE
+    assert {u[0] for u in build.devblocks_units(hsh)} == {"devblocks_h2c.hip", "devblocks_h2c_std.hip"}
+    assert len({u[2] for u in build.devblocks_units(hsh)}) == len(build.devblocks_units(hsh))  # one object each
+    assert build.DEVBLOCKS_PRODUCT_SOURCES[hsh] == ["hashsplit.hip"] and build.DEVBLOCKS_PRODUCT_SOURCES[curve] == ["msm.hip"]
+    others = list(build.DEVBLOCKS_BUILDS) + [curve]
+
+    def ids(which):
+        return {b: build.devblocks_build_id(b, root=root) for b in which}
+    hid = build.devblocks_build_id(hsh, root=root)
+    assert hid == build.devblocks_build_id(hsh) and hid.startswith(build.DEVBLOCKS_PREFIX)
+    assert len(set(ids(others + [hsh]).values())) == 4  # the three harness kinds (two block builds) differ
+    for rel in ("charon_amd/csrc/pipeline.hip", "charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip",
+                "tests/native/hostcheck.cpp", "include/hipbls.h", "tests/native/devblocks_grp.hip",
+                "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip", "tests/native/devblocks_msm.hip"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    assert build.devblocks_build_id(hsh, root=root) == hid
+    before_others = ids(others)
+    for rel in ("tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip", "charon_amd/csrc/hashsplit.hip"):
+        before = build.devblocks_build_id(hsh, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(hsh, root=root) != before, rel
+        assert ids(others) == before_others, rel
+    for rel in ("tests/native/devblocks.h", "charon_amd/csrc/h2c.h", "charon_amd/csrc/sha256.h", "charon_amd/csrc/fp.h"):
+        before = build.devblocks_build_id(hsh, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(hsh, root=root) != before, rel
+    path = build.devblocks_path(hsh)
+    assert os.path.basename(path) == "libhbls_devblockshash.so"
+    if os.path.exists(path):  # what build() left in the tree is this tree's
+        assert build.embedded_devblocks_id(path) == build.devblocks_build_id(hsh)
+    # build() goes through build_devblocks_all: every harness is among its builds
+    seen = {}
+    real = build.build_devblocks
+    try:
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: seen.setdefault("builds", list(builds))
+        build.build_devblocks_all()
+    finally:
+        build.build_devblocks = real
+    assert sorted(seen["builds"]) == sorted(others + [hsh])
