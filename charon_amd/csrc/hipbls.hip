@@ -11,6 +11,7 @@
 #include "../../include/hipbls.h"
 #include "coalesce.h"
 #include "msgtable.h"
+#include "vplan.h"
 
 #include <rccl/rccl.h>
 #include <sys/random.h>
@@ -968,17 +969,43 @@ int kl_keys(Dev& d, const KeyLearnTab& t, const uint8_t* pks, size_t n, G1AEntry
   return 0;
 }
 
-// defer_hm / defer_msgs: the caller hashed the defer_msgs messages at defer_hm (the call's messages
-// or a contiguous range of them) without their Miller lines (callers whose messages have about one
-// verification group each, batched final exponentiation sizes): the slot-wide check evaluates each
-// group's chain at P directly (k_lines_at_p) and the unevaluated lines are computed only behind a
-// failed check; any other path computes them first.
-int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, const uint32_t* didx,
-                    const MsgEntry* hm, size_t n, const uint32_t* dgoff, size_t n_groups, uint8_t* dst,
-                    hipStream_t s, hipEvent_t hm_ready, const TaFold* fold, bool kc = false,
-                    hipEvent_t h_ready = nullptr, MsgEntry* defer_hm = nullptr, size_t defer_msgs = 0,
-                    uint32_t* first_out = nullptr) {
-  if (!dgoff) n_groups = n;
+static_assert(VP_GROUPS_PER_WAVE == GROUPS_PER_WAVE && VP_PROD_FAN == PROD_FAN && VP_RLC_CHUNK == RLC_CHUNK,
+              "vplan.h restates layout.h");
+
+// One verification (verify_pipeline): the call's inputs by name, and what it hands back.
+struct VerifyCall {
+  const uint8_t *pks = nullptr, *sigs = nullptr;  // compressed, n of each
+  const uint32_t* msg_idx = nullptr;              // each item's message in hm
+  const MsgEntry* hm = nullptr;
+  size_t n = 0;
+  const uint32_t* grp_off = nullptr;  // the verification groups' offsets (null: every item its own group)
+  size_t n_groups = 0;
+  uint8_t* status = nullptr;  // out: one per item
+  hipStream_t s = nullptr;
+  hipEvent_t hm_ready = nullptr;  // the hashed messages and their lines (null: already ordered before s)
+  hipEvent_t h_ready = nullptr;   // host calls: the hashing alone, before the messages' lines
+  const TaFold* fold = nullptr;   // the slot's ThresholdAggregate and folded aggregates, key tables
+  bool key_cache = false;         // host-buffer call: the keys through the public-key cache
+  // defer_hm / defer_msgs: the caller hashed the defer_msgs messages at defer_hm (the call's messages
+  // or a contiguous range of them) without their Miller lines (callers whose messages have about one
+  // verification group each, batched final exponentiation sizes): the slot-wide check evaluates each
+  // group's chain at P directly (k_lines_at_p) and the unevaluated lines are computed only behind a
+  // failed check; any other path computes them first.
+  MsgEntry* defer_hm = nullptr;
+  size_t defer_msgs = 0;
+  // first-error mode (vplan.h): the first item whose status is decided and not OK (0xffffffff: none)
+  uint32_t* first_out = nullptr;
+  // handed back: the decompressed signatures and their statuses (the host calls' signature-cache put)
+  HmEntry* vsig = nullptr;
+  uint8_t* vsigst = nullptr;
+};
+
+// The call's workspace buffers (verify_bufs; value-initialised, so null where the plan has no use
+// for one), its coefficient key, and what a phase leaves for a later one.
+struct VerifyBufs {
+  // the decompressed keys and signatures with their statuses (vpk / vpkst and apk / apkst: the
+  // caller's key tables when it gave them), the items' groups and sides, the groups' sums, states,
+  // messages, verdicts and lines, the fallback's list
   G1AEntry* vpk;
   HmEntry* vsig;
   uint8_t *vpkst, *vsigst, *gst, *gver;
@@ -987,109 +1014,98 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
   G2JEntry* sr;
   G1AEntry* gP;
   LineEntry *glines, *fbl;
-  const size_t gcap = std::min(std::max<size_t>(1, g_gcap.load()), std::max<size_t>(n_groups, 1));
-  const size_t n_agg = (fold && fold->dv_pks) ? fold->n_groups : 0;
-  const size_t fbcap = std::min(std::max<size_t>(1, g_fbcap.load()), std::max<size_t>(n + n_agg, 1));
-  if (wsbuf(w, W_VPK, n, &vpk) || wsbuf(w, W_VPKST, n, &vpkst) || wsbuf(w, W_VSIG, n, &vsig) ||
-      wsbuf(w, W_VSIGST, n, &vsigst) || wsbuf(w, W_IGRP, n, &igrp) || wsbuf(w, W_PR, n, &pr) ||
-      wsbuf(w, W_SR, n, &sr) || wsbuf(w, W_GP, gcap, &gP) || wsbuf(w, W_GST, gcap, &gst) ||
-      wsbuf(w, W_GMSG, n_groups, &gmsg) || wsbuf(w, W_GVER, n_groups, &gver) ||
-      wsbuf(w, W_GLINES, gcap * N_LINES, &glines) || wsbuf(w, W_LIST, n + n_agg, &list) ||
-      wsbuf(w, W_COUNT, 1, &count) || wsbuf(w, W_FBLINES, fbcap * N_LINES, &fbl))
-    return -1;
-  G1AEntry* apk = nullptr;
-  uint8_t* apkst = nullptr;
-  HmEntry* asig = nullptr;
-  G1JEntry* apr = nullptr;
-  G2JEntry* asr = nullptr;
-  if (n_agg && (wsbuf(w, W_APK, n_agg, &apk) || wsbuf(w, W_APKST, n_agg, &apkst) ||
-                wsbuf(w, W_ASIG, n_agg, &asig) || wsbuf(w, W_APR, n_agg, &apr) || wsbuf(w, W_ASR, n_agg, &asr)))
-    return -1;
-  RlcKey key;
-  if (rlc_key(key)) return -1;
-  // Coefficients: at most ONE fixed (r = 1) coefficient per combined check.  Items of a singleton
-  // group keep r = 1 only when nothing else joins their group's check; with a folded aggregate
-  // (which keeps r = 1 without the batched final exponentiation) every item takes a random one --
-  // otherwise an error +D on a group's single partial and -D on its aggregate would cancel.
-  // Batched final exponentiation: a batch of groups (FE_BATCH; behind a failed slot-wide check the
-  // multi-Miller loops' chunks of mmlk groups) shares one final exponentiation and one Miller
-  // loop of the signature side, checking prod_g e(P_g, H(m_g)) * e(-g1, sum_g S_g) == 1.  Every
-  // item (singletons and folded aggregates included) then takes a random coefficient: with two
-  // fixed coefficients in one combination, errors of two items could cancel.
-  const size_t fe_min = g_fe_batch_min.load();
-  const bool bfe = fe_min && n_groups >= fe_min;
-  const int item_always = (bfe || n_agg) ? 1 : 0;  // see the coefficient rule above
-  // First-error mode (first_out, the callers' contract: parsigex.go:93-98, sigagg.go:56-63 stop at
-  // the first failing item): behind a failed combined check only the FIRST failing batch descends
-  // to its groups and only the first failing group to its items -- groups and batches are in item
-  // order, so every item before the first failure has passed a check and every item left
-  // unresolved (ST_UNCHECKED) comes after it.  Without the batched final exponentiation every
-  // group is checked anyway (exact statuses).  *first_out: the first item whose status is decided
-  // and not OK (0xffffffff: none).
-  if (first_out && n_agg) return set_err("verify: the first-error mode takes no folded aggregates");
-  const bool first_only = first_out && bfe;
-  uint32_t* wfirst = nullptr;
-  if (first_only) {
-    if (wsbuf(w, W_FIRST, 2, &wfirst)) return -1;
-    HCHK(hipMemsetAsync(wfirst, 0xff, 2 * sizeof(uint32_t), s));
-  }
-  // pairs per multi-Miller loop of the slot-wide check: enough that the loops fill at most one
-  // round of waves (21 groups per wave, one wave per SIMD) -- a second, partial round would double
-  // the kernel's span
-  const size_t mmlk = std::min<size_t>(16, std::max<size_t>(1, (std::min(gcap, n_groups) + GROUPS_PER_WAVE * 4 * d.n_cu - 1) /
-                                                              (GROUPS_PER_WAVE * 4 * d.n_cu)));
-  const size_t nb1 = (gcap + mmlk - 1) / mmlk, nb2 = (nb1 + PROD_FAN - 1) / PROD_FAN;
-  // batches of >= 2 groups (FE_BATCH), or behind a failed slot-wide check its multi-Miller loops' chunks
-  const size_t nbcap = std::max((gcap + 1) / 2, nb1);
-  Fp4Entry* fbuf = nullptr;
-  G2JEntry *gS = nullptr, *bS = nullptr;
-  LineEntry* blines = nullptr;
-  uint8_t *bbad = nullptr, *bver = nullptr;
-  uint32_t *glist = nullptr, *gcount = nullptr;
+  // folded aggregates (n_agg)
+  G1AEntry* apk;
+  uint8_t* apkst;
+  HmEntry* asig;
+  G1JEntry* apr;
+  G2JEntry* asr;
+  uint32_t* wfirst;  // first_only
+  // batched final exponentiation (bfe)
+  Fp4Entry* fbuf;
+  G2JEntry *gS, *bS;
+  LineEntry* blines;
+  uint8_t *bbad, *bver;
+  uint32_t *glist, *gcount;
   // the two factors of each final exponentiation side by side (product tree root, signature-side
   // loop), and the product tree's intermediate level
-  Fp4Entry *pfin = nullptr, *tbuf = nullptr;
-  if (bfe && (wsbuf(w, W_FBUF, 3 * gcap, &fbuf) || wsbuf(w, W_GS, gcap, &gS) || wsbuf(w, W_BS, nbcap, &bS) ||
-              wsbuf(w, W_BLINES, nbcap * N_LINES, &blines) || wsbuf(w, W_BBAD, nbcap, &bbad) ||
-              wsbuf(w, W_BVER, nbcap, &bver) || wsbuf(w, W_GLIST, gcap, &glist) || wsbuf(w, W_GCOUNT, 1, &gcount) ||
-              wsbuf(w, W_PFIN, 3 * 2 * std::max<size_t>(nbcap, 1), &pfin) || wsbuf(w, W_TBUF, 3 * nbcap, &tbuf)))
-    return -1;
-  // Slot-wide check (msm.hip): every group of the call at once, the signature side as one
-  // multi-scalar multiplication; the per-batch path below runs only if it fails (its kernels wait
-  // on the device flag sfail).  Needs all groups in one chunk.
-  const size_t smin = g_slot_msm_min.load();
-  const bool smsm = bfe && smin && n_groups <= gcap && n + n_agg >= smin;
-  G2MsmArgs ma{};
-  // pbuf1: the multi-Miller loops (kept: behind a failed slot-wide check they are the per-batch
-  // check's public-key sides); pbuf2 / pbuf3: the product tree's levels
-  Fp4Entry *pbuf1 = nullptr, *pbuf2 = nullptr, *pbuf3 = nullptr;
-  uint8_t* sfail = nullptr;
-  LineEntry* mlev = nullptr;
-  if (smsm && (wsbuf(w, W_MCNT, MSM_KEYS, &ma.cnt) || wsbuf(w, W_MOFF, MSM_KEYS + 1, &ma.off) ||
-               wsbuf(w, W_MCUR, MSM_KEYS, &ma.cur) || wsbuf(w, W_MORDER, MSM_KEYS, &ma.order) ||
-               wsbuf(w, W_MENT, 2 * MSM_WINDOWS * (n + n_agg), &ma.ent) ||
-               wsbuf(w, W_MBUCKET, MSM_KEYS, &ma.bucket) || wsbuf(w, W_MPART, MSM_PARTS, &ma.part) ||
-               wsbuf(w, W_MPART2, MSM_PARTS / 128, &ma.part2) || wsbuf(w, W_MTOT, 1, &ma.total) ||
-               wsbuf(w, W_PBUF1, 3 * nb1, &pbuf1) || wsbuf(w, W_PBUF2, 3 * nb2, &pbuf2) ||
-               wsbuf(w, W_PBUF3, 3 * nb2, &pbuf3) ||
-               wsbuf(w, W_SFAIL, 2, &sfail) || wsbuf(w, W_MLEV, N_LINES * gcap, &mlev)))
-    return -1;
-  // adaptive: the outcome of the last completed checked call decides whether this one tries the
-  // slot-wide check at all (skip: the fallback's kernels run unguarded, sfail set to 1)
-  bool skip_msm = false;
-  if (smsm && g_adaptive.load()) {
-    while (d.res_tail != d.res_head && hipEventQuery(d.res_ev[d.res_tail % N_RES]) == hipSuccess) {
-      const SlotRes& r = d.res_host[d.res_tail % N_RES];
-      d.attack = r.skipped ? r.gcount != 0 : r.sfail != 0;
-      d.res_tail++;
-    }
-    skip_msm = d.attack;
-  }
-  // first pass: the public-key side only when the MSM takes the other
-  const int sides1 = smsm && !skip_msm ? 1 : 3;
+  Fp4Entry *pfin, *tbuf;
+  // slot-wide check (smsm).  pbuf1: the multi-Miller loops (kept: behind a failed slot-wide check
+  // they are the per-batch check's public-key sides); pbuf2 / pbuf3: the product tree's levels
+  G2MsmArgs ma;
+  Fp4Entry *pbuf1, *pbuf2, *pbuf3;
+  uint8_t* sfail;
+  LineEntry* mlev;
+  // the items' coefficients (folded aggregates' behind them at coef + n): written by the first
+  // combination for the slot-wide check's MSM and its guarded second pass (smsm), or the chunked
+  // combination's own
+  uint2* coef;
+  // chunked combination (rlc_chunked)
+  uint32_t *pcnt, *pcoff, *pcf, *pcc;
+  uint4* coef4;
+  G1J* t1;
+  G2J* t2;
+  // small calls (no bfe)
+  Fp4Entry* f1;
+  uint8_t* f1bad;
+  G2JEntry* f1S;
+  RlcKey key;
+  bool learned;  // decompress recorded Dev::kl_ev for this call (resolve joins it)
+};
 
+// chunks of the chunked combination (an upper bound: a group's last chunk may be short)
+uint32_t rlc_chunk_count(const VerifyPlan& p) { return (uint32_t)(p.n / p.rlc_cmax + p.n_groups); }
+
+// Same buffers, sizes and conditions whatever the phases do with them: wsbuf synchronises when a
+// buffer grows, so none is taken that the plan does not use.
+int verify_bufs(Ws& w, const VerifyPlan& p, VerifyBufs& b) {
+  const size_t n = p.n, n_agg = p.n_agg, n_groups = p.n_groups, gcap = p.gcap, nbcap = p.nbcap;
+  if (wsbuf(w, W_VPK, n, &b.vpk) || wsbuf(w, W_VPKST, n, &b.vpkst) || wsbuf(w, W_VSIG, n, &b.vsig) ||
+      wsbuf(w, W_VSIGST, n, &b.vsigst) || wsbuf(w, W_IGRP, n, &b.igrp) || wsbuf(w, W_PR, n, &b.pr) ||
+      wsbuf(w, W_SR, n, &b.sr) || wsbuf(w, W_GP, gcap, &b.gP) || wsbuf(w, W_GST, gcap, &b.gst) ||
+      wsbuf(w, W_GMSG, n_groups, &b.gmsg) || wsbuf(w, W_GVER, n_groups, &b.gver) ||
+      wsbuf(w, W_GLINES, gcap * N_LINES, &b.glines) || wsbuf(w, W_LIST, n + n_agg, &b.list) ||
+      wsbuf(w, W_COUNT, 1, &b.count) || wsbuf(w, W_FBLINES, p.fbcap * N_LINES, &b.fbl))
+    return -1;
+  if (n_agg && (wsbuf(w, W_APK, n_agg, &b.apk) || wsbuf(w, W_APKST, n_agg, &b.apkst) ||
+                wsbuf(w, W_ASIG, n_agg, &b.asig) || wsbuf(w, W_APR, n_agg, &b.apr) || wsbuf(w, W_ASR, n_agg, &b.asr)))
+    return -1;
+  if (p.first_only && wsbuf(w, W_FIRST, 2, &b.wfirst)) return -1;
+  if (p.bfe && (wsbuf(w, W_FBUF, 3 * gcap, &b.fbuf) || wsbuf(w, W_GS, gcap, &b.gS) || wsbuf(w, W_BS, nbcap, &b.bS) ||
+                wsbuf(w, W_BLINES, nbcap * N_LINES, &b.blines) || wsbuf(w, W_BBAD, nbcap, &b.bbad) ||
+                wsbuf(w, W_BVER, nbcap, &b.bver) || wsbuf(w, W_GLIST, gcap, &b.glist) ||
+                wsbuf(w, W_GCOUNT, 1, &b.gcount) || wsbuf(w, W_PFIN, 3 * 2 * std::max<size_t>(nbcap, 1), &b.pfin) ||
+                wsbuf(w, W_TBUF, 3 * nbcap, &b.tbuf)))
+    return -1;
+  G2MsmArgs& ma = b.ma;
+  if (p.smsm && (wsbuf(w, W_MCNT, MSM_KEYS, &ma.cnt) || wsbuf(w, W_MOFF, MSM_KEYS + 1, &ma.off) ||
+                 wsbuf(w, W_MCUR, MSM_KEYS, &ma.cur) || wsbuf(w, W_MORDER, MSM_KEYS, &ma.order) ||
+                 wsbuf(w, W_MENT, 2 * MSM_WINDOWS * (n + n_agg), &ma.ent) ||
+                 wsbuf(w, W_MBUCKET, MSM_KEYS, &ma.bucket) || wsbuf(w, W_MPART, MSM_PARTS, &ma.part) ||
+                 wsbuf(w, W_MPART2, MSM_PARTS / 128, &ma.part2) || wsbuf(w, W_MTOT, 1, &ma.total) ||
+                 wsbuf(w, W_PBUF1, 3 * p.nb1, &b.pbuf1) || wsbuf(w, W_PBUF2, 3 * p.nb2, &b.pbuf2) ||
+                 wsbuf(w, W_PBUF3, 3 * p.nb2, &b.pbuf3) || wsbuf(w, W_SFAIL, 2, &b.sfail) ||
+                 wsbuf(w, W_MLEV, N_LINES * gcap, &b.mlev)))
+    return -1;
+  if ((p.rlc_chunked || p.smsm) && wsbuf(w, W_COEF, n + n_agg, &b.coef)) return -1;
+  const size_t max_chunks = rlc_chunk_count(p);
+  if (p.rlc_chunked &&
+      (wsbuf(w, W_PCNT, n_groups, &b.pcnt) || wsbuf(w, W_PCOFF, n_groups + 1, &b.pcoff) ||
+       wsbuf(w, W_PCFIRST, max_chunks, &b.pcf) || wsbuf(w, W_PCCOUNT, max_chunks, &b.pcc) ||
+       wsbuf(w, W_RT1, 4 * n, &b.t1) || wsbuf(w, W_RT2, 4 * n, &b.t2) || (p.sparse && wsbuf(w, W_COEF4, n, &b.coef4))))
+    return -1;
+  if (!p.bfe && (wsbuf(w, W_F1, 3 * 2 * gcap, &b.f1) || wsbuf(w, W_F1BAD, gcap, &b.f1bad) || wsbuf(w, W_F1S, gcap, &b.f1S)))
+    return -1;
+  return rlc_key(b.key) ? -1 : 0;
+}
+
+// Decompress: the fork onto the side streams, the public keys from one of four sources, the
+// signatures, and the learned key cache's chain (Dev::kl_ev)
+int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b) {
+  const TaFold* fold = c.fold;
+  const size_t n = p.n, n_agg = p.n_agg;
   // fork: decompression on the side streams (after the previous verification's decompression)
-  HCHK(hipEventRecord(w.ev_fork, s));
+  HCHK(hipEventRecord(w.ev_fork, c.s));
   for (int k = 0; k < 2; k++) HCHK(hipStreamWaitEvent(w.side[k], w.ev_fork, 0));
   // public keys: from the caller's decompressed-key tables when given (static per cluster lock:
   // decompressed and subgroup-checked once); device calls without tables through the learned key
@@ -1097,11 +1113,11 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
   // here
   // (the lookup loads a key as three 16-byte words: a caller's array that is not 16-byte aligned
   // takes the plain decompression)
-  const auto al16 = [](const void* p) { return ((uintptr_t)p & 15) == 0; };
-  const bool learn_pk = !kc && !(fold && fold->pk_table) && n && al16(dpk);
-  const bool learn_dv = !kc && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
+  const auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
+  const bool learn_pk = !c.key_cache && !(fold && fold->pk_table) && n && al16(c.pks);
+  const bool learn_dv = !c.key_cache && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
   KeyLearnTab kl{};
-  uint32_t *kmiss = nullptr, *kcnt = nullptr;
+  uint32_t *kmiss = nullptr, *kcnt = nullptr;  // taken here: whether there is a table is only known now
   if (learn_pk || learn_dv) {
     // the ordering chain of Dev::kl_ev: behind the last call's k_pk_learn
     if (d.kl_ev_set) HCHK(hipStreamWaitEvent(w.side[0], d.kl_ev, 0));
@@ -1112,135 +1128,116 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
     }
   }
   if (fold && fold->pk_table) {
-    vpk = const_cast<G1AEntry*>(fold->pk_table);
-    vpkst = const_cast<uint8_t*>(fold->pk_table_st);
-  } else if (kc && d.kc_n) {  // host-buffer call with the key cache: cached entries, the rest decompressed
+    b.vpk = const_cast<G1AEntry*>(fold->pk_table);
+    b.vpkst = const_cast<uint8_t*>(fold->pk_table_st);
+  } else if (c.key_cache && d.kc_n) {  // host-buffer call with the key cache: cached entries, the rest decompressed
     TIMED(d, "k_dec_pk", w.side[0],
-          launch_pk_cached(dpk, (uint32_t)n, (const uint8_t*)d.kc_keys.p, (const G1AEntry*)d.kc_tab.p,
+          launch_pk_cached(c.pks, (uint32_t)n, (const uint8_t*)d.kc_keys.p, (const G1AEntry*)d.kc_tab.p,
                            (const uint8_t*)d.kc_st.p, (const uint32_t*)d.kc_hidx.p, (uint32_t)d.kc_tcap, g_sc_k0,
-                           g_sc_k1, vpk, vpkst, w.side[0]));
+                           g_sc_k1, b.vpk, b.vpkst, w.side[0]));
   } else if (learn_pk && kl.cap) {
-    if (kl_keys(d, kl, dpk, n, vpk, vpkst, kmiss, kcnt, w.side[0])) return -1;
+    if (kl_keys(d, kl, c.pks, n, b.vpk, b.vpkst, kmiss, kcnt, w.side[0])) return -1;
   } else {
-    TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(dpk, (uint32_t)n, vpk, vpkst, w.side[0]));
+    TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(c.pks, (uint32_t)n, b.vpk, b.vpkst, w.side[0]));
   }
   HCHK(hipEventRecord(w.ev_pk, w.side[0]));
   if (n_agg && fold->dv_pk_table) {
-    apk = const_cast<G1AEntry*>(fold->dv_pk_table);
-    apkst = const_cast<uint8_t*>(fold->dv_pk_table_st);
+    b.apk = const_cast<G1AEntry*>(fold->dv_pk_table);
+    b.apkst = const_cast<uint8_t*>(fold->dv_pk_table_st);
   } else if (learn_dv && kl.cap) {
-    if (kl_keys(d, kl, fold->dv_pks, n_agg, apk, apkst, kmiss + n, kcnt + 1, w.side[0])) return -1;
+    if (kl_keys(d, kl, fold->dv_pks, n_agg, b.apk, b.apkst, kmiss + n, kcnt + 1, w.side[0])) return -1;
   } else if (n_agg) {
-    TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(fold->dv_pks, (uint32_t)n_agg, apk, apkst, w.side[0]));
+    TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(fold->dv_pks, (uint32_t)n_agg, b.apk, b.apkst, w.side[0]));
   }
-  TIMED(d, "k_dec_sig_pt", w.side[1], launch_dec_sig_pt(dsig, (uint32_t)n, vsig, vsigst, w.side[1], nullptr, w.ev_dec));
+  TIMED(d, "k_dec_sig_pt", w.side[1],
+        launch_dec_sig_pt(c.sigs, (uint32_t)n, b.vsig, b.vsigst, w.side[1], nullptr, w.ev_dec));
   HCHK(hipEventRecord(w.ev_side[0], w.side[0]));
   HCHK(hipEventRecord(w.ev_side[1], w.side[1]));
   // the misses into the table, behind everything that waits for the keys; the next call's lookup
   // (on any workspace set) waits for kl_ev, and so does the end of this call: k_pk_learn reads the
   // caller's key bytes and this set's buffers
-  const bool learned = kl.cap != 0;
-  if (learned) {
+  b.learned = kl.cap != 0;
+  if (b.learned) {
     if (learn_pk)
       TIMED(d, "k_pk_learn", w.side[0],
-            launch_pk_learn(kl, dpk, (uint32_t)n, kmiss, kcnt, g_sc_k0, g_sc_k1, vpk, vpkst, w.side[0]));
+            launch_pk_learn(kl, c.pks, (uint32_t)n, kmiss, kcnt, g_sc_k0, g_sc_k1, b.vpk, b.vpkst, w.side[0]));
     if (learn_dv)
       TIMED(d, "k_pk_learn", w.side[0],
-            launch_pk_learn(kl, fold->dv_pks, (uint32_t)n_agg, kmiss + n, kcnt + 1, g_sc_k0, g_sc_k1, apk, apkst,
+            launch_pk_learn(kl, fold->dv_pks, (uint32_t)n_agg, kmiss + n, kcnt + 1, g_sc_k0, g_sc_k1, b.apk, b.apkst,
                             w.side[0]));
     HCHK(hipEventRecord(d.kl_ev, w.side[0]));
     d.kl_ev_set = true;
   }
+  return 0;
+}
 
-  // the slot's ThresholdAggregate on side 3 (needs the decompressed partials when it reuses them)
-  const bool ta = fold && fold->n_groups;
-  if (ta) {
-    hipStream_t st = w.side[3];
-    HCHK(hipStreamWaitEvent(st, w.ev_fork, 0));
-    const HmEntry* pts = vsig;
-    const uint8_t* mst_in = vsigst;
-    hipEvent_t mst_ready = nullptr, pts_ready = nullptr;
-    if (fold->ta_src) {  // the points once decompressed; their subgroup statuses before the digits
-      pts_ready = w.ev_dec;
-      mst_ready = w.ev_side[1];
-    } else {  // the aggregation members come as their own bytes: decompress them here
-      HmEntry* tpts;
-      uint8_t* tdst;
-      if (wsbuf(w, W_TAPTS, fold->n_partials, &tpts) || wsbuf(w, W_TADST, fold->n_partials, &tdst)) return -1;
-      TIMED(d, "k_dec_sig_pt", st, launch_dec_sig_pt(fold->ta_sigs, (uint32_t)fold->n_partials, tpts, tdst, st));
-      pts = tpts;
-      mst_in = tdst;
-    }
-    if (ta_tail(d, w, pts, fold->ta_src, mst_in, fold->ta_idx, fold->grp_off, fold->n_groups, fold->n_partials, 0,
-                fold->ta_out, fold->ta_status, asig, st, mst_ready, pts_ready))
-      return -1;
-    HCHK(hipEventRecord(w.ev_ta, st));
+// Fold: the slot's ThresholdAggregate on side 3 (needs the decompressed partials when it reuses them)
+int verify_fold(Dev& d, Ws& w, const VerifyCall& c, VerifyBufs& b) {
+  const TaFold* fold = c.fold;
+  if (!(fold && fold->n_groups)) return 0;
+  hipStream_t st = w.side[3];
+  HCHK(hipStreamWaitEvent(st, w.ev_fork, 0));
+  const HmEntry* pts = b.vsig;
+  const uint8_t* mst_in = b.vsigst;
+  hipEvent_t mst_ready = nullptr, pts_ready = nullptr;
+  if (fold->ta_src) {  // the points once decompressed; their subgroup statuses before the digits
+    pts_ready = w.ev_dec;
+    mst_ready = w.ev_side[1];
+  } else {  // the aggregation members come as their own bytes: decompress them here
+    HmEntry* tpts;
+    uint8_t* tdst;
+    if (wsbuf(w, W_TAPTS, fold->n_partials, &tpts) || wsbuf(w, W_TADST, fold->n_partials, &tdst)) return -1;
+    TIMED(d, "k_dec_sig_pt", st, launch_dec_sig_pt(fold->ta_sigs, (uint32_t)fold->n_partials, tpts, tdst, st));
+    pts = tpts;
+    mst_in = tdst;
   }
+  if (ta_tail(d, w, pts, fold->ta_src, mst_in, fold->ta_idx, fold->grp_off, fold->n_groups, fold->n_partials, 0,
+              fold->ta_out, fold->ta_status, b.asig, st, mst_ready, pts_ready))
+    return -1;
+  HCHK(hipEventRecord(w.ev_ta, st));
+  return 0;
+}
 
-  // random linear combinations per item, then per group (the partials' keys only: the DV keys'
-  // decompression behind them on side 0 is waited for by the aggregates' combination below)
+// the chunked combination's launch (the first pass; the slot-wide check's guarded second pass
+// changes its sides and guard)
+RlcMsmArgs rlc_chunk_args(const VerifyPlan& p, const VerifyBufs& b) {
+  RlcMsmArgs ra{};
+  ra.pk = b.vpk;
+  ra.pk_st = b.vpkst;
+  ra.sig = b.vsig;
+  ra.sig_st = b.vsigst;
+  ra.cfirst = b.pcf;
+  ra.ccount = b.pcc;
+  ra.total = b.pcoff + p.n_groups;
+  ra.key_base = 0;
+  ra.key = b.key;
+  ra.coef = b.coef;
+  ra.coef4 = b.coef4;
+  ra.sparse = p.sparse ? 1 : 0;
+  ra.t1 = b.t1;
+  ra.t2 = b.t2;
+  ra.pout = b.pr;
+  ra.sout = b.sr;
+  ra.always = p.item_always;
+  ra.sides = p.sides1;
+  return ra;
+}
+
+// Combine: random linear combinations per item, then per group (the partials' keys only: the DV
+// keys' decompression behind them on side 0 is waited for by the aggregates' combination below)
+int verify_combine(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b) {
+  hipStream_t s = c.s;
+  const size_t n = p.n, n_agg = p.n_agg;
   HCHK(hipStreamWaitEvent(s, w.ev_pk, 0));
-  // the partials' key side from the keys alone when the slot-wide MSM takes the signature side
-  // (sides1 1, the per-lane combination): it runs beside the signatures' subgroup checks, whose
-  // statuses group_scan and msm_take apply; otherwise the signatures' statuses first
-  const uint32_t rlc_cmax = (uint32_t)std::min<size_t>(RLC_CHUNK, std::max<size_t>(1, n / g_rlc_lanes.load()));
-  const bool keys_only = sides1 == 1 && !(dgoff && rlc_cmax > 1);
-  if (!keys_only) HCHK(hipStreamWaitEvent(s, w.ev_side[1], 0));
-  TIMED(d, "k_item_group", s, launch_item_group(dgoff, (uint32_t)n_groups, (uint32_t)n, igrp, s));
-  RlcMsmArgs rlc_fallback{};
-  uint32_t rlc_fallback_chunks = 0;
-  uint2* coef_pi = nullptr;  // per-item path's coefficients (slot-wide check)
-  if (dgoff && rlc_cmax > 1) {
-    // chunks of a group's items share their ladders' doublings (k_rlc_msm); the chunk size keeps
-    // about g_rlc_lanes lanes busy (at most RLC_CHUNK items, one item per lane for small calls)
-    const uint32_t cmax = rlc_cmax;
-    const size_t max_chunks = n / cmax + n_groups;
-    uint32_t *pcnt, *pcoff, *pcf, *pcc;
-    uint2* coef;
-    uint4* coef4 = nullptr;
-    G1J* t1;
-    G2J* t2;
-    // the sparse coefficient format (22 additions per item instead of 32) unless the slot-wide
-    // bucket MSM reads the coefficients: under attack (skip_msm), or a chunked call without the
-    // slot-wide check (HBLS_SLOT_MSM above its size)
-    const bool sparse = !(smsm && !skip_msm);
-    if (wsbuf(w, W_PCNT, n_groups, &pcnt) || wsbuf(w, W_PCOFF, n_groups + 1, &pcoff) ||
-        wsbuf(w, W_PCFIRST, max_chunks, &pcf) || wsbuf(w, W_PCCOUNT, max_chunks, &pcc) ||
-        wsbuf(w, W_COEF, n + n_agg, &coef) || wsbuf(w, W_RT1, 4 * n, &t1) || wsbuf(w, W_RT2, 4 * n, &t2) ||
-        (sparse && wsbuf(w, W_COEF4, n, &coef4)))
-      return -1;
-    TIMED(d, "k_plan", s, launch_plan(dgoff, (uint32_t)n_groups, cmax, pcnt, pcoff, pcf, pcc, s));
-    RlcMsmArgs ra{};
-    ra.pk = vpk;
-    ra.pk_st = vpkst;
-    ra.sig = vsig;
-    ra.sig_st = vsigst;
-    ra.cfirst = pcf;
-    ra.ccount = pcc;
-    ra.total = pcoff + n_groups;
-    ra.key_base = 0;
-    ra.key = key;
-    ra.coef = coef;
-    ra.coef4 = coef4;
-    ra.sparse = sparse ? 1 : 0;
-    ra.t1 = t1;
-    ra.t2 = t2;
-    ra.pout = pr;
-    ra.sout = sr;
-    ra.always = item_always;
-    ra.sides = sides1;
-    TIMED(d, "k_rlc", s, launch_rlc_msm(ra, (uint32_t)max_chunks, s));
-    if (smsm && !skip_msm) {  // the per-item signature side, only if the slot-wide check fails
-      ra.sides = 2;
-      ra.guard = sfail;
-      rlc_fallback = ra;
-      rlc_fallback_chunks = (uint32_t)max_chunks;
-    }
+  if (!p.keys_only) HCHK(hipStreamWaitEvent(s, w.ev_side[1], 0));  // (vplan.h keys_only)
+  TIMED(d, "k_item_group", s, launch_item_group(c.grp_off, (uint32_t)p.n_groups, (uint32_t)n, b.igrp, s));
+  if (p.rlc_chunked) {
+    TIMED(d, "k_plan", s, launch_plan(c.grp_off, (uint32_t)p.n_groups, p.rlc_cmax, b.pcnt, b.pcoff, b.pcf, b.pcc, s));
+    TIMED(d, "k_rlc", s, launch_rlc_msm(rlc_chunk_args(p, b), rlc_chunk_count(p), s));
   } else {
-    if (smsm && wsbuf(w, W_COEF, n + n_agg, &coef_pi)) return -1;
     TIMED(d, "k_rlc", s,
-          launch_rlc(vpk, vpkst, keys_only ? nullptr : vsig, keys_only ? nullptr : vsigst, igrp, dgoff, item_always,
-                     (uint32_t)n, 0, key, pr, sr, s, coef_pi, sides1));
+          launch_rlc(b.vpk, b.vpkst, p.keys_only ? nullptr : b.vsig, p.keys_only ? nullptr : b.vsigst, b.igrp,
+                     c.grp_off, p.item_always, (uint32_t)n, 0, b.key, b.pr, b.sr, s, b.coef, p.sides1));
     HCHK(hipStreamWaitEvent(s, w.ev_side[1], 0));  // the groups' states below read the signatures
   }
   if (n_agg) {
@@ -1252,396 +1249,474 @@ int verify_pipeline(Dev& d, Ws& w, const uint8_t* dpk, const uint8_t* dsig, cons
     // Key side only (sides1 1, the slot-wide check's MSM takes the signature side): the DV keys
     // are all it reads, so it runs beside the slot's ThresholdAggregate; the aggregates' statuses
     // and points are applied where the signature side is read (group_scan's with_agg, msm_take)
-    const bool key_only = sides1 == 1;
-    if (!key_only) HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));
+    const bool key_side = p.sides1 == 1;
+    if (!key_side) HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));
     HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
-    uint2* acoef = smsm && !skip_msm ? (coef_pi ? coef_pi : rlc_fallback.coef) + n : nullptr;
     TIMED(d, "k_rlc", s,
-          launch_rlc(apk, apkst, key_only ? nullptr : asig, key_only ? nullptr : fold->ta_status, nullptr, nullptr,
-                     bfe ? 1 : 0, (uint32_t)n_agg, (uint32_t)n, key, apr, asr, s, acoef, sides1));
+          launch_rlc(b.apk, b.apkst, key_side ? nullptr : b.asig, key_side ? nullptr : c.fold->ta_status, nullptr,
+                     nullptr, p.bfe ? 1 : 0, (uint32_t)n_agg, (uint32_t)n, b.key, b.apr, b.asr, s,
+                     p.try_msm ? b.coef + n : nullptr, p.sides1));
     HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));  // the groups' states below read the aggregates
   }
   // small calls (no batched final exponentiation): the groups' sums and signature lines do not
   // need the hashed messages, so they overlap the hashing; the wait comes before the pairing
-  if (hm_ready && bfe) HCHK(hipStreamWaitEvent(s, hm_ready, 0));
-  if (defer_msgs && !bfe) return set_err("verify: deferred Miller lines need the batched final exponentiation");
-  const bool lines_at_p = defer_msgs && smsm && !skip_msm;
-  if (defer_msgs && !lines_at_p)  // the per-batch check reads the unevaluated lines
-    TIMED(d, "k_lines_msg", s, launch_lines_msg(defer_hm, (uint32_t)defer_msgs, s));
-  Fp4Entry* f1 = nullptr;
-  uint8_t* f1bad = nullptr;
-  G2JEntry* f1S = nullptr;
-  if (!bfe && (wsbuf(w, W_F1, 3 * 2 * gcap, &f1) || wsbuf(w, W_F1BAD, gcap, &f1bad) || wsbuf(w, W_F1S, gcap, &f1S)))
-    return -1;
-  for (size_t g0 = 0; g0 < n_groups; g0 += gcap) {
-    const uint32_t ng = (uint32_t)std::min(gcap, n_groups - g0);
-    GroupPrepArgs ga{};
-    ga.keys_only = keys_only ? 1 : 0;
-    ga.grp_off = dgoff;
-    ga.g0 = (uint32_t)g0;
-    ga.ng = ng;
-    ga.msg_idx = didx;
-    ga.hm = hm;
-    ga.pk = vpk;
-    ga.pk_st = vpkst;
-    ga.sig = vsig;
-    ga.sig_st = vsigst;
-    ga.pr = pr;
-    ga.sr = sr;
-    if (n_agg) {
-      ga.agg_pk = apk;
-      ga.agg_pk_st = apkst;
-      ga.agg_sig = asig;
-      ga.agg_st = fold->ta_status;
-      ga.agg_pr = apr;
-      ga.agg_sr = asr;
-    }
-    ga.gP = gP;
-    ga.gmsg = gmsg;
-    ga.gst = gst;
-    ga.glines = glines;
-    if (bfe) {
-      const uint32_t fb = FE_BATCH;
-      const uint32_t nb = (ng + fb - 1) / fb;
-      ga.fe_batch = fb;
-      Pair3Args pm{};
-      pm.pk = gP;
-      pm.pk_st = gst;
-      pm.msg_idx = gmsg + g0;
-      pm.hm = hm;
-      pm.sig_lines = glines;
-      pm.stride = ng;
-      pm.n = ng;
-      pm.f_out = fbuf;
-      if (smsm) {
-        // the groups' public-key sides and states; then beside each other: the (P_g, H(m_g))
-        // Miller loops and their product tree (s), the MSM of the signature side and its lines (side 0)
-        ga.p_only = 1;
-        TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
-        if (skip_msm) HCHK(hipMemsetAsync(sfail, 1, 1, s));  // the per-batch check runs unconditionally
-        HCHK(hipEventRecord(w.ev_msm, s));
-        hipStream_t sm = w.side[0];
-        if (!skip_msm) {
-        // the bucket counters zeroed before the wait (side 0 is idle since the keys' decompression;
-        // under three slots these fills wait for free CUs: ~1 ms on the check's chain otherwise)
-        HCHK(hipMemsetAsync(ma.cnt, 0, MSM_KEYS * sizeof(uint32_t), sm));
-        HCHK(hipMemsetAsync(ma.cur, 0, MSM_KEYS * sizeof(uint32_t), sm));
-        HCHK(hipStreamWaitEvent(sm, w.ev_msm, 0));
-        ma.sig = vsig;
-        ma.sig_st = vsigst;
-        ma.agg_sig = asig;
-        ma.agg_st = n_agg ? fold->ta_status : nullptr;
-        ma.coef = coef_pi ? coef_pi : rlc_fallback.coef;
-        ma.igrp = igrp;
-        ma.gst = gst;
-        ma.n = (uint32_t)n;
-        ma.n_agg = (uint32_t)n_agg;
-        TIMED(d, "k_msm_count", sm, launch_msm_count(ma, sm));
-        TIMED(d, "k_msm_scan", sm, launch_scan(ma.cnt, MSM_KEYS, ma.off, sm));
-        TIMED(d, "k_msm_fill", sm, launch_msm_fill(ma, sm));
-        TIMED(d, "k_msm_bucket", sm, launch_msm_bucket(ma, sm));
-        TIMED(d, "k_msm_reduce", sm, launch_msm_reduce(ma, sm));
-        TIMED(d, "k_msm_sum", sm, launch_msm_sum(ma, sm));
-        // the signature side's Miller loop, beside the multi-Miller loops and their product tree:
-        // the final exponentiation's second factor, pfin[1] (lines and loop in one kernel, k_lml)
-        TIMED(d, "k_pair3_mls", sm, launch_lml(ma.total, 1, pfin, 1, 1, bbad, sm));
-        }
-        HCHK(hipEventRecord(w.ev_side[0], sm));
-        // multi-Miller loops over mmlk groups (shared squarings), then a product tree of fan-in
-        // PROD_FAN down to ONE value, pfin[0] (ping-pong between pbuf1 and pbuf2): eight products
-        // per level in each lane group instead of a chain of 64
-        Pair3Args pp{};
-        pp.pk = gP;
-        pp.pk_st = gst;
-        pp.msg_idx = gmsg + g0;
-        pp.hm = hm;
-        pp.n = (uint32_t)((ng + mmlk - 1) / mmlk);
-        pp.f_range = (uint32_t)mmlk;
-        pp.f_n = ng;
-        pp.f_out = pbuf1;
-        pp.sig_lines = mlev;
-        if (lines_at_p) TIMED(d, "k_lines_at_p", s, launch_lines_at_p(pp, mlev, s));
-        else TIMED(d, "k_mml_eval", s, launch_mml_eval(pp, mlev, s));
-        TIMED(d, "k_pair3_mml", s, launch_pair3_mml(pp, s));
-        Fp4Entry* cur = pbuf1;
-        uint32_t cur_n = pp.n;
-        if (!skip_msm) do {
-          Pair3Args pr{};
-          pr.n = (cur_n + PROD_FAN - 1) / PROD_FAN;
-          pr.f_in = cur;
-          pr.f_range = PROD_FAN;
-          pr.f_n = cur_n;
-          pr.f_out = pr.n == 1 ? pfin : (cur == pbuf2 ? pbuf3 : pbuf2);
-          TIMED(d, "k_pair3_prod", s, launch_pair3_prod(pr, s));
-          cur = pr.f_out;
-          cur_n = pr.n;
-        } while (cur_n > 1);
-        HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
-        Pair3Args pf{};
-        pf.pk_st = bbad;
-        pf.n = 1;
-        pf.f_in = pfin;
-        pf.f_range = 2;
-        pf.f_n = 2;
-        pf.status = sfail;
-        if (!skip_msm) {
-          TIMED(d, "k_pair3_fin", s, launch_pair6_fin(pf, s));
-          HCHK(hipMemsetAsync(sfail + 1, 0, 1, s));
-          TIMED(d, "k_slot_verdict", s, launch_slot_verdict(gst, sfail, ng, gver + g0, s));
-          // deferred lines: read by the per-batch check behind a failed slot-wide check and by
-          // the per-item fallback of any group that was not READY (k_slot_verdict sets sfail[1])
-          if (lines_at_p)
-            TIMED(d, "k_lines_msg", s, launch_lines_msg(defer_hm, (uint32_t)defer_msgs, s, sfail + 1));
-          // the slot-wide check failed: the per-batch check (signature sides per item and group;
-          // computed in the first pass when the check was skipped)
-          if (rlc_fallback_chunks) {
-            TIMED(d, "k_rlc", s, launch_rlc_msm(rlc_fallback, rlc_fallback_chunks, s));
-          } else {
-            TIMED(d, "k_rlc", s,
-                  launch_rlc(vpk, vpkst, vsig, vsigst, igrp, dgoff, 1, (uint32_t)n, 0, key, pr, sr, s, coef_pi, 2,
-                             sfail));
-          }
-          if (n_agg)
-            TIMED(d, "k_rlc", s,
-                  launch_rlc(apk, apkst, asig, fold->ta_status, nullptr, nullptr, 1, (uint32_t)n_agg, (uint32_t)n,
-                             key, apr, asr, s, const_cast<uint2*>(ma.coef) + n, 2, sfail));
-        }
-        ga.p_only = 0;
-        ga.guard = sfail;
-        pm.guard = sfail;
-        // the per-batch check over the multi-Miller loops' chunks (mmlk consecutive groups): their
-        // stored loops (pbuf1) are the batches' public-key sides, so no group's (P_g, H(m_g)) loop
-        // is recomputed unless its batch fails.  Per batch: the signature sides S_g summed, the
-        // lines of the sum, its loop times the stored one, one final exponentiation (3 lanes: one
-        // round of waves for the chip-sized batch count, where six lanes would take two)
-        const uint32_t nbm = (uint32_t)((ng + mmlk - 1) / mmlk);
-        ga.gS = gS;
-        ga.bS = nullptr;
-        ga.fe_batch = 1;
-        TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
-        TIMED(d, "k_group_prep", s, launch_batch_sum(gS, ng, (uint32_t)mmlk, bS, s, sfail));
-        TIMED(d, "k_slines", s, launch_slines(bS, nullptr, nullptr, nbm, blines, nbm, bbad, s, sfail));
-        Pair3Args pb{};
-        pb.sig_lines = blines;
-        pb.stride = nbm;
-        pb.n = nbm;
-        pb.f_in = pbuf1;
-        pb.f_range = 1;
-        pb.f_n = nbm;
-        pb.pk_st = bbad;
-        pb.status = bver;
-        pb.guard = sfail;
-        TIMED(d, "k_pair3_fin", s, launch_pair3_fin(pb, s));
-        HCHK(hipMemsetAsync(gcount, 0, sizeof(uint32_t), s));
-        TIMED(d, "k_batch_verdict", s,
-              launch_batch_verdict(gst, bver, ng, gver + g0, glist, gcount, s, sfail, (uint32_t)mmlk, wfirst,
-                                   (uint32_t)g0));
-        // groups of a failing batch: their own (P_g, H(m_g)) loops, then each group alone below
-        pm.list = glist;
-        pm.count = gcount;
-        TIMED(d, "k_pair3_ml", s, launch_pair3_ml(pm, s));
-        // the call's outcome for the next calls' choice (read when its event has completed)
-        if (g_adaptive.load() && d.res_head - d.res_tail < N_RES) {
-          const unsigned k = d.res_head % N_RES;
-          d.res_host[k].skipped = skip_msm ? 1 : 0;
-          HCHK(hipMemcpyAsync(&d.res_host[k].sfail, sfail, 1, hipMemcpyDeviceToHost, s));
-          HCHK(hipMemcpyAsync(&d.res_host[k].gcount, gcount, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-          HCHK(hipEventRecord(d.res_ev[k], s));
-          d.res_head++;
-        }
-      }
-      if (!smsm) {  // the per-batch check of FE_BATCH groups (below the slot-wide check's size)
-        ga.gS = gS;
-        ga.bS = bS;
-        TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
-        // the (P_g, H(m_g)) Miller loops, stored unexponentiated
-        TIMED(d, "k_pair3_ml", s, launch_pair3_ml(pm, s));
-        // per batch: the lines of sum_g S_g, one Miller loop times the batch's stored loops, one
-        // final exponentiation
-        const uint8_t* guard = nullptr;
-        TIMED(d, "k_slines", s, launch_slines(bS, nullptr, nullptr, nb, blines, nb, bbad, s, guard));
-        // the batches' signature-side loops (pfin[2b + 1]), the product trees of their stored loops
-        // (fan-in PROD_FAN, the last level into pfin[2b]), then each batch's final exponentiation
-        // multiplies just the two.  All on s: with several slots in flight a side stream here would
-        // share a hardware queue with another slot's long kernels (C2 24.4 vs 19.1 ms per slot)
-        {
-          Pair3Args ps{};
-          ps.sig_lines = blines;
-          ps.stride = nb;
-          ps.n = nb;
-          ps.f_out = pfin;
-          ps.f_out_stride = 2;
-          ps.f_out_off = 1;
-          ps.guard = guard;
-          TIMED(d, "k_pair3_mls", s, launch_pair3_mls(ps, s));
-        }
-        {
-          const Fp4Entry* cur = fbuf;
-          uint32_t cur_n = ng, span = 1;
-          while (span < fb) {
-            const uint32_t fan = std::min<uint32_t>(PROD_FAN, fb / span);
-            Pair3Args pr{};
-            pr.n = (cur_n + fan - 1) / fan;
-            pr.f_in = cur;
-            pr.f_range = fan;
-            pr.f_n = cur_n;
-            pr.guard = guard;
-            span *= fan;
-            if (span == fb) {
-              pr.f_out = pfin;
-              pr.f_out_stride = 2;
-            } else {
-              pr.f_out = tbuf;
-            }
-            TIMED(d, "k_pair3_prod", s, launch_pair3_prod(pr, s));
-            cur = pr.f_out;
-            cur_n = pr.n;
-          }
-        }
-        Pair3Args pf{};
-        pf.pk_st = bbad;
-        pf.n = nb;
-        pf.f_in = pfin;
-        pf.f_range = 2;
-        pf.f_n = 2 * nb;
-        pf.status = bver;
-        pf.guard = guard;
-        TIMED(d, "k_pair3_fin", s, launch_pair6_fin(pf, s));
-        // groups of a failing batch: checked one by one (their stored loop, their own S lines)
-        HCHK(hipMemsetAsync(gcount, 0, sizeof(uint32_t), s));
-        TIMED(d, "k_batch_verdict", s,
-              launch_batch_verdict(gst, bver, ng, gver + g0, glist, gcount, s, guard, fb, wfirst, (uint32_t)g0));
-      }
-      TIMED(d, "k_slines", s, launch_slines(gS, glist, gcount, ng, glines, ng, nullptr, s));
-      Pair3Args pg{};
-      pg.sig_lines = glines;
-      pg.stride = ng;
-      pg.n = ng;
-      pg.list = glist;
-      pg.count = gcount;
-      pg.f_in = fbuf;
-      pg.f_range = 1;
-      pg.f_n = ng;
-      pg.status = gver + g0;
-      TIMED(d, "k_pair3_fin", s, launch_pair3_fin(pg, s));
-      continue;
-    }
-    ga.skip_hm = 1;
-    // these calls are single Verifies and small batches, latency-bound: each group's sums (S kept
-    // Jacobian, no lines), then its signature side's Miller loop -- lines produced and consumed in
-    // one kernel (k_lml) -- on side stream 0 while the messages still hash; after the hashing (not
-    // its lines) the (P, H(m)) loop the same way on s, beside it; then ONE six-lane final
-    // exponentiation of the two stored loops (f1[2g], f1[2g + 1])
-    ga.gS = f1S;
-    ga.bS = nullptr;
-    ga.fe_batch = 1;
-    TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
-    hipStream_t sl = w.side[0];
-    HCHK(hipEventRecord(w.ev_msm, s));
-    HCHK(hipStreamWaitEvent(sl, w.ev_msm, 0));
-    TIMED(d, "k_pair3", sl, launch_lml(f1S, ng, f1, 2, 1, nullptr, sl));
-    HCHK(hipEventRecord(w.ev_side[0], sl));
-    if (g0 == 0 && (h_ready || hm_ready)) HCHK(hipStreamWaitEvent(s, h_ready ? h_ready : hm_ready, 0));
-    LmlArgs pa{};
-    pa.pk = gP;
-    pa.pk_st = gst;
-    pa.msg_idx = gmsg + g0;
-    pa.hm = hm;
-    pa.n = ng;
-    pa.f_out = f1;
-    pa.f_stride = 2;
-    pa.bad = f1bad;
-    TIMED(d, "k_pair3", s, launch_lml_p(pa, s));
-    HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
-    Pair3Args pf{};
-    pf.pk_st = f1bad;
-    pf.n = ng;
-    pf.f_in = f1;
-    pf.f_range = 2;
-    pf.f_n = 2 * ng;
-    pf.status = gver + g0;
-    TIMED(d, "k_pair3", s, launch_pair6_fin(pf, s));
+  if (c.hm_ready && p.bfe) HCHK(hipStreamWaitEvent(s, c.hm_ready, 0));
+  if (c.defer_msgs && !p.lines_at_p)  // the per-batch check reads the unevaluated lines
+    TIMED(d, "k_lines_msg", s, launch_lines_msg(c.defer_hm, (uint32_t)c.defer_msgs, s));
+  return 0;
+}
+
+// the groups [g0, g0 + ng) of one chunk: their sums, states and signature lines
+GroupPrepArgs group_prep_args(const VerifyCall& c, const VerifyPlan& p, const VerifyBufs& b, size_t g0, uint32_t ng) {
+  GroupPrepArgs ga{};
+  ga.keys_only = p.keys_only ? 1 : 0;
+  ga.grp_off = c.grp_off;
+  ga.g0 = (uint32_t)g0;
+  ga.ng = ng;
+  ga.msg_idx = c.msg_idx;
+  ga.hm = c.hm;
+  ga.pk = b.vpk;
+  ga.pk_st = b.vpkst;
+  ga.sig = b.vsig;
+  ga.sig_st = b.vsigst;
+  ga.pr = b.pr;
+  ga.sr = b.sr;
+  if (p.n_agg) {
+    ga.agg_pk = b.apk;
+    ga.agg_pk_st = b.apkst;
+    ga.agg_sig = b.asig;
+    ga.agg_st = c.fold->ta_status;
+    ga.agg_pr = b.apr;
+    ga.agg_sr = b.asr;
   }
+  ga.gP = b.gP;
+  ga.gmsg = b.gmsg;
+  ga.gst = b.gst;
+  ga.glines = b.glines;
+  return ga;
+}
+// the chunk's (P_g, H(m_g)) Miller loops, stored unexponentiated in fbuf
+Pair3Args group_loops_args(const VerifyCall& c, const VerifyBufs& b, size_t g0, uint32_t ng) {
+  Pair3Args pm{};
+  pm.pk = b.gP;
+  pm.pk_st = b.gst;
+  pm.msg_idx = b.gmsg + g0;
+  pm.hm = c.hm;
+  pm.sig_lines = b.glines;
+  pm.stride = ng;
+  pm.n = ng;
+  pm.f_out = b.fbuf;
+  return pm;
+}
+// behind a batched check (slot-wide or per-batch): the groups of a failing batch (glist) one by
+// one, their stored loop times their own S lines' loop
+int group_recheck(Dev& d, const VerifyCall& c, const VerifyBufs& b, size_t g0, uint32_t ng) {
+  hipStream_t s = c.s;
+  TIMED(d, "k_slines", s, launch_slines(b.gS, b.glist, b.gcount, ng, b.glines, ng, nullptr, s));
+  Pair3Args pg{};
+  pg.sig_lines = b.glines;
+  pg.stride = ng;
+  pg.n = ng;
+  pg.list = b.glist;
+  pg.count = b.gcount;
+  pg.f_in = b.fbuf;
+  pg.f_range = 1;
+  pg.f_n = ng;
+  pg.status = b.gver + g0;
+  TIMED(d, "k_pair3_fin", s, launch_pair3_fin(pg, s));
+  return 0;
+}
+
+// Group check, slot-wide (plan smsm; one chunk holds every group), with its guarded per-batch fallback
+int check_slot_wide(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b, size_t g0, uint32_t ng) {
+  hipStream_t s = c.s;
+  const size_t n = p.n, n_agg = p.n_agg, mmlk = p.mmlk;
+  const bool skip_msm = p.skip_msm;
+  uint8_t* sfail = b.sfail;
+  GroupPrepArgs ga = group_prep_args(c, p, b, g0, ng);
+  Pair3Args pm = group_loops_args(c, b, g0, ng);
+  // the groups' public-key sides and states; then beside each other: the (P_g, H(m_g))
+  // Miller loops and their product tree (s), the MSM of the signature side and its lines (side 0)
+  ga.fe_batch = FE_BATCH;
+  ga.p_only = 1;
+  TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
+  if (skip_msm) HCHK(hipMemsetAsync(sfail, 1, 1, s));  // the per-batch check runs unconditionally
+  HCHK(hipEventRecord(w.ev_msm, s));
+  hipStream_t sm = w.side[0];
+  if (!skip_msm) {
+    G2MsmArgs& ma = b.ma;
+    // the bucket counters zeroed before the wait (side 0 is idle since the keys' decompression;
+    // under three slots these fills wait for free CUs: ~1 ms on the check's chain otherwise)
+    HCHK(hipMemsetAsync(ma.cnt, 0, MSM_KEYS * sizeof(uint32_t), sm));
+    HCHK(hipMemsetAsync(ma.cur, 0, MSM_KEYS * sizeof(uint32_t), sm));
+    HCHK(hipStreamWaitEvent(sm, w.ev_msm, 0));
+    ma.sig = b.vsig;
+    ma.sig_st = b.vsigst;
+    ma.agg_sig = b.asig;
+    ma.agg_st = n_agg ? c.fold->ta_status : nullptr;
+    ma.coef = b.coef;
+    ma.igrp = b.igrp;
+    ma.gst = b.gst;
+    ma.n = (uint32_t)n;
+    ma.n_agg = (uint32_t)n_agg;
+    TIMED(d, "k_msm_count", sm, launch_msm_count(ma, sm));
+    TIMED(d, "k_msm_scan", sm, launch_scan(ma.cnt, MSM_KEYS, ma.off, sm));
+    TIMED(d, "k_msm_fill", sm, launch_msm_fill(ma, sm));
+    TIMED(d, "k_msm_bucket", sm, launch_msm_bucket(ma, sm));
+    TIMED(d, "k_msm_reduce", sm, launch_msm_reduce(ma, sm));
+    TIMED(d, "k_msm_sum", sm, launch_msm_sum(ma, sm));
+    // the signature side's Miller loop, beside the multi-Miller loops and their product tree:
+    // the final exponentiation's second factor, pfin[1] (lines and loop in one kernel, k_lml)
+    TIMED(d, "k_pair3_mls", sm, launch_lml(ma.total, 1, b.pfin, 1, 1, b.bbad, sm));
+  }
+  HCHK(hipEventRecord(w.ev_side[0], sm));
+  // multi-Miller loops over mmlk groups (shared squarings), then a product tree of fan-in
+  // PROD_FAN down to ONE value, pfin[0] (ping-pong between pbuf1 and pbuf2): eight products
+  // per level in each lane group instead of a chain of 64
+  Pair3Args pp{};
+  pp.pk = b.gP;
+  pp.pk_st = b.gst;
+  pp.msg_idx = b.gmsg + g0;
+  pp.hm = c.hm;
+  pp.n = (uint32_t)((ng + mmlk - 1) / mmlk);
+  pp.f_range = (uint32_t)mmlk;
+  pp.f_n = ng;
+  pp.f_out = b.pbuf1;
+  pp.sig_lines = b.mlev;
+  if (p.lines_at_p) TIMED(d, "k_lines_at_p", s, launch_lines_at_p(pp, b.mlev, s));
+  else TIMED(d, "k_mml_eval", s, launch_mml_eval(pp, b.mlev, s));
+  TIMED(d, "k_pair3_mml", s, launch_pair3_mml(pp, s));
+  Fp4Entry* cur = b.pbuf1;
+  uint32_t cur_n = pp.n;
+  if (!skip_msm) do {
+    Pair3Args pt{};
+    pt.n = (cur_n + PROD_FAN - 1) / PROD_FAN;
+    pt.f_in = cur;
+    pt.f_range = PROD_FAN;
+    pt.f_n = cur_n;
+    pt.f_out = pt.n == 1 ? b.pfin : (cur == b.pbuf2 ? b.pbuf3 : b.pbuf2);
+    TIMED(d, "k_pair3_prod", s, launch_pair3_prod(pt, s));
+    cur = pt.f_out;
+    cur_n = pt.n;
+  } while (cur_n > 1);
+  HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
+  if (!skip_msm) {
+    Pair3Args pf{};
+    pf.pk_st = b.bbad;
+    pf.n = 1;
+    pf.f_in = b.pfin;
+    pf.f_range = 2;
+    pf.f_n = 2;
+    pf.status = sfail;
+    TIMED(d, "k_pair3_fin", s, launch_pair6_fin(pf, s));
+    HCHK(hipMemsetAsync(sfail + 1, 0, 1, s));
+    TIMED(d, "k_slot_verdict", s, launch_slot_verdict(b.gst, sfail, ng, b.gver + g0, s));
+    // deferred lines: read by the per-batch check behind a failed slot-wide check and by
+    // the per-item fallback of any group that was not READY (k_slot_verdict sets sfail[1])
+    if (p.lines_at_p)
+      TIMED(d, "k_lines_msg", s, launch_lines_msg(c.defer_hm, (uint32_t)c.defer_msgs, s, sfail + 1));
+    // the slot-wide check failed: the per-batch check (signature sides per item and group;
+    // computed in the first pass when the check was skipped)
+    if (p.rlc_chunked) {
+      RlcMsmArgs ra = rlc_chunk_args(p, b);
+      ra.sides = 2;
+      ra.guard = sfail;
+      TIMED(d, "k_rlc", s, launch_rlc_msm(ra, rlc_chunk_count(p), s));
+    } else {
+      TIMED(d, "k_rlc", s,
+            launch_rlc(b.vpk, b.vpkst, b.vsig, b.vsigst, b.igrp, c.grp_off, 1, (uint32_t)n, 0, b.key, b.pr, b.sr, s,
+                       b.coef, 2, sfail));
+    }
+    if (n_agg)
+      TIMED(d, "k_rlc", s,
+            launch_rlc(b.apk, b.apkst, b.asig, c.fold->ta_status, nullptr, nullptr, 1, (uint32_t)n_agg, (uint32_t)n,
+                       b.key, b.apr, b.asr, s, b.coef + n, 2, sfail));
+  }
+  ga.p_only = 0;
+  ga.guard = sfail;
+  pm.guard = sfail;
+  // the per-batch check over the multi-Miller loops' chunks (mmlk consecutive groups): their
+  // stored loops (pbuf1) are the batches' public-key sides, so no group's (P_g, H(m_g)) loop
+  // is recomputed unless its batch fails.  Per batch: the signature sides S_g summed, the
+  // lines of the sum, its loop times the stored one, one final exponentiation (3 lanes: one
+  // round of waves for the chip-sized batch count, where six lanes would take two)
+  const uint32_t nbm = (uint32_t)((ng + mmlk - 1) / mmlk);
+  ga.gS = b.gS;
+  ga.bS = nullptr;
+  ga.fe_batch = 1;
+  TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
+  TIMED(d, "k_group_prep", s, launch_batch_sum(b.gS, ng, (uint32_t)mmlk, b.bS, s, sfail));
+  TIMED(d, "k_slines", s, launch_slines(b.bS, nullptr, nullptr, nbm, b.blines, nbm, b.bbad, s, sfail));
+  Pair3Args pb{};
+  pb.sig_lines = b.blines;
+  pb.stride = nbm;
+  pb.n = nbm;
+  pb.f_in = b.pbuf1;
+  pb.f_range = 1;
+  pb.f_n = nbm;
+  pb.pk_st = b.bbad;
+  pb.status = b.bver;
+  pb.guard = sfail;
+  TIMED(d, "k_pair3_fin", s, launch_pair3_fin(pb, s));
+  HCHK(hipMemsetAsync(b.gcount, 0, sizeof(uint32_t), s));
+  TIMED(d, "k_batch_verdict", s,
+        launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, sfail, (uint32_t)mmlk, b.wfirst,
+                             (uint32_t)g0));
+  // groups of a failing batch: their own (P_g, H(m_g)) loops, then each group alone below
+  pm.list = b.glist;
+  pm.count = b.gcount;
+  TIMED(d, "k_pair3_ml", s, launch_pair3_ml(pm, s));
+  // the call's outcome for the next calls' choice (read when its event has completed)
+  if (p.adaptive && d.res_head - d.res_tail < N_RES) {
+    const unsigned k = d.res_head % N_RES;
+    d.res_host[k].skipped = skip_msm ? 1 : 0;
+    HCHK(hipMemcpyAsync(&d.res_host[k].sfail, sfail, 1, hipMemcpyDeviceToHost, s));
+    HCHK(hipMemcpyAsync(&d.res_host[k].gcount, b.gcount, sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HCHK(hipEventRecord(d.res_ev[k], s));
+    d.res_head++;
+  }
+  return group_recheck(d, c, b, g0, ng);
+}
+
+// Group check, per batch of FE_BATCH groups (plan bfe, below the slot-wide check's size)
+int check_per_batch(Dev& d, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b, size_t g0, uint32_t ng) {
+  hipStream_t s = c.s;
+  const uint32_t fb = FE_BATCH;
+  const uint32_t nb = (ng + fb - 1) / fb;
+  GroupPrepArgs ga = group_prep_args(c, p, b, g0, ng);
+  ga.fe_batch = fb;
+  ga.gS = b.gS;
+  ga.bS = b.bS;
+  TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
+  // the (P_g, H(m_g)) Miller loops, stored unexponentiated
+  TIMED(d, "k_pair3_ml", s, launch_pair3_ml(group_loops_args(c, b, g0, ng), s));
+  // per batch: the lines of sum_g S_g, one Miller loop times the batch's stored loops, one
+  // final exponentiation
+  const uint8_t* guard = nullptr;
+  TIMED(d, "k_slines", s, launch_slines(b.bS, nullptr, nullptr, nb, b.blines, nb, b.bbad, s, guard));
+  // the batches' signature-side loops (pfin[2b + 1]), the product trees of their stored loops
+  // (fan-in PROD_FAN, the last level into pfin[2b]), then each batch's final exponentiation
+  // multiplies just the two.  All on s: with several slots in flight a side stream here would
+  // share a hardware queue with another slot's long kernels (C2 24.4 vs 19.1 ms per slot)
+  Pair3Args ps{};
+  ps.sig_lines = b.blines;
+  ps.stride = nb;
+  ps.n = nb;
+  ps.f_out = b.pfin;
+  ps.f_out_stride = 2;
+  ps.f_out_off = 1;
+  ps.guard = guard;
+  TIMED(d, "k_pair3_mls", s, launch_pair3_mls(ps, s));
+  const Fp4Entry* cur = b.fbuf;
+  uint32_t cur_n = ng, span = 1;
+  while (span < fb) {
+    const uint32_t fan = std::min<uint32_t>(PROD_FAN, fb / span);
+    Pair3Args pt{};
+    pt.n = (cur_n + fan - 1) / fan;
+    pt.f_in = cur;
+    pt.f_range = fan;
+    pt.f_n = cur_n;
+    pt.guard = guard;
+    span *= fan;
+    if (span == fb) {
+      pt.f_out = b.pfin;
+      pt.f_out_stride = 2;
+    } else {
+      pt.f_out = b.tbuf;
+    }
+    TIMED(d, "k_pair3_prod", s, launch_pair3_prod(pt, s));
+    cur = pt.f_out;
+    cur_n = pt.n;
+  }
+  Pair3Args pf{};
+  pf.pk_st = b.bbad;
+  pf.n = nb;
+  pf.f_in = b.pfin;
+  pf.f_range = 2;
+  pf.f_n = 2 * nb;
+  pf.status = b.bver;
+  pf.guard = guard;
+  TIMED(d, "k_pair3_fin", s, launch_pair6_fin(pf, s));
+  // groups of a failing batch: checked one by one (their stored loop, their own S lines)
+  HCHK(hipMemsetAsync(b.gcount, 0, sizeof(uint32_t), s));
+  TIMED(d, "k_batch_verdict", s,
+        launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, guard, fb, b.wfirst, (uint32_t)g0));
+  return group_recheck(d, c, b, g0, ng);
+}
+
+// Group check of small calls (no batched final exponentiation): every group on its own.
+// These calls are single Verifies and small batches, latency-bound: each group's sums (S kept
+// Jacobian, no lines), then its signature side's Miller loop -- lines produced and consumed in
+// one kernel (k_lml) -- on side stream 0 while the messages still hash; after the hashing (not
+// its lines) the (P, H(m)) loop the same way on s, beside it; then ONE six-lane final
+// exponentiation of the two stored loops (f1[2g], f1[2g + 1])
+int check_small(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b, size_t g0, uint32_t ng) {
+  hipStream_t s = c.s;
+  GroupPrepArgs ga = group_prep_args(c, p, b, g0, ng);
+  ga.skip_hm = 1;
+  ga.gS = b.f1S;
+  ga.bS = nullptr;
+  ga.fe_batch = 1;
+  TIMED(d, "k_group_prep", s, launch_group_prep(ga, s));
+  hipStream_t sl = w.side[0];
+  HCHK(hipEventRecord(w.ev_msm, s));
+  HCHK(hipStreamWaitEvent(sl, w.ev_msm, 0));
+  TIMED(d, "k_pair3", sl, launch_lml(b.f1S, ng, b.f1, 2, 1, nullptr, sl));
+  HCHK(hipEventRecord(w.ev_side[0], sl));
+  if (g0 == 0 && (c.h_ready || c.hm_ready)) HCHK(hipStreamWaitEvent(s, c.h_ready ? c.h_ready : c.hm_ready, 0));
+  LmlArgs pa{};
+  pa.pk = b.gP;
+  pa.pk_st = b.gst;
+  pa.msg_idx = b.gmsg + g0;
+  pa.hm = c.hm;
+  pa.n = ng;
+  pa.f_out = b.f1;
+  pa.f_stride = 2;
+  pa.bad = b.f1bad;
+  TIMED(d, "k_pair3", s, launch_lml_p(pa, s));
+  HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
+  Pair3Args pf{};
+  pf.pk_st = b.f1bad;
+  pf.n = ng;
+  pf.f_in = b.f1;
+  pf.f_range = 2;
+  pf.f_n = 2 * ng;
+  pf.status = b.gver + g0;
+  TIMED(d, "k_pair3", s, launch_pair6_fin(pf, s));
+  return 0;
+}
+
+// Resolve: the groups' verdicts to their items, every item of a failing group on its own, the
+// first-error reduction, and the joins of what ran beside the call
+int verify_resolve(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b) {
+  hipStream_t s = c.s;
+  const TaFold* fold = c.fold;
+  const size_t n = p.n, n_agg = p.n_agg;
   // the per-item fallback reads the messages' lines (the small calls' group checks did not wait)
-  if (!bfe && hm_ready && h_ready) HCHK(hipStreamWaitEvent(s, hm_ready, 0));
-  HCHK(hipMemsetAsync(count, 0, sizeof(uint32_t), s));
+  if (!p.bfe && c.hm_ready && c.h_ready) HCHK(hipStreamWaitEvent(s, c.hm_ready, 0));
+  HCHK(hipMemsetAsync(b.count, 0, sizeof(uint32_t), s));
   ScatterArgs sa{};
   sa.n = (uint32_t)n;
-  sa.item_grp = igrp;
-  sa.msg_idx = didx;
-  sa.hm = hm;
-  sa.pk = vpk;
-  sa.pk_st = vpkst;
-  sa.sig = vsig;
-  sa.sig_st = vsigst;
-  sa.gverdict = gver;
-  sa.grp_off = dgoff;
+  sa.item_grp = b.igrp;
+  sa.msg_idx = c.msg_idx;
+  sa.hm = c.hm;
+  sa.pk = b.vpk;
+  sa.pk_st = b.vpkst;
+  sa.sig = b.vsig;
+  sa.sig_st = b.vsigst;
+  sa.gverdict = b.gver;
+  sa.grp_off = c.grp_off;
   sa.n_agg = (uint32_t)n_agg;
   if (n_agg) {
     sa.ta_status = fold->ta_status;
-    sa.agg_pk = apk;
-    sa.agg_pk_st = apkst;
-    sa.agg_sig = asig;
+    sa.agg_pk = b.apk;
+    sa.agg_pk_st = b.apkst;
+    sa.agg_sig = b.asig;
     sa.agg_status = fold->agg_status;
   }
-  sa.status = dst;
-  sa.list = list;
-  sa.count = count;
-  if (first_only) {
-    TIMED(d, "k_first_group", s, launch_first_group(gver, (uint32_t)n_groups, wfirst + 1, s));
-    sa.first_group = wfirst + 1;
+  sa.status = c.status;
+  sa.list = b.list;
+  sa.count = b.count;
+  if (p.first_only) {
+    TIMED(d, "k_first_group", s, launch_first_group(b.gver, (uint32_t)p.n_groups, b.wfirst + 1, s));
+    sa.first_group = b.wfirst + 1;
   }
   TIMED(d, "k_scatter", s, launch_scatter(sa, s));
   // fallback: every item of a failing group on its own; passes beyond the list end exit at once
-  for (size_t base = 0; base < n + n_agg; base += fbcap) {
+  for (size_t base = 0; base < n + n_agg; base += p.fbcap) {
     TIMED(d, "k_fb_lines", s,
-          launch_fb_lines(list, count, (uint32_t)base, (uint32_t)fbcap, vsig, asig, (uint32_t)n, fbl, s));
+          launch_fb_lines(b.list, b.count, (uint32_t)base, (uint32_t)p.fbcap, b.vsig, b.asig, (uint32_t)n, b.fbl, s));
     Pair3Args pa{};
-    pa.pk = vpk;
-    pa.msg_idx = didx;
-    pa.hm = hm;
-    pa.sig_lines = fbl;
-    pa.stride = (uint32_t)fbcap;
-    pa.n = (uint32_t)fbcap;
-    pa.list = list;
-    pa.count = count;
+    pa.pk = b.vpk;
+    pa.msg_idx = c.msg_idx;
+    pa.hm = c.hm;
+    pa.sig_lines = b.fbl;
+    pa.stride = (uint32_t)p.fbcap;
+    pa.n = (uint32_t)p.fbcap;
+    pa.list = b.list;
+    pa.count = b.count;
     pa.base = (uint32_t)base;
     pa.n_items = (uint32_t)n;
-    pa.agg_pk = apk;
-    pa.agg_msg = gmsg;
-    pa.status = dst;
+    pa.agg_pk = b.apk;
+    pa.agg_msg = b.gmsg;
+    pa.status = c.status;
     pa.agg_status = n_agg ? fold->agg_status : nullptr;
     TIMED(d, "k_pair3_fallback", s, launch_pair3(pa, s));
   }
-  if (first_out) {
-    HCHK(hipMemsetAsync(first_out, 0xff, sizeof(uint32_t), s));
-    TIMED(d, "k_first_item", s, launch_first_item(dst, (uint32_t)n, first_out, s));
+  if (c.first_out) {
+    HCHK(hipMemsetAsync(c.first_out, 0xff, sizeof(uint32_t), s));
+    TIMED(d, "k_first_item", s, launch_first_item(c.status, (uint32_t)n, c.first_out, s));
   }
-  if (ta && !n_agg) {  // the aggregation ran beside the verification: join it
+  if (fold && fold->n_groups && !n_agg) {  // the aggregation ran beside the verification: join it
     HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));
   }
-  if (learned) HCHK(hipStreamWaitEvent(s, d.kl_ev, 0));  // (recorded by this call: d.mu is still held)
-  if (stats_on()) {  // HBLS_STATS=1: count the fallback items (synchronises; tests and diagnosis)
-    uint32_t c = 0;
-    HCHK(hipMemcpyAsync(&c, count, sizeof(c), hipMemcpyDeviceToHost, s));
+  if (b.learned) HCHK(hipStreamWaitEvent(s, d.kl_ev, 0));  // (recorded by this call: d.mu is still held)
+  return 0;
+}
+
+// HBLS_STATS=1: count the fallback items (synchronises; tests and diagnosis)
+int verify_stats(const VerifyCall& c, const VerifyPlan& p, const VerifyBufs& b) {
+  hipStream_t s = c.s;
+  uint32_t k = 0;
+  HCHK(hipMemcpyAsync(&k, b.count, sizeof(k), hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  g_stats[0] += p.n + p.n_agg;
+  g_stats[1] += p.n_groups;
+  g_stats[2] += k;
+  if (p.bfe) {  // only the last chunk's count is still in gcount: enough for the tests' sizes
+    HCHK(hipMemcpyAsync(&k, b.gcount, sizeof(k), hipMemcpyDeviceToHost, s));
     HCHK(hipStreamSynchronize(s));
-    g_stats[0] += n + n_agg;
-    g_stats[1] += n_groups;
-    g_stats[2] += c;
-    if (bfe) {  // only the last chunk's count is still in gcount: enough for the tests' sizes
-      HCHK(hipMemcpyAsync(&c, gcount, sizeof(c), hipMemcpyDeviceToHost, s));
-      HCHK(hipStreamSynchronize(s));
-      g_stats[3] += c;
-    }
-    if (smsm && !skip_msm) {
-      uint8_t f = 0;
-      HCHK(hipMemcpyAsync(&f, sfail, 1, hipMemcpyDeviceToHost, s));
-      HCHK(hipStreamSynchronize(s));
-      g_stats[4] += 1;
-      g_stats[5] += f ? 1 : 0;
-    }
+    g_stats[3] += k;
+  }
+  if (p.try_msm) {
+    uint8_t f = 0;
+    HCHK(hipMemcpyAsync(&f, b.sfail, 1, hipMemcpyDeviceToHost, s));
+    HCHK(hipStreamSynchronize(s));
+    g_stats[4] += 1;
+    g_stats[5] += f ? 1 : 0;
   }
   return 0;
+}
+
+// One verification, every verifying entry point's end: plan, buffers, then the phases in the
+// order they enqueue.  Fills c.vsig / c.vsigst.
+int verify_pipeline(Dev& d, Ws& w, VerifyCall& c) {
+  const VerifyKnobs knobs{g_gcap.load(),         g_fbcap.load(),     g_fe_batch_min.load(),
+                          g_slot_msm_min.load(), g_rlc_lanes.load(), g_adaptive.load()};
+  VerifyShape sh{};
+  sh.n = c.n;
+  sh.n_groups = c.n_groups;
+  sh.n_agg = (c.fold && c.fold->dv_pks) ? c.fold->n_groups : 0;
+  sh.grouped = c.grp_off != nullptr;
+  sh.first_error = c.first_out != nullptr;
+  sh.defer_msgs = c.defer_msgs;
+  sh.n_cu = d.n_cu;
+  // the adaptive history, read by the calls that could take the slot-wide check: the outcomes of
+  // the checked calls that have completed since (never a synchronisation)
+  if (knobs.adaptive && vp_slot_wide(sh, knobs))
+    while (d.res_tail != d.res_head && hipEventQuery(d.res_ev[d.res_tail % N_RES]) == hipSuccess) {
+      const SlotRes& r = d.res_host[d.res_tail % N_RES];
+      d.attack = r.skipped ? r.gcount != 0 : r.sfail != 0;
+      d.res_tail++;
+    }
+  sh.attack = d.attack;
+  VerifyPlan p;
+  if (const char* refused = verify_plan(sh, knobs, p)) return set_err(refused);
+  VerifyBufs b{};
+  if (verify_bufs(w, p, b)) return -1;
+  c.vsig = b.vsig;
+  c.vsigst = b.vsigst;
+  if (p.first_only) HCHK(hipMemsetAsync(b.wfirst, 0xff, 2 * sizeof(uint32_t), c.s));
+  if (verify_decompress(d, w, c, p, b) || verify_fold(d, w, c, b) || verify_combine(d, w, c, p, b)) return -1;
+  for (size_t g0 = 0; g0 < p.n_groups; g0 += p.gcap) {
+    const uint32_t ng = (uint32_t)std::min(p.gcap, p.n_groups - g0);
+    if (p.smsm ? check_slot_wide(d, w, c, p, b, g0, ng)
+        : p.bfe ? check_per_batch(d, c, p, b, g0, ng)
+                : check_small(d, w, c, p, b, g0, ng))
+      return -1;
+  }
+  if (verify_resolve(d, w, c, p, b)) return -1;
+  return stats_on() ? verify_stats(c, p, b) : 0;
 }
 
 // hash every distinct message to G2 (+ its Miller line chain) into hm, on stream s
@@ -2090,16 +2165,23 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
     HCHK(hipEventRecord(w.ev_side[2], hs));
     // the key cache is looked up on the device (k_pk_cached): its tables are only rewritten under
     // Dev::mu, held while this call enqueues, after every launch that may still read them
-    if (verify_pipeline(d, w, cpk, csig, dmidx + ib, hm, m, dgoffs + goff_base[c], ng, dst, sc, w.ev_side[2], nullptr,
-                        true, w.ev_h, hm + mfirst, cdefer ? mcount : 0))
-      return -1;
-    {  // the decompressed partials into the signature cache (the aggregation of these partials reads them)
-      HmEntry* vsig;
-      uint8_t* vsigst;
-      if (wsbuf(w, W_VSIG, m, &vsig) || wsbuf(w, W_VSIGST, m, &vsigst) ||
-          sc_put_release(d, w, csig, vsig, vsigst, m, sc, h0))
-        return -1;
-    }
+    VerifyCall vc;
+    vc.pks = cpk;
+    vc.sigs = csig;
+    vc.msg_idx = dmidx + ib;
+    vc.hm = hm;
+    vc.n = m;
+    vc.grp_off = dgoffs + goff_base[c];
+    vc.n_groups = ng;
+    vc.status = dst;
+    vc.s = sc;
+    vc.hm_ready = w.ev_side[2];
+    vc.h_ready = w.ev_h;
+    vc.key_cache = true;
+    vc.defer_hm = hm + mfirst;
+    vc.defer_msgs = cdefer ? mcount : 0;
+    // then the decompressed partials into the signature cache (the aggregation of these partials reads them)
+    if (verify_pipeline(d, w, vc) || sc_put_release(d, w, csig, vc.vsig, vc.vsigst, m, sc, h0)) return -1;
     LAUNCH(k_scatter_status, m, sc, dst, dord + ib, (uint32_t)m, dst_out);
     if (c) {
       HCHK(hipEventRecord(hc.ev, sc));
@@ -2117,6 +2199,15 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
   return 0;
 }
 
+// the distinct messages of a host call: the parallel dedup for large calls on hosts with the threads
+void dedup_call(const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n, MsgTable& all) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  if (n >= (1u << 16) && hw >= 4)
+    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
+  else
+    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
+}
+
 int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
                 const uint32_t* msg_len, size_t n, uint8_t* status) {
   if (n == 0) return 0;
@@ -2129,11 +2220,7 @@ int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, co
   const double t_start = now_ms();
   // global message ids, order items by (message, position), groups of <= g_gmax
   MsgTable all;
-  const unsigned hw = std::thread::hardware_concurrency();
-  if (n >= (1u << 16) && hw >= 4)
-    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
-  else
-    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
+  dedup_call(msgs, msg_off, msg_len, n, all);
   // items ordered by message id, stable (a counting sort: one pass, no comparisons)
   std::vector<size_t> order(n), mstart(all.len.size() + 1, 0);
   for (size_t k = 0; k < n; k++) mstart[all.idx[k] + 1]++;
@@ -2221,16 +2308,23 @@ int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, co
       return -1;
     // the key cache is looked up on the device (k_pk_cached): its tables are only rewritten under
     // Dev::mu, held while this call enqueues, after every launch that may still read them
-    if (verify_pipeline(d, w, dpk, dsig, didx, hm, m, dgoff, ge - gb, dst, h.s, hm_ready, nullptr, true, h_ready, hm,
-                        defer ? t.len.size() : 0))
-      return -1;
-    {  // the decompressed partials into the signature cache (the aggregation of these partials reads them)
-      HmEntry* vsig;
-      uint8_t* vsigst;
-      if (wsbuf(w, W_VSIG, m, &vsig) || wsbuf(w, W_VSIGST, m, &vsigst) ||
-          sc_put_release(d, w, dsig, vsig, vsigst, m, h.s, h))
-        return -1;
-    }
+    VerifyCall vc;
+    vc.pks = dpk;
+    vc.sigs = dsig;
+    vc.msg_idx = didx;
+    vc.hm = hm;
+    vc.n = m;
+    vc.grp_off = dgoff;
+    vc.n_groups = ge - gb;
+    vc.status = dst;
+    vc.s = h.s;
+    vc.hm_ready = hm_ready;
+    vc.h_ready = h_ready;
+    vc.key_cache = true;
+    vc.defer_hm = hm;
+    vc.defer_msgs = defer ? t.len.size() : 0;
+    // then the decompressed partials into the signature cache (the aggregation of these partials reads them)
+    if (verify_pipeline(d, w, vc) || sc_put_release(d, w, dsig, vc.vsig, vc.vsigst, m, h.s, h)) return -1;
     if (whole) LAUNCH(k_scatter_status, m, h.s, dst, dord, (uint32_t)m, dst_out);
     lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
     const double t_enq = now_ms();
@@ -2266,11 +2360,7 @@ int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* ms
   if (n == 0) return 0;
   if (n >= 0xffffffffull) return set_err("verify first error: too many items");
   MsgTable all;
-  const unsigned hw = std::thread::hardware_concurrency();
-  if (n >= (1u << 16) && hw >= 4)
-    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
-  else
-    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
+  dedup_call(msgs, msg_off, msg_len, n, all);
   std::vector<uint32_t> goff;
   for (size_t k = 0; k < n; k++)
     if (k == 0 || all.idx[k] != all.idx[k - 1] || k - goff.back() >= std::max<size_t>(1, g_gmax.load()))
@@ -2300,15 +2390,24 @@ int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* ms
     return -1;
   uint8_t* dst = (uint8_t*)pst;
   uint32_t* dfirst = (uint32_t*)pfirst;
-  if (verify_pipeline(d, w, dpk, dsig, didx, hm, n, dgoff, n_groups, dst, h.s, hm_ready, nullptr, true, h_ready, hm,
-                      defer ? all.len.size() : 0, dfirst))
-    return -1;
-  {  // the decoded signatures enter the signature cache as after hbls_verify_batch
-    HmEntry* vsig;
-    uint8_t* vsigst;
-    if (wsbuf(w, W_VSIG, n, &vsig) || wsbuf(w, W_VSIGST, n, &vsigst) || sc_put_release(d, w, dsig, vsig, vsigst, n, h.s, h))
-      return -1;
-  }
+  VerifyCall vc;
+  vc.pks = dpk;
+  vc.sigs = dsig;
+  vc.msg_idx = didx;
+  vc.hm = hm;
+  vc.n = n;
+  vc.grp_off = dgoff;
+  vc.n_groups = n_groups;
+  vc.status = dst;
+  vc.s = h.s;
+  vc.hm_ready = hm_ready;
+  vc.h_ready = h_ready;
+  vc.key_cache = true;
+  vc.defer_hm = hm;
+  vc.defer_msgs = defer ? all.len.size() : 0;
+  vc.first_out = dfirst;
+  // then the decoded signatures enter the signature cache as after hbls_verify_batch
+  if (verify_pipeline(d, w, vc) || sc_put_release(d, w, dsig, vc.vsig, vc.vsigst, n, h.s, h)) return -1;
   lk.unlock();
   uint32_t f = 0;
   std::vector<uint8_t> own;
@@ -2846,9 +2945,17 @@ int hbls_verify_device(const uint8_t* pks, const uint8_t* sigs, const uint32_t* 
   if (n == 0) return 0;
   std::lock_guard<std::mutex> lk(d->mu);
   Ws& w = ws_acquire(*d, s);
-  if (verify_pipeline(*d, w, pks, sigs, msg_idx, (const MsgEntry*)hm, n, vgrp_off, n_vgroups, status, s, nullptr,
-                      nullptr))
-    return -1;
+  VerifyCall vc;
+  vc.pks = pks;
+  vc.sigs = sigs;
+  vc.msg_idx = msg_idx;
+  vc.hm = (const MsgEntry*)hm;
+  vc.n = n;
+  vc.grp_off = vgrp_off;
+  vc.n_groups = n_vgroups;
+  vc.status = status;
+  vc.s = s;
+  if (verify_pipeline(*d, w, vc)) return -1;
   return ws_release(w, s);
 }
 
@@ -2866,9 +2973,18 @@ int hbls_verify_device_first_error(const uint8_t* pks, const uint8_t* sigs, cons
   if (n >= 0xffffffffull) return set_err("verify first error: too many items");
   std::lock_guard<std::mutex> lk(d->mu);
   Ws& w = ws_acquire(*d, s);
-  if (verify_pipeline(*d, w, pks, sigs, msg_idx, (const MsgEntry*)hm, n, vgrp_off, n_vgroups, status, s, nullptr,
-                      nullptr, false, nullptr, nullptr, 0, first))
-    return -1;
+  VerifyCall vc;
+  vc.pks = pks;
+  vc.sigs = sigs;
+  vc.msg_idx = msg_idx;
+  vc.hm = (const MsgEntry*)hm;
+  vc.n = n;
+  vc.grp_off = vgrp_off;
+  vc.n_groups = n_vgroups;
+  vc.status = status;
+  vc.s = s;
+  vc.first_out = first;
+  if (verify_pipeline(*d, w, vc)) return -1;
   return ws_release(w, s);
 }
 
@@ -3094,9 +3210,21 @@ int hbls_slot_device(const hbls_slot* a, void* stream) {
   fold.pk_table_st = a->pk_table_st;
   fold.dv_pk_table = (const G1AEntry*)a->dv_pk_table;
   fold.dv_pk_table_st = a->dv_pk_table_st;
-  if (verify_pipeline(*d, w, a->pks, a->sigs, a->msg_idx, (const MsgEntry*)a->hm, a->n, a->vgrp_off, a->n_vgroups,
-                      a->vstatus, s, w.ev_side[2], &fold, false, nullptr, (MsgEntry*)a->hm, defer ? a->n_msgs : 0))
-    return -1;
+  VerifyCall vc;
+  vc.pks = a->pks;
+  vc.sigs = a->sigs;
+  vc.msg_idx = a->msg_idx;
+  vc.hm = (const MsgEntry*)a->hm;
+  vc.n = a->n;
+  vc.grp_off = a->vgrp_off;
+  vc.n_groups = a->n_vgroups;
+  vc.status = a->vstatus;
+  vc.s = s;
+  vc.hm_ready = w.ev_side[2];
+  vc.fold = &fold;
+  vc.defer_hm = (MsgEntry*)a->hm;
+  vc.defer_msgs = defer ? a->n_msgs : 0;
+  if (verify_pipeline(*d, w, vc)) return -1;
   HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
   return ws_release(w, s);
 }

@@ -1016,3 +1016,26 @@ extern "C" long hc_dedup(const uint8_t* msgs, const uint64_t* off, const uint32_
   }
   return (long)t.len.size();
 }
+
+// vplan.h: the plan of one verification from plain values.  in: n, n_groups, n_agg, grouped,
+// first_error, defer_msgs, n_cu, attack, then the knobs gcap, fbcap, fe_batch_min, slot_msm_min,
+// rlc_lanes, adaptive.  out: n_groups, gcap, fbcap, bfe, item_always, first_only, mmlk, nb1, nb2,
+// nbcap, smsm, skip_msm, try_msm, sides1, rlc_cmax, rlc_chunked, keys_only, sparse, lines_at_p,
+// adaptive.  Returns 0, or 1 with the refusal's text in err.
+#include "../../charon_amd/csrc/vplan.h"
+extern "C" int hc_verify_plan(const uint64_t* in, uint64_t* out, char* err, size_t err_cap) {
+  const VerifyShape sh{(size_t)in[0], (size_t)in[1], (size_t)in[2], in[3] != 0, in[4] != 0, (size_t)in[5], (int)in[6],
+                       in[7] != 0};
+  const VerifyKnobs k{(size_t)in[8], (size_t)in[9], (size_t)in[10], (size_t)in[11], (size_t)in[12], in[13] != 0};
+  VerifyPlan p{};
+  if (const char* refused = verify_plan(sh, k, p)) {
+    strncpy(err, refused, err_cap - 1);
+    err[err_cap - 1] = 0;
+    return 1;
+  }
+  const uint64_t f[20] = {p.n_groups, p.gcap, p.fbcap, p.bfe, (uint64_t)p.item_always, p.first_only, p.mmlk, p.nb1, p.nb2,
+                          p.nbcap, p.smsm, p.skip_msm, p.try_msm, (uint64_t)p.sides1, p.rlc_cmax, p.rlc_chunked,
+                          p.keys_only, p.sparse, p.lines_at_p, p.adaptive};
+  memcpy(out, f, sizeof f);
+  return 0;
+}
