@@ -37,7 +37,7 @@ EXPORTS = (
     "hbls_decompress_pubkeys_device", "hbls_pubkey_cache_add", "hbls_pubkey_cache_clear", "hbls_pubkey_cache_size",
     "hbls_debug_split", "hbls_build_id", "hbls_sig_cache", "hbls_duty_signing_roots",
     "hbls_single_max", "hbls_dec_pair_max", "hbls_tune", "hbls_verify_batch_first_error",
-    "hbls_verify_device_first_error", "hbls_key_learn_stats",
+    "hbls_verify_device_first_error", "hbls_key_learn_stats", "hbls_key_wide_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -136,6 +136,7 @@ def _declare(lib):
         "hbls_pubkey_cache_clear": ([], ctypes.c_int),
         "hbls_pubkey_cache_size": ([], SZ),
         "hbls_key_learn_stats": ([P, SZ, P], ctypes.c_int),
+        "hbls_key_wide_stats": ([P, SZ, P], ctypes.c_int),
         "hbls_debug_split": ([U32], ctypes.c_int),
         "hbls_slot_device": ([ctypes.POINTER(HblsSlot), P], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
@@ -221,6 +222,16 @@ def key_learn_stats(L, max_devices: int = 32):
     check(L.hbls_key_learn_stats(out, max_devices, ctypes.byref(n)))
     return [dict(zip(("size", "capacity", "hits", "misses"), (int(v) for v in out[4 * k:4 * k + 4])))
             for k in range(n.value)]
+
+
+def key_wide_stats(L, max_devices: int = 32):
+    """Per device of the mask: the ladder tables' cumulative counters (hbls_key_wide_stats; waits
+    for the library's enqueued work)."""
+    out = (ctypes.c_uint64 * (5 * max_devices))()
+    n = ctypes.c_size_t(0)
+    check(L.hbls_key_wide_stats(out, max_devices, ctypes.byref(n)))
+    names = ("built", "wide_chunks", "narrow_chunks", "wide_items", "narrow_items")
+    return [dict(zip(names, (int(v) for v in out[5 * k:5 * k + 5]))) for k in range(n.value)]
 
 
 def check(rc: int):

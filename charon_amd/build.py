@@ -121,6 +121,48 @@ def build_hostcheck(force: bool = False, verbose: bool = True, defines=(), out: 
     return out
 
 
+WIDECHECK_PREFIX = "hbls-widecheck:"
+
+
+def widecheck_build_id(root: str = "") -> str:
+    """The id embedded in the ladder-table harness (tests/native/widecheck.cpp, `wc_build_id()`):
+    sha256 over its source, every header of charon_amd/csrc and the compiler flags, as
+    hostcheck_build_id."""
+    import hashlib
+    root = root or ROOT
+    csrc = os.path.join(root, "charon_amd", "csrc")
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "widecheck.cpp")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return WIDECHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_widecheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_widecheck.so (tests/test_key_wide_host.py): the learned keys' ladder
+    tables and the ladders through them on the CPU; test-only.  Reused when its embedded id equals
+    the tree's, as build_hostcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "widecheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_widecheck.so")
+    bid = widecheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-widecheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DWC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
 def build_c_client(force: bool = False, verbose: bool = True) -> str:
     """tests/native/cabi_client: a C program linked against libhipbls.so through include/hipbls.h
     (what the Go shim's cgo does), compiled with -std=c99 -Wall -Wextra -Werror so the header is
@@ -270,6 +312,49 @@ def build_devblocks(force: bool = False, verbose: bool = True, builds=None) -> d
     return paths
 
 
+WIDEDEV_PREFIX = "hbls-widedev:"
+
+
+def widedev_build_id(root: str = "") -> str:
+    """The id embedded in the ladder-table device harness (tests/native/widedev.hip,
+    tests/test_gpu_key_wide.py; `wd_build_id()`): sha256 over its source, the device harnesses'
+    shared devblocks.h, every header of charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "widedev.hip"), os.path.join(native, "devblocks.h")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return WIDEDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_widedev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_widedev.so: the learned keys' ladder tables and the ladders through them
+    on the device, a harness of its own like the curve and hash harnesses (one unit, fp.h's default
+    HB_ARG_LANES); test-only.  Reused when its embedded id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "widedev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_widedev.so")
+    bid = widedev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-widedev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DWD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -317,7 +402,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_devblocks_all):
+    for fn in (build_c_client, build_widecheck, build_devblocks_all, build_widedev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -786,6 +786,94 @@ HD G1J g1l_msm_ladder(const G1J* __restrict__ tab, const Pair* __restrict__ coef
   return g1l_to_jac(R);
 }
 
+// ---- Ladder tables of learned keys (vbatch.hip k_pk_wide, DESIGN.md §4 "Key ladder tables").  A
+// key's table holds the 15 affine points
+//     T[d - 1] = [d0] P + [d1] 2^16 P + [d2] phi(P) + [d3] 2^16 phi(P),   d = d0 + 2 d1 + 4 d2 + 8 d3,
+// stored words below 2p (what l_from takes), so r = a + b lambda with a = a_lo + 2^16 a_hi and b
+// likewise is a 16-step ladder: step j adds the entry chosen by bits j of (a_lo, a_hi, b_lo, b_hi).
+struct G1WidePt {
+  Fp x, y;
+};
+constexpr uint32_t KEY_WIDE_PTS = 15;
+constexpr uint32_t KEY_WIDE_NONE = 0xffffffffu;  // "no table" where an entry number is expected
+
+// The table of an affine P of order r (no entry is then at infinity: 0 < d0 + 2^16 d1 +
+// lambda (d2 + 2^16 d3) has no multiple of r among its values, as |coefficients| < 2^17): 16 lazy
+// doublings give Q = 2^16 P, the sums follow in Jacobian coordinates -- an odd d adds P to entry
+// d - 1, an even one Q to entry d - 2, d = 12 is phi of entry 3 -- and ONE inversion makes all 15
+// affine (Montgomery's trick).  A zero Z (never for such a P) is replaced by 1 so that the product
+// stays invertible, as vbatch.hip rlc_tab_g1 does.
+HDNI void g1_wide_build(const G1A& P, G1WidePt* __restrict__ out) {
+  const Fp beta = fp_from_const(G1_BETA);
+  G1J T[KEY_WIDE_PTS + 1];
+  Fp pre[KEY_WIDE_PTS + 1];
+  G1L q = {l_from(P.x), l_from(P.y), l_from(fp_one()), false};
+  HB_NOUNROLL for (int i = 0; i < 16; i++) q = g1l_dbl(q);
+  T[1] = jac_from_aff(P);
+  T[2] = g1l_to_jac(q);
+  HB_NOUNROLL for (uint32_t d = 3; d <= KEY_WIDE_PTS; d++) {
+    if (d == 4 || d == 8 || d == 12) {
+      const G1J s = T[d >> 2];
+      T[d] = {fp_mul(s.X, beta), s.Y, s.Z};
+    } else if (d & 1u) {
+      T[d] = jac_add_aff(T[d - 1], P);
+    } else {
+      T[d] = jac_add(T[d - 2], T[2]);
+    }
+  }
+  Fp acc = fp_one();
+  HB_NOUNROLL for (uint32_t d = 1; d <= KEY_WIDE_PTS; d++) {
+    if (fp_is_zero(T[d].Z)) T[d].Z = fp_one();
+    pre[d] = acc;
+    acc = fp_mul(acc, T[d].Z);
+  }
+  Fp inv = fp_inv(acc);
+  HB_NOUNROLL for (uint32_t d = KEY_WIDE_PTS; d >= 1; d--) {
+    const Fp zi = fp_mul(inv, pre[d]);
+    inv = fp_mul(inv, T[d].Z);
+    const Fp zi2 = fp_sqr(zi);
+    out[d - 1] = {fp_mul(T[d].X, zi2), fp_mul(T[d].Y, fp_mul(zi2, zi))};
+  }
+}
+
+// the table entry (1-based; 0: none) of step j for the pair (a, b)
+HD uint32_t wide_sel(uint32_t a, uint32_t b, int j) {
+  return ((a >> j) & 1u) | (((a >> (j + 16)) & 1u) << 1) | (((b >> j) & 1u) << 2) | (((b >> (j + 16)) & 1u) << 3);
+}
+
+// g1l_msm_ladder over the tables of learned keys: item i's table is wide[15 ent[i] ..]; 16
+// doublings per chunk and at most 16 mixed additions per item.  The same group element.
+template <class Pair>  // uint2 on the device
+HD G1J g1l_msm_ladder_wide(const G1WidePt* __restrict__ wide, const uint32_t* __restrict__ ent,
+                           const Pair* __restrict__ coef, uint32_t first, uint32_t cnt) {
+  G1L R = g1l_infinity();
+  HB_NOUNROLL for (int j = 15; j >= 0; j--) {
+    R = g1l_dbl(R);
+    HB_NOUNROLL for (uint32_t k = 0; k < cnt; k++) {
+      const uint32_t i = first + k;
+      const Pair ab = coef[i];
+      const uint32_t sel = wide_sel(ab.x, ab.y, j);
+      if (!sel) continue;
+      const G1WidePt T = wide[(uint64_t)KEY_WIDE_PTS * ent[i] + (sel - 1u)];
+      R = g1l_madd(R, l_from(T.x), l_from(T.y));
+    }
+  }
+  return g1l_to_jac(R);
+}
+
+// its one-item form (vbatch.hip k_rlc<1>): [a + b lambda] P from P's table t[0 .. 14]
+HD G1J g1l_mul_wide(const G1WidePt* __restrict__ t, uint32_t a, uint32_t b) {
+  G1L R = g1l_infinity();
+  HB_NOUNROLL for (int j = 15; j >= 0; j--) {
+    R = g1l_dbl(R);
+    const uint32_t sel = wide_sel(a, b, j);
+    if (!sel) continue;
+    const G1WidePt T = t[sel - 1u];
+    R = g1l_madd(R, l_from(T.x), l_from(T.y));
+  }
+  return g1l_to_jac(R);
+}
+
 // The sparse coefficient format of the chunk ladders when no bucket MSM reads the coefficients
 // (vbatch.hip rlc_digits): r = A + B lambda, A = sum_j u_j 4^j and B = sum_j v_j 4^j over
 // RLC_DIGITS = 22 positions, every (u_j, v_j) one of the eight nonzero pairs of {-1, 0, 1}^2 --

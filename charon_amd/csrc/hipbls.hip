@@ -317,6 +317,7 @@ enum WsId {
   W_MLEV,                                                                          // its evaluated Miller lines
   W_PFIN, W_TBUF, W_F1, W_F1BAD, W_F1S, W_FIRST,                                                                  // final exponentiations' factors
   W_KLMISS, W_KLCNT,  // learned key cache: the call's missing keys (partials' keys, then DV keys) and their two counts
+  W_KLENT, W_KLMENT,  // its ladder tables: every key's entry number (lookup), every miss's (learn -> k_pk_wide)
   W_COUNT_
 };
 
@@ -422,6 +423,11 @@ struct Dev {
   // emptied (0: not yet, or dropped by a reset); kl_ctr stays for the device's lifetime.
   DevBuf kl_keys, kl_ent, kl_st, kl_idx, kl_ctr;
   size_t kl_cap = 0, kl_tcap = 0;
+  // the ladder tables of its first kl_wcap entries (ec28.h G1WidePt, 15 per entry; HBLS_KEY_WIDE),
+  // written by k_pk_wide behind k_pk_learn and read by the combinations of later calls -- which
+  // run behind their own lookup, so the ordering chain below covers them
+  DevBuf kl_wide;
+  size_t kl_wcap = 0;
   // ORDERING INVARIANT of the learned key cache.  Every kernel that touches the table runs on the
   // side stream 0 of some workspace set, enqueued under `mu`, in the order
   //     wait(kl_ev); k_pk_lookup ...; k_pk_learn ...; record(kl_ev)
@@ -477,6 +483,10 @@ uint64_t g_sc_k0 = 0x243f6a8885a308d3ull, g_sc_k1 = 0x13198a2e03707344ull;  // k
 // that uses it.
 std::atomic<size_t> g_key_learn{size_t(1) << 21};
 constexpr size_t KEY_LEARN_MAX = size_t(1) << 30;
+// HBLS_KEY_WIDE / hbls_tune: how many of those entries also get a ladder table (15 affine points,
+// 1440 B; at most the cache's capacity, the default; 0 = none): 2 M x 1440 B = 3.0 GB per device,
+// allocated with the cache.  A new value empties the cache.
+std::atomic<size_t> g_key_wide{KEY_LEARN_MAX};
 
 std::mutex g_init_mu;
 std::vector<Dev*> g_devs;  // in device-mask order (hbls_debug_split: each ordinal repeated); g_devs_mu
@@ -638,6 +648,7 @@ int init_mask(uint32_t mask) {
   g_hash_split = env_size("HBLS_HASH_SPLIT", 1) != 0;
   g_fe18_max = env_size("HBLS_FE18_MAX", g_fe18_max.load());
   g_key_learn = std::min(env_size("HBLS_KEY_LEARN", g_key_learn.load()), KEY_LEARN_MAX);
+  g_key_wide = std::min(env_size("HBLS_KEY_WIDE", g_key_wide.load()), KEY_LEARN_MAX);
   g_ws_sets = (int)std::min<size_t>(N_WS_MAX, std::max<size_t>(1, env_size("HBLS_WS_SETS", 3)));
   {
     size_t sc = env_size("HBLS_SIG_CACHE", g_sc_cap.load());
@@ -919,10 +930,10 @@ int kl_reset(Dev& d, bool release) {
   if (!d.kl_cap && !release) return 0;
   HCHK(hipSetDevice(d.ord));
   if (drain_lib_streams(d)) return -1;
-  d.kl_cap = d.kl_tcap = 0;
+  d.kl_cap = d.kl_tcap = d.kl_wcap = 0;
   d.kl_ev_set = false;
   if (release)
-    for (DevBuf* b : {&d.kl_keys, &d.kl_ent, &d.kl_st, &d.kl_idx}) {
+    for (DevBuf* b : {&d.kl_keys, &d.kl_ent, &d.kl_st, &d.kl_idx, &d.kl_wide}) {
       if (b->p) HCHK(hipFree(b->p));
       *b = DevBuf{};
     }
@@ -940,6 +951,14 @@ int kl_table(Dev& d, hipStream_t ss, KeyLearnTab* t) {
     while (tcap < 2 * cap) tcap *= 2;
     void* p;
     const bool first = d.kl_ctr.p == nullptr;
+    const size_t wcap = std::min(g_key_wide.load(), cap);
+    const size_t wbytes = wcap * KEY_WIDE_PTS * sizeof(G1WidePt);  // (exact: ensure_buf's slack would be 0.75 GB)
+    if (d.kl_wide.cap < wbytes) {
+      if (d.kl_wide.p) HCHK(hipFree(d.kl_wide.p));
+      d.kl_wide = DevBuf{};
+      HCHK(hipMalloc(&d.kl_wide.p, wbytes));
+      d.kl_wide.cap = wbytes;
+    }
     if (ensure_buf(d.kl_keys, 48 * cap, &p) || ensure_buf(d.kl_ent, cap * sizeof(G1AEntry), &p) ||
         ensure_buf(d.kl_st, cap, &p) || ensure_buf(d.kl_idx, tcap * sizeof(uint32_t), &p) ||
         ensure_buf(d.kl_ctr, sizeof(KeyLearnCtr), &p))
@@ -949,6 +968,7 @@ int kl_table(Dev& d, hipStream_t ss, KeyLearnTab* t) {
     HCHK(hipMemsetAsync(&((KeyLearnCtr*)d.kl_ctr.p)->size, 0, sizeof(uint32_t), ss));
     d.kl_cap = cap;
     d.kl_tcap = tcap;
+    d.kl_wcap = wcap;
   }
   t->keys = (uint8_t*)d.kl_keys.p;
   t->ent = (G1AEntry*)d.kl_ent.p;
@@ -957,14 +977,16 @@ int kl_table(Dev& d, hipStream_t ss, KeyLearnTab* t) {
   t->ctr = (KeyLearnCtr*)d.kl_ctr.p;
   t->cap = (uint32_t)d.kl_cap;
   t->tcap = (uint32_t)d.kl_tcap;
+  t->wide = (G1WidePt*)d.kl_wide.p;
+  t->wcap = (uint32_t)d.kl_wcap;
   return 0;
 }
 // The keys of one array through the cache on ss: hits copied, the misses listed at miss[0 ..
 // *mcount) and decompressed there (labelled k_pk_miss, not k_dec_pk: with every key cached these
 // launches are empty, and a per-key rate computed from them would mean nothing)
 int kl_keys(Dev& d, const KeyLearnTab& t, const uint8_t* pks, size_t n, G1AEntry* out, uint8_t* st, uint32_t* miss,
-            uint32_t* mcount, hipStream_t ss) {
-  TIMED(d, "k_pk_lookup", ss, launch_pk_lookup(t, pks, (uint32_t)n, g_sc_k0, g_sc_k1, out, st, miss, mcount, ss));
+            uint32_t* mcount, uint32_t* went, hipStream_t ss) {
+  TIMED(d, "k_pk_lookup", ss, launch_pk_lookup(t, pks, (uint32_t)n, g_sc_k0, g_sc_k1, out, st, miss, mcount, went, ss));
   TIMED(d, "k_pk_miss", ss, launch_pk_miss(pks, (uint32_t)n, miss, mcount, out, st, ss));
   return 0;
 }
@@ -1051,6 +1073,9 @@ struct VerifyBufs {
   G2JEntry* f1S;
   RlcKey key;
   bool learned;  // decompress recorded Dev::kl_ev for this call (resolve joins it)
+  // the learned keys' ladder tables for the key sides of the combinations: the partials' keys and
+  // the DV keys (ent null unless this call's keys came through the learned cache's lookup)
+  KeyWideRef kw, akw;
 };
 
 // chunks of the chunked combination (an upper bound: a group's last chunk may be short)
@@ -1118,13 +1143,18 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
   const bool learn_dv = !c.key_cache && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
   KeyLearnTab kl{};
   uint32_t *kmiss = nullptr, *kcnt = nullptr;  // taken here: whether there is a table is only known now
+  uint32_t *kent = nullptr, *kment = nullptr;
   if (learn_pk || learn_dv) {
     // the ordering chain of Dev::kl_ev: behind the last call's k_pk_learn
     if (d.kl_ev_set) HCHK(hipStreamWaitEvent(w.side[0], d.kl_ev, 0));
     if (kl_table(d, w.side[0], &kl)) return -1;
     if (kl.cap) {
-      if (wsbuf(w, W_KLMISS, n + n_agg, &kmiss) || wsbuf(w, W_KLCNT, 2, &kcnt)) return -1;
+      if (wsbuf(w, W_KLMISS, n + n_agg, &kmiss) || wsbuf(w, W_KLCNT, 2, &kcnt) ||
+          wsbuf(w, W_KLENT, n + n_agg, &kent) || wsbuf(w, W_KLMENT, n + n_agg, &kment))
+        return -1;
       HCHK(hipMemsetAsync(kcnt, 0, 2 * sizeof(uint32_t), w.side[0]));
+      b.kw.ctr = b.akw.ctr = kl.ctr;
+      b.kw.wide = b.akw.wide = kl.wide;
     }
   }
   if (fold && fold->pk_table) {
@@ -1136,7 +1166,8 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
                            (const uint8_t*)d.kc_st.p, (const uint32_t*)d.kc_hidx.p, (uint32_t)d.kc_tcap, g_sc_k0,
                            g_sc_k1, b.vpk, b.vpkst, w.side[0]));
   } else if (learn_pk && kl.cap) {
-    if (kl_keys(d, kl, c.pks, n, b.vpk, b.vpkst, kmiss, kcnt, w.side[0])) return -1;
+    if (kl_keys(d, kl, c.pks, n, b.vpk, b.vpkst, kmiss, kcnt, kent, w.side[0])) return -1;
+    if (kl.wcap) b.kw.ent = kent;
   } else {
     TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(c.pks, (uint32_t)n, b.vpk, b.vpkst, w.side[0]));
   }
@@ -1145,7 +1176,8 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
     b.apk = const_cast<G1AEntry*>(fold->dv_pk_table);
     b.apkst = const_cast<uint8_t*>(fold->dv_pk_table_st);
   } else if (learn_dv && kl.cap) {
-    if (kl_keys(d, kl, fold->dv_pks, n_agg, b.apk, b.apkst, kmiss + n, kcnt + 1, w.side[0])) return -1;
+    if (kl_keys(d, kl, fold->dv_pks, n_agg, b.apk, b.apkst, kmiss + n, kcnt + 1, kent + n, w.side[0])) return -1;
+    if (kl.wcap) b.akw.ent = kent + n;
   } else if (n_agg) {
     TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(fold->dv_pks, (uint32_t)n_agg, b.apk, b.apkst, w.side[0]));
   }
@@ -1160,11 +1192,11 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
   if (b.learned) {
     if (learn_pk)
       TIMED(d, "k_pk_learn", w.side[0],
-            launch_pk_learn(kl, c.pks, (uint32_t)n, kmiss, kcnt, g_sc_k0, g_sc_k1, b.vpk, b.vpkst, w.side[0]));
+            launch_pk_learn(kl, c.pks, (uint32_t)n, kmiss, kcnt, g_sc_k0, g_sc_k1, b.vpk, b.vpkst, kment, w.side[0]));
     if (learn_dv)
       TIMED(d, "k_pk_learn", w.side[0],
             launch_pk_learn(kl, fold->dv_pks, (uint32_t)n_agg, kmiss + n, kcnt + 1, g_sc_k0, g_sc_k1, b.apk, b.apkst,
-                            w.side[0]));
+                            kment + n, w.side[0]));
     HCHK(hipEventRecord(d.kl_ev, w.side[0]));
     d.kl_ev_set = true;
   }
@@ -1220,6 +1252,7 @@ RlcMsmArgs rlc_chunk_args(const VerifyPlan& p, const VerifyBufs& b) {
   ra.sout = b.sr;
   ra.always = p.item_always;
   ra.sides = p.sides1;
+  ra.kw = b.kw;
   return ra;
 }
 
@@ -1237,7 +1270,7 @@ int verify_combine(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, Veri
   } else {
     TIMED(d, "k_rlc", s,
           launch_rlc(b.vpk, b.vpkst, p.keys_only ? nullptr : b.vsig, p.keys_only ? nullptr : b.vsigst, b.igrp,
-                     c.grp_off, p.item_always, (uint32_t)n, 0, b.key, b.pr, b.sr, s, b.coef, p.sides1));
+                     c.grp_off, p.item_always, (uint32_t)n, 0, b.key, b.pr, b.sr, s, b.coef, p.sides1, nullptr, b.kw));
     HCHK(hipStreamWaitEvent(s, w.ev_side[1], 0));  // the groups' states below read the signatures
   }
   if (n_agg) {
@@ -1255,7 +1288,7 @@ int verify_combine(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, Veri
     TIMED(d, "k_rlc", s,
           launch_rlc(b.apk, b.apkst, key_side ? nullptr : b.asig, key_side ? nullptr : c.fold->ta_status, nullptr,
                      nullptr, p.bfe ? 1 : 0, (uint32_t)n_agg, (uint32_t)n, b.key, b.apr, b.asr, s,
-                     p.try_msm ? b.coef + n : nullptr, p.sides1));
+                     p.try_msm ? b.coef + n : nullptr, p.sides1, nullptr, b.akw));
     HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));  // the groups' states below read the aggregates
   }
   // small calls (no batched final exponentiation): the groups' sums and signature lines do not
@@ -3074,6 +3107,33 @@ int hbls_key_learn_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
   return 0;
 }
 
+// The ladder tables of the learned keys, per device of the mask and cumulative: out[5 k + 0] tables
+// built, + 1 / + 2 chunks of the chunked combination's key side combined through tables / without,
+// + 3 / + 4 per-item key-side ladders through tables / without.  Waits like hbls_key_learn_stats.
+int hbls_key_wide_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
+  if (ensure_init()) return -1;
+  if (!out || !n_devices) return set_err("hbls_key_wide_stats: null arguments");
+  size_t k = 0;
+  for (Dev* d : devs()) {
+    if (k == max_devices) break;
+    std::lock_guard<std::mutex> lk(d->mu);
+    HCHK(hipSetDevice(d->ord));
+    KeyLearnCtr c{};
+    if (d->kl_ctr.p) {
+      if (drain_lib_streams(*d)) return -1;
+      HCHK(hipMemcpy(&c, d->kl_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    out[5 * k + 0] = c.wide_built;
+    out[5 * k + 1] = c.wide_chunks;
+    out[5 * k + 2] = c.narrow_chunks;
+    out[5 * k + 3] = c.wide_items;
+    out[5 * k + 4] = c.narrow_items;
+    k++;
+  }
+  *n_devices = k;
+  return 0;
+}
+
 // Test switch of the in-process multi-device split: every device of the mask is driven through
 // `copies` contexts (streams, workspaces, host thread), so host-buffer calls shard over them as
 // over several GPUs (for_each_device) on a one-GPU box.  Call while no other call is in flight.
@@ -3284,6 +3344,22 @@ int hbls_tune(const char* name, size_t value, size_t* previous) {
       for (Dev* d : devs()) {
         std::lock_guard<std::mutex> lk(d->mu);
         if (kl_reset(*d, value == 0)) return -1;
+      }
+    return 0;
+  }
+  if (strcmp(name, "HBLS_KEY_WIDE") == 0) {  // likewise: the tables are built as keys are learned (0: freed)
+    value = std::min(value, KEY_LEARN_MAX);
+    const size_t old = g_key_wide.exchange(value);
+    if (previous) *previous = old;
+    if (old != value)
+      for (Dev* d : devs()) {
+        std::lock_guard<std::mutex> lk(d->mu);
+        if (kl_reset(*d, false)) return -1;
+        if (value == 0 && d->kl_wide.p) {
+          HCHK(hipSetDevice(d->ord));
+          HCHK(hipFree(d->kl_wide.p));
+          d->kl_wide = DevBuf{};
+        }
       }
     return 0;
   }

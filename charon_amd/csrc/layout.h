@@ -231,7 +231,12 @@ void launch_pk_cached(const uint8_t* pks, uint32_t n, const uint8_t* keys, const
 struct KeyLearnCtr {
   unsigned long long hits, misses;  // keys looked up, cumulative
   uint32_t size, pad;               // entries taken (the last wave of a filling call may count past cap)
+  // ladder tables (hbls_key_wide_stats), cumulative: tables built; chunks of k_rlc_msm's key side
+  // combined through tables / without; per-item ladders of k_rlc<1> through tables / without
+  unsigned long long wide_built, wide_chunks, narrow_chunks, wide_items, narrow_items;
 };
+// Entries [0, wcap) also have a ladder table (ec28.h G1WidePt, KEY_WIDE_PTS per entry at
+// wide[15 e ..]), built by k_pk_wide behind k_pk_learn when the key is good and finite.
 struct KeyLearnTab {
   uint8_t* keys;  // 48 bytes per entry
   G1AEntry* ent;
@@ -239,13 +244,24 @@ struct KeyLearnTab {
   uint32_t* idx;  // tcap slots: entry + 1, 0 = empty
   KeyLearnCtr* ctr;
   uint32_t cap, tcap;
+  G1WidePt* wide;
+  uint32_t wcap;
 };
+// What the key side of a combination needs to go through the tables: each key's entry number
+// (KEY_WIDE_NONE: no table; ent null: none has one), the tables, the counters (nullable)
+struct KeyWideRef {
+  const uint32_t* ent;
+  const G1WidePt* wide;
+  KeyLearnCtr* ctr;
+};
+// went (nullable): each key's entry number when it is a hit with a ladder table, else KEY_WIDE_NONE
 void launch_pk_lookup(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, uint64_t k0, uint64_t k1, G1AEntry* out,
-                      uint8_t* st, uint32_t* miss, uint32_t* mcount, hipStream_t s);
+                      uint8_t* st, uint32_t* miss, uint32_t* mcount, uint32_t* went, hipStream_t s);
 void launch_pk_miss(const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount, G1AEntry* out,
                     uint8_t* st, hipStream_t s);
+// ment: workspace of n entry numbers (miss j's entry, handed from k_pk_learn to k_pk_wide)
 void launch_pk_learn(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount,
-                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, hipStream_t s);
+                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, uint32_t* ment, hipStream_t s);
 // Chunk plans and the multi-scalar random linear combination (vbatch.hip k_plan_*, k_rlc_msm).
 constexpr uint32_t RLC_CHUNK = 16;  // items per lane of k_rlc_msm
 struct RlcMsmArgs {
@@ -268,15 +284,19 @@ struct RlcMsmArgs {
   int always;     // random r for groups of one item too (batched final exponentiation)
   int sides;      // 1: public-key side only (coef written); 2: signature side only (coef read); 3: both
   const uint8_t* guard;  // nullable: nothing unless *guard != 0
+  // A dense key-side launch (sides 1) combines a chunk whose items all have an entry number through
+  // their ladder tables (ec28.h g1l_msm_ladder_wide): phase 1 then writes its coefficients only
+  KeyWideRef kw;
 };
 void launch_plan(const uint32_t* grp_off, uint32_t ng, uint32_t cmax, uint32_t* cnt, uint32_t* coff,
                  uint32_t* cfirst, uint32_t* ccount, hipStream_t s);
 void launch_rlc_msm(const RlcMsmArgs& a, uint32_t max_chunks, hipStream_t s);
-// per item; coef (nullable) as RlcMsmArgs::coef with `sides`, guard as RlcMsmArgs::guard
+// per item; coef (nullable) as RlcMsmArgs::coef with `sides`, guard as RlcMsmArgs::guard; kw: with
+// sides 1, a lane whose key has an entry number runs its ladder through the key's table
 void launch_rlc(const G1AEntry* pk, const uint8_t* pk_st, const HmEntry* sig, const uint8_t* sig_st,
                 const uint32_t* item_grp, const uint32_t* grp_off, int always, uint32_t n, uint32_t key_base,
                 const RlcKey& key, G1JEntry* pout, G2JEntry* sout, hipStream_t s, uint2* coef = nullptr,
-                int sides = 3, const uint8_t* guard = nullptr);
+                int sides = 3, const uint8_t* guard = nullptr, const KeyWideRef& kw = KeyWideRef{});
 // exclusive scan of cnt[0..n) into off[0..n], off[n] = total (one workgroup)
 void launch_scan(const uint32_t* cnt, uint32_t n, uint32_t* off, hipStream_t s);
 struct GroupPrepArgs {

@@ -352,10 +352,11 @@ __device__ __forceinline__ bool kc_key_eq(const uint4* a, const uint4* b) {
 __global__ __launch_bounds__(64) void k_pk_lookup(KeyLearnTab t, const uint8_t* __restrict__ pks, uint32_t n,
                                                   uint64_t k0, uint64_t k1, G1AEntry* __restrict__ out,
                                                   uint8_t* __restrict__ st, uint32_t* __restrict__ miss,
-                                                  uint32_t* __restrict__ mcount) {
+                                                  uint32_t* __restrict__ mcount, uint32_t* __restrict__ went) {
   const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = i < n;
   bool hit = false;
+  uint32_t we = KEY_WIDE_NONE;  // the hit's entry when it has a ladder table
   if (in) {
     uint4 kb[3];
     kc_key_load(pks + 48ull * i, kb);
@@ -366,12 +367,16 @@ __global__ __launch_bounds__(64) void k_pk_lookup(KeyLearnTab t, const uint8_t* 
       uint4 ke[3];
       kc_key_load(t.keys + 48ull * (v - 1), ke);
       if (kc_key_eq(ke, kb)) {
-        out[i] = t.ent[v - 1];
-        st[i] = t.st[v - 1];
+        const G1AEntry e = t.ent[v - 1];
+        const uint8_t es = t.st[v - 1];
+        out[i] = e;
+        st[i] = es;
+        if (v - 1 < t.wcap && !es && !e.inf) we = v - 1;
         hit = true;
         break;
       }
     }
+    if (went) went[i] = we;
   }
   const uint64_t mm = __ballot(in && !hit), hm = __ballot(hit);
   const uint32_t lane = threadIdx.x & 63u;
@@ -409,7 +414,7 @@ __global__ KB_OCC(HB_OCC_SUBG) void k_pk_miss_subgroup(const uint32_t* __restric
 __global__ __launch_bounds__(64) void k_pk_learn(KeyLearnTab t, const uint8_t* __restrict__ pks,
                                                  const uint32_t* __restrict__ miss, const uint32_t* __restrict__ mcount,
                                                  uint64_t k0, uint64_t k1, const G1AEntry* __restrict__ pts,
-                                                 const uint8_t* __restrict__ st) {
+                                                 const uint8_t* __restrict__ st, uint32_t* __restrict__ ment) {
   const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
   const bool in = j < *mcount;
   const uint64_t am = __ballot(in);
@@ -420,7 +425,9 @@ __global__ __launch_bounds__(64) void k_pk_learn(KeyLearnTab t, const uint8_t* _
   if (lane == 0 && t.ctr->size < t.cap) base = atomicAdd(&t.ctr->size, (uint32_t)__popcll(am));
   base = __shfl(base, 0);
   const uint32_t e = base + __popcll(am & ((1ull << lane) - 1));
-  if (!in || base >= t.cap || e >= t.cap) return;
+  const bool took = in && base < t.cap && e < t.cap;
+  if (in) ment[j] = took ? e : KEY_WIDE_NONE;  // for k_pk_wide
+  if (!took) return;
   const uint32_t i = miss[j];
   uint4 kb[3];
   kc_key_load(pks + 48ull * i, kb);
@@ -430,6 +437,31 @@ __global__ __launch_bounds__(64) void k_pk_learn(KeyLearnTab t, const uint8_t* _
   const uint32_t home = kc_hash(kb, k0, k1) & (t.tcap - 1);
   for (uint32_t q = 0; q < t.tcap; q++)  // load factor <= 1/2: a free slot exists
     if (atomicCAS(&t.idx[(home + q) & (t.tcap - 1)], 0u, e + 1) == 0u) return;
+}
+// The ladder tables of the misses that took an entry below wcap and are good, finite keys (ec28.h
+// g1_wide_build), one lane per listed key behind k_pk_learn; every other miss gets none, and the
+// lookup never reports such an entry.  Paid once per key: the table phase and half the ladder steps
+// of every later combination of the key are what it saves.
+__global__ KB_OCC(HB_OCC_DECPK) void k_pk_wide(KeyLearnTab t, const uint32_t* __restrict__ miss,
+                                               const uint32_t* __restrict__ mcount,
+                                               const uint32_t* __restrict__ ment,
+                                               const G1AEntry* __restrict__ pts, const uint8_t* __restrict__ st) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  const uint32_t j = blockIdx.x * blockDim.x + threadIdx.x;
+  bool build = false;
+  uint32_t e = KEY_WIDE_NONE, i = 0;
+  if (j < *mcount) {
+    e = ment[j];
+    i = miss[j];
+    build = e < t.wcap && !st[i] && !pts[i].inf;
+  }
+  const uint64_t bm = __ballot(build);
+  if (!bm) return;
+  if ((threadIdx.x & 63u) == 0) atomicAdd(&t.ctr->wide_built, (unsigned long long)__popcll(bm));
+  if (!build) return;
+  const G1AEntry pe = pts[i];
+  g1_wide_build(G1A{pe.x, pe.y, false}, t.wide + (uint64_t)KEY_WIDE_PTS * e);
+#endif
 }
 
 // the random coefficient r = a + b lambda of entry `item` (SHA-256 of key || item, one block)
@@ -476,7 +508,8 @@ __global__ KB_OCC(HB_OCC_RLC) void k_rlc(const G1AEntry* __restrict__ pk, const 
                          const HmEntry* __restrict__ sig, const uint8_t* __restrict__ sig_st,
                          const uint32_t* __restrict__ item_grp, const uint32_t* __restrict__ grp_off, int always,
                          uint32_t n, uint32_t key_base, RlcKey key, G1JEntry* __restrict__ pout,
-                         G2JEntry* __restrict__ sout, uint2* __restrict__ coef, const uint8_t* __restrict__ guard) {
+                         G2JEntry* __restrict__ sout, uint2* __restrict__ coef, const uint8_t* __restrict__ guard,
+                         KeyWideRef kw) {
 #if defined(__HIP_DEVICE_COMPILE__)
   if (guard && *guard == 0) return;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -503,7 +536,21 @@ __global__ KB_OCC(HB_OCC_RLC) void k_rlc(const G1AEntry* __restrict__ pk, const 
     } else {
       rlc_coeffs(key, key_base + i, a, b);
     }
-    if (sides & 1) rp = rlc_g1(P, a, b);
+    if (sides == 1) {
+      // a learned key's ladder through its table (16 steps in lazy limbs), any other as before
+      const uint32_t e = kw.ent ? kw.ent[i] : KEY_WIDE_NONE;
+      const bool wide = e != KEY_WIDE_NONE;
+      if (kw.ctr) {
+        const uint64_t act = __ballot(true), wm = __ballot(wide);
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)act) - 1)) {
+          if (wm) atomicAdd(&kw.ctr->wide_items, (unsigned long long)__popcll(wm));
+          if (act & ~wm) atomicAdd(&kw.ctr->narrow_items, (unsigned long long)__popcll(act & ~wm));
+        }
+      }
+      rp = wide ? g1l_mul_wide(kw.wide + (uint64_t)KEY_WIDE_PTS * e, a, b) : rlc_g1(P, a, b);
+    } else if (sides & 1) {
+      rp = rlc_g1(P, a, b);
+    }
     if (sides & 2) rs = rlc_g2(S, a, b);
   }
   if (sides & 1) pout[i] = {rp.X, rp.Y, rp.Z};
@@ -741,6 +788,32 @@ __device__ __forceinline__ void rlc_lad_g2(const RlcMsmArgs& a, uint32_t first, 
   for (uint32_t k = 1; k < cnt; k++) a.sout[first + k] = {zs.X, zs.Y, zs.Z};
 }
 
+// A chunk of a dense key-side launch whose items all have an entry number goes through the keys'
+// ladder tables; both phases evaluate this from the same array.
+__device__ __forceinline__ bool rlc_chunk_wide(const RlcMsmArgs& a, uint32_t first, uint32_t cnt) {
+  if (a.sparse || a.sides != 1 || !a.kw.ent) return false;
+  bool all = true;
+  for (uint32_t k = 0; k < cnt; k++) all = all && a.kw.ent[first + k] != KEY_WIDE_NONE;
+  return all;
+}
+// phase 1 of such a chunk: the coefficients only ((0, 0) for unusable items), no ladder records
+__device__ __forceinline__ void rlc_coef_only(const RlcMsmArgs& a, uint32_t first, uint32_t cnt) {
+  HB_NOUNROLL for (uint32_t k = 0; k < cnt; k++) {
+    const uint32_t i = first + k;
+    const bool usable = !a.pk_st[i] && !a.sig_st[i] && !a.pk[i].inf && !a.sig[i].inf;
+    uint32_t ca = 0, cb = 0;
+    if (usable) rlc_coeffs(a.key, a.key_base + i, ca, cb);
+    a.coef[i] = make_uint2(ca, cb);
+  }
+}
+// phase 2: as rlc_lad_g1, through the tables
+__device__ __forceinline__ void rlc_lad_g1_wide(const RlcMsmArgs& a, uint32_t first, uint32_t cnt) {
+  const G1J rp = g1l_msm_ladder_wide(a.kw.wide, a.kw.ent, a.coef, first, cnt);
+  a.pout[first] = {rp.X, rp.Y, rp.Z};
+  const G1J zi = jac_infinity<Fp>();
+  for (uint32_t k = 1; k < cnt; k++) a.pout[first + k] = {zi.X, zi.Y, zi.Z};
+}
+
 // One lane per chunk.  PHASE 1: coefficients and tables of SIDES; 2: the ladder of side SIDES (1
 // or 2).  SIDES as RlcMsmArgs::sides, a template argument so that the public-key-only launch of
 // the slot-wide check does not allocate registers for the G2 side.
@@ -753,8 +826,24 @@ __global__ KB_OCC(HB_OCC_RLC) void k_rlc_msm(RlcMsmArgs a) {
   const uint32_t first = a.cfirst[c], cc = a.ccount[c], cnt = cc & 0x7fffffffu;
   if (rlc_single<SIDES>(a, first, cc, PHASE != 2)) return;
   if (PHASE == 2) {
-    if (SIDES == 1) rlc_lad_g1(a, first, cnt);
-    else rlc_lad_g2(a, first, cnt);
+    if (SIDES == 1) {
+      const bool wide = rlc_chunk_wide(a, first, cnt);
+      if (a.kw.ctr) {
+        const uint64_t act = __ballot(true), wm = __ballot(wide);
+        if ((threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)act) - 1)) {
+          if (wm) atomicAdd(&a.kw.ctr->wide_chunks, (unsigned long long)__popcll(wm));
+          if (act & ~wm) atomicAdd(&a.kw.ctr->narrow_chunks, (unsigned long long)__popcll(act & ~wm));
+        }
+      }
+      if (wide) rlc_lad_g1_wide(a, first, cnt);
+      else rlc_lad_g1(a, first, cnt);
+    } else {
+      rlc_lad_g2(a, first, cnt);
+    }
+    return;
+  }
+  if (SIDES == 1 && rlc_chunk_wide(a, first, cnt)) {
+    rlc_coef_only(a, first, cnt);
     return;
   }
   if (SIDES & 1) rlc_tab_g1(a, first, cnt);
@@ -853,8 +942,10 @@ void launch_pk_cached(const uint8_t* pks, uint32_t n, const uint8_t* keys, const
                        out, st);
 }
 void launch_pk_lookup(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, uint64_t k0, uint64_t k1, G1AEntry* out,
-                      uint8_t* st, uint32_t* miss, uint32_t* mcount, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_pk_lookup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, n, k0, k1, out, st, miss, mcount);
+                      uint8_t* st, uint32_t* miss, uint32_t* mcount, uint32_t* went, hipStream_t s) {
+  if (n)
+    hipLaunchKernelGGL(k_pk_lookup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, n, k0, k1, out, st, miss, mcount,
+                       went);
 }
 // (the subgroup checks one lane per key whatever HBLS_DEC_PAIR_MAX says: the lane-pair layout is
 // for calls whose few keys are all the device has to do, and here most keys are hits)
@@ -865,8 +956,10 @@ void launch_pk_miss(const uint8_t* pks, uint32_t n, const uint32_t* miss, const 
   hipLaunchKernelGGL(k_pk_miss_subgroup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, miss, mcount, out, st);
 }
 void launch_pk_learn(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, const uint32_t* miss, const uint32_t* mcount,
-                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, hipStream_t s) {
-  if (n) hipLaunchKernelGGL(k_pk_learn, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, miss, mcount, k0, k1, pts, st);
+                     uint64_t k0, uint64_t k1, const G1AEntry* pts, const uint8_t* st, uint32_t* ment, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_pk_learn, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, miss, mcount, k0, k1, pts, st, ment);
+  if (t.wcap) hipLaunchKernelGGL(k_pk_wide, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, miss, mcount, ment, pts, st);
 }
 void launch_dec_sig_pt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip,
                        hipEvent_t decoded) {
@@ -899,17 +992,17 @@ void launch_sc_get(const uint8_t* sigs, uint32_t n, const void* key, const HmEnt
 void launch_rlc(const G1AEntry* pk, const uint8_t* pk_st, const HmEntry* sig, const uint8_t* sig_st,
                 const uint32_t* item_grp, const uint32_t* grp_off, int always, uint32_t n, uint32_t key_base,
                 const RlcKey& key, G1JEntry* pout, G2JEntry* sout, hipStream_t s, uint2* coef, int sides,
-                const uint8_t* guard) {
+                const uint8_t* guard, const KeyWideRef& kw) {
   if (!n) return;
   if (sides == 1)
     hipLaunchKernelGGL(k_rlc<1>, dim3(blocks_for(n)), dim3(BLOCK), 0, s, pk, pk_st, sig, sig_st, item_grp, grp_off,
-                       always, n, key_base, key, pout, sout, coef, guard);
+                       always, n, key_base, key, pout, sout, coef, guard, kw);
   else if (sides == 2)
     hipLaunchKernelGGL(k_rlc<2>, dim3(blocks_for(n)), dim3(BLOCK), 0, s, pk, pk_st, sig, sig_st, item_grp, grp_off,
-                       always, n, key_base, key, pout, sout, coef, guard);
+                       always, n, key_base, key, pout, sout, coef, guard, kw);
   else
     hipLaunchKernelGGL(k_rlc<3>, dim3(blocks_for(n)), dim3(BLOCK), 0, s, pk, pk_st, sig, sig_st, item_grp, grp_off,
-                       always, n, key_base, key, pout, sout, coef, guard);
+                       always, n, key_base, key, pout, sout, coef, guard, kw);
 }
 void launch_scatter(const ScatterArgs& a, hipStream_t s) {
   const size_t tot = (size_t)a.n + a.n_agg;

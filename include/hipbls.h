@@ -154,8 +154,9 @@ size_t hbls_pubkey_cache_size(void);
  * Nothing for the caller to manage: a node's pubshares and DV keys are fixed by its cluster lock
  * (cluster/lock.go), so from its second slot on every key is found.  Statuses and outputs are
  * byte-identical with or without it (a status is a function of the key's bytes alone).  The table
- * holds HBLS_KEY_LEARN entries (environment at init, or hbls_tune; default 2^21, about 0.33 GB per
- * device, allocated by the first call that uses it; 0 = off), is append-only and never evicts: a
+ * holds HBLS_KEY_LEARN entries (environment at init, or hbls_tune; default 2^21, about 3.3 GB per
+ * device with the ladder tables below, 0.33 GB without them, allocated by the first call that uses
+ * it; 0 = off), is append-only and never evicts: a
  * full table keeps what it has and further new keys are decompressed in every call.  Consecutive
  * calls are ordered on the device (a call's lookup runs after the previous call's inserts), so
  * slots enqueued back to back from a cold start decompress each key once.  Not used by calls that
@@ -164,8 +165,17 @@ size_t hbls_pubkey_cache_size(void);
  * hbls_key_learn_stats: for each device of the mask (at most max_devices; *n_devices receives the
  * number written) four values: out[4k] entries held, out[4k+1] capacity, out[4k+2] keys found and
  * out[4k+3] keys decompressed, both cumulative since init.  Waits for the library's enqueued work
- * on each device. */
+ * on each device.
+ * Ladder tables: the first HBLS_KEY_WIDE entries (environment at init, or hbls_tune; default: all of
+ * them; 0 = none) also keep 15 affine multiples of the key (1440 bytes), built once when a good,
+ * finite key is learned.  The random linear combination of a later call then takes 16 ladder steps
+ * per key instead of 32 and builds no per-slot tables; the coefficients, and so every status and
+ * output, are what they are without the tables.
+ * hbls_key_wide_stats: per device five cumulative values: out[5k] tables built, out[5k+1] /
+ * out[5k+2] chunks of the chunked combination's key side combined through tables / without,
+ * out[5k+3] / out[5k+4] per-item key-side ladders through tables / without.  Waits likewise. */
 int hbls_key_learn_stats(uint64_t* out, size_t max_devices, size_t* n_devices);
+int hbls_key_wide_stats(uint64_t* out, size_t max_devices, size_t* n_devices);
 /* Decompressed-signature cache (new, no herumi counterpart): hbls_verify_batch keeps the
  * decompressed, subgroup-checked points of the partials it verified (a ring of `entries` per
  * device, keyed by all 96 bytes), and hbls_threshold_aggregate_batch takes its members from it
@@ -339,7 +349,8 @@ size_t hbls_dec_pair_max(size_t items);
  * "HBLS_DEC_PAIR_MAX"; the chunking of large verifications "HBLS_GROUP_CHUNK" (groups per pairing
  * chunk), "HBLS_FALLBACK_CHUNK" (items per fallback pass), "HBLS_GROUP_MAX" (items per group of a
  * host call); "HBLS_KEY_LEARN" (entries of the learned key cache, 0 = off: a new value empties the
- * table after waiting for the library's enqueued work).  *previous (if not NULL) receives the old
+ * table after waiting for the library's enqueued work); "HBLS_KEY_WIDE" (how many of those entries
+ * get a ladder table, 0 = none: a new value empties the cache likewise).  *previous (if not NULL) receives the old
  * value.  Returns 0, or -1 for an unknown name. */
 int hbls_tune(const char* name, size_t value, size_t* previous);
 /* Tuning: the random linear combination's public-key side groups a verification group's items

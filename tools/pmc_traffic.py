@@ -11,7 +11,7 @@ LABELS = {  # bench.py / TIMED label -> kernel symbols of the slot
                      "k_h2c_clear2", "k_h2c_clear3", "k_h2c_clear1h", "k_h2c_clear2h"], "k_lines_msg": ["k_lines_msg"],
     "k_dec_pk": ["k_dec_pk", "k_g1_subgroup"],
     # the learned key cache of the device calls: the lookup, the misses' decompression, the inserts
-    "k_pk_lookup": ["k_pk_lookup"], "k_pk_miss": ["k_pk_miss_dec", "k_pk_miss_subgroup"], "k_pk_learn": ["k_pk_learn"],
+    "k_pk_lookup": ["k_pk_lookup"], "k_pk_miss": ["k_pk_miss_dec", "k_pk_miss_subgroup"], "k_pk_learn": ["k_pk_learn", "k_pk_wide"],
     "k_dec_sig_pt": ["k_dec_sig_pt", "k_g2_subgroup"], "k_ta_straus": ["k_ta_jtab", "k_ta_jladder", "k_ta_jgeneral", "k_ta_joint", "k_ta_straus"],
     "k_ta_small": ["k_ta_sprep", "k_ta_small", "k_ta_stab", "k_ta_sladder", "k_ta_sladder<false>", "k_ta_sladder<true>"], "k_mml_eval": ["k_mml_eval"],
     "k_pair3_mls": ["k_pair3<5>", "k_lml<0>", "k_lml<1>"],
