@@ -10,6 +10,7 @@
 #include "layout.h"
 #include "../../include/hipbls.h"
 #include "coalesce.h"
+#include "hgroup.h"
 #include "msgtable.h"
 #include "vplan.h"
 
@@ -294,8 +295,7 @@ std::atomic<size_t> g_slot_msm_min{32768};
 // exponentiation per slot.  Verdicts are the same either way.
 std::atomic<bool> g_adaptive{true};
 // HBLS_SINGLE_MAX / hbls_single_max: host Verify batches of fewer items check every item alone
-// (SINGLE_MAX_DEFAULT: the batched final exponentiation's threshold, g_fe_batch_min)
-constexpr size_t SINGLE_MAX_DEFAULT = ~size_t(0);
+// (hgroup.h SINGLE_MAX_DEFAULT: the batched final exponentiation's threshold, g_fe_batch_min)
 std::atomic<size_t> g_single_max{SINGLE_MAX_DEFAULT};
 
 struct DevBuf {
@@ -1760,21 +1760,32 @@ int hash_messages(Dev& d, const uint8_t* dmsg, const uint64_t* doff, const uint3
   return 0;
 }
 
-// Whether a verification defers its messages' Miller lines (verify_pipeline defer_msgs): messages
-// with about one group each (the chain per group is then no extra work) and the batched sizes.
-bool defer_lines(size_t n_groups, size_t n_msgs) {
-  const size_t fe_min = g_fe_batch_min.load();
-  return fe_min && n_groups >= fe_min && n_groups <= n_msgs;
-}
+// hgroup.h defer_lines at the run-time threshold of the batched final exponentiation
+bool defer_lines(size_t n_groups, size_t n_msgs) { return hb::defer_lines(n_groups, n_msgs, g_fe_batch_min.load()); }
 
 // ---------------------------------------------------------------------------------------
 // Host-buffer calls: staging, message dedup, multi-device sharding
 // ---------------------------------------------------------------------------------------
-// Upload the distinct messages (library stream) and hash them; with a workspace set, the hashing
-// runs on its side stream 2 (beside the decompression the verification forks next) and *ready is
-// the event the verification waits on before it needs H(m).
-int hash_table(Dev& d, const MsgTable& t, MsgEntry** hm_out, bool lines, Ws* w = nullptr,
-               hipEvent_t* ready = nullptr, Hc* h = nullptr, hipEvent_t* h_ready = nullptr) {
+// Hash messages first .. first + count - 1 of an uploaded table (dmsg, doff, dlen; entries in hm)
+// on w's side stream 2 -- beside the decompression the verification forks next -- behind what
+// stream `after` holds now (the table's upload, a chunk's gather; ev_ta is free until the
+// verification).  The verification waits on w.ev_h before it needs H(m) and on w.ev_side[2] before
+// it needs the messages' lines (computed here unless deferred).
+int hash_range(Dev& d, Ws& w, hipStream_t after, const uint8_t* dmsg, const uint64_t* doff, const uint32_t* dlen,
+               MsgEntry* hm, size_t first, size_t count, bool lines) {
+  HCHK(hipEventRecord(w.ev_ta, after));
+  hipStream_t hs = w.side[2];
+  HCHK(hipStreamWaitEvent(hs, w.ev_ta, 0));
+  TIMED(d, "k_hash_to_g2", hs, launch_hash_to_g2(dmsg, doff + first, dlen + first, (uint32_t)count, hm + first, hs));
+  HCHK(hipEventRecord(w.ev_h, hs));
+  if (lines) TIMED(d, "k_lines_msg", hs, launch_lines_msg(hm + first, (uint32_t)count, hs));
+  HCHK(hipEventRecord(w.ev_side[2], hs));
+  return 0;
+}
+
+// Upload the distinct messages (the call's stream) and hash them: there, or with a workspace on
+// its side stream 2 (hash_range).
+int hash_table(Dev& d, const MsgTable& t, MsgEntry** hm_out, bool lines, Hc* h = nullptr, Ws* w = nullptr) {
   uint8_t* dmsg;
   uint64_t* doff;
   uint32_t* dlen;
@@ -1783,50 +1794,38 @@ int hash_table(Dev& d, const MsgTable& t, MsgEntry** hm_out, bool lines, Ws* w =
   if (upload(d, I_OFF, t.off.data(), t.off.size(), &doff, h)) return -1;
   if (upload(d, I_LEN, t.len.data(), t.len.size(), &dlen, h)) return -1;
   if (ensure_buf(call_io(d, h)[I_HM], t.len.size() * sizeof(MsgEntry), &hm)) return -1;
-  hipStream_t hs = call_stream(d, h);
-  if (w) {
-    HCHK(hipEventRecord(w->ev_ta, hs));  // the uploads (ev_ta is free until the verification)
-    hs = w->side[2];
-    HCHK(hipStreamWaitEvent(hs, w->ev_ta, 0));
-  }
-  TIMED(d, "k_hash_to_g2", hs, launch_hash_to_g2(dmsg, doff, dlen, (uint32_t)t.len.size(), (MsgEntry*)hm, hs));
-  if (w && h_ready) {
-    HCHK(hipEventRecord(w->ev_h, hs));
-    *h_ready = w->ev_h;
-  }
-  if (lines) TIMED(d, "k_lines_msg", hs, launch_lines_msg((MsgEntry*)hm, (uint32_t)t.len.size(), hs));
-  if (w) {
-    HCHK(hipEventRecord(w->ev_side[2], hs));
-    *ready = w->ev_side[2];
-  }
   *hm_out = (MsgEntry*)hm;
-  return 0;
+  hipStream_t hs = call_stream(d, h);
+  if (w) return hash_range(d, *w, hs, dmsg, doff, dlen, *hm_out, 0, t.len.size(), lines);
+  return hash_messages(d, dmsg, doff, dlen, t.len.size(), *hm_out, hs, lines);
 }
 
-// Run fn(dev, shard) for each device's shard concurrently (one host thread per extra device).
-int for_each_device(size_t n_units, const std::function<int(Dev&, size_t, size_t)>& fn) {
+// The host-call contexts a call holds: one (waited for) and whatever idle ones it adds
+// (hc_try_acquire), all released when the call returns.
+struct HcLease {
+  Dev& d;
+  std::vector<Hc*> h;
+  explicit HcLease(Dev& dev) : d(dev), h{&hc_acquire(dev)} {}
+  HcLease(const HcLease&) = delete;
+  ~HcLease() {
+    for (size_t c = h.size(); c-- > 0;) hc_release(d, *h[c]);
+  }
+};
+
+// Run fn(dev, shard) for each device's shard of n_units concurrently (one host thread per extra
+// device); a failing shard's error is reported with its device.  fn locks the device itself.
+using ShardFn = std::function<int(Dev&, size_t, size_t)>;
+int fan_out(size_t n_units, const ShardFn& fn) {
   const std::vector<Dev*> ds = devs();
   const size_t nd = std::min(ds.size(), std::max<size_t>(n_units, 1));
-  if (nd <= 1) {
-    Dev& d = *ds[0];
-    std::lock_guard<std::mutex> lk(d.mu);
-    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-    return fn(d, 0, n_units);
-  }
+  if (nd <= 1) return fn(*ds[0], 0, n_units);
   std::vector<int> rc(nd, 0);
   std::vector<std::string> errs(nd);
   std::vector<std::thread> th;
   for (size_t k = 0; k < nd; k++) {
     const size_t b = n_units * k / nd, e = n_units * (k + 1) / nd;
     th.emplace_back([&, k, b, e]() {
-      Dev& d = *ds[k];
-      std::lock_guard<std::mutex> lk(d.mu);
-      if (hipSetDevice(d.ord) != hipSuccess) {
-        rc[k] = -1;
-        errs[k] = "hipSetDevice failed";
-        return;
-      }
-      rc[k] = fn(d, b, e);
+      rc[k] = fn(*ds[k], b, e);
       if (rc[k]) errs[k] = g_err;
     });
   }
@@ -1836,43 +1835,28 @@ int for_each_device(size_t n_units, const std::function<int(Dev&, size_t, size_t
   return 0;
 }
 
-// for_each_device for the heavy host-buffer calls: each device's share runs in a host-call context
+// fan_out with the device locked throughout (the small entry points)
+int for_each_device(size_t n_units, const ShardFn& fn) {
+  return fan_out(n_units, [&fn](Dev& d, size_t b, size_t e) -> int {
+    std::lock_guard<std::mutex> lk(d.mu);
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    return fn(d, b, e);
+  });
+}
+
+// fan_out for the heavy host-buffer calls: each device's share runs in a host-call context
 // (acquired before the device lock); fn may release the lock once everything is enqueued and then
 // wait for its own stream only
 using HcFn = std::function<int(Dev&, Hc&, size_t, size_t, std::unique_lock<std::mutex>&)>;
 int for_each_device_hc(size_t n_units, const HcFn& fn) {
-  auto run = [&fn](Dev& d, size_t b, size_t e) -> int {
-    Hc& h = hc_acquire(d);
-    struct Rel {
-      Dev& d;
-      Hc& h;
-      ~Rel() { hc_release(d, h); }
-    } rel{d, h};
+  return fan_out(n_units, [&fn](Dev& d, size_t b, size_t e) -> int {
+    HcLease hcs(d);
     std::unique_lock<std::mutex> lk(d.mu);
     if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-    return fn(d, h, b, e, lk);
-  };
-  const std::vector<Dev*> ds = devs();
-  const size_t nd = std::min(ds.size(), std::max<size_t>(n_units, 1));
-  if (nd <= 1) return run(*ds[0], 0, n_units);
-  std::vector<int> rc(nd, 0);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < nd; k++) {
-    const size_t b = n_units * k / nd, e = n_units * (k + 1) / nd;
-    th.emplace_back([&, k, b, e]() {
-      rc[k] = run(*ds[k], b, e);
-      if (rc[k]) errs[k] = g_err;
-    });
-  }
-  for (auto& t : th) t.join();
-  for (size_t k = 0; k < nd; k++)
-    if (rc[k]) return set_err("device " + std::to_string(ds[k]->ord) + ": " + errs[k]);
-  return 0;
+    return fn(d, *hcs.h[0], b, e, lk);
+  });
 }
 
-// Verify n host-buffer items (tbls.Verify per item): items are ordered by message and grouped
-// (at most g_gmax per group), the groups sharded over the devices, statuses scattered back.
 // Decompress m compressed keys into entries first .. first+m-1 of d's key table (grown, keeping
 // the entries before `first`).  Caller holds d.mu.
 int kc_fill(Dev& d, const uint8_t* keys, size_t first, size_t m) {
@@ -2071,6 +2055,44 @@ static double now_ms() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
+// One enqueued chunk of a host-buffer Verify -- a whole call, one device's shard of it, or one
+// chunk of a large call.  vc names the chunk's device buffers (keys and signatures in group order,
+// msg_idx, the group offsets, hm, the deferred range, status, first_out); its messages were hashed
+// by hash_range on workspace w.  Verifies it on stream s (w released behind it), then enters its
+// decompressed signatures into the signature cache (the aggregation of these partials reads them)
+// through the context `owner`, whose staging buffers hold vc.sigs.
+int verify_chunk(Dev& d, Ws& w, VerifyCall& vc, hipStream_t s, Hc& owner) {
+  vc.s = s;
+  vc.hm_ready = w.ev_side[2];
+  vc.h_ready = w.ev_h;
+  // the key cache is looked up on the device (k_pk_cached): its tables are only rewritten under
+  // Dev::mu, held while this call enqueues, after every launch that may still read them
+  vc.key_cache = true;
+  return verify_pipeline(d, w, vc) || sc_put_release(d, w, vc.sigs, vc.vsig, vc.vsigst, vc.n, s, owner) ? -1 : 0;
+}
+
+// The bracket of a chunk whose keys and signatures went up in the caller's order (pk, sig): its m
+// items `ord` gathered into group order on the device before the verification, their statuses
+// scattered back to the caller's positions after it.
+int gather_items(const uint8_t* pk, const uint8_t* sig, const uint32_t* ord, size_t m, uint8_t* gpk, uint8_t* gsig,
+                 hipStream_t s) {
+  LAUNCH(k_gather_items, m, s, (const uint4*)pk, (const uint4*)sig, ord, (uint32_t)m, (uint4*)gpk, (uint4*)gsig);
+  return 0;
+}
+int scatter_status(const uint8_t* st, const uint32_t* ord, size_t m, uint8_t* st_out, hipStream_t s) {
+  LAUNCH(k_scatter_status, m, s, st, ord, (uint32_t)m, st_out);
+  return 0;
+}
+
+// the distinct messages of a host call: the parallel dedup for large calls on hosts with the threads
+void dedup_call(const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n, MsgTable& all) {
+  const unsigned hw = std::thread::hardware_concurrency();
+  if (n >= (1u << 16) && hw >= 4)
+    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
+  else
+    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
+}
+
 // A large one-device Verify batch.  Its keys and signatures go up in the caller's order while the
 // host groups them (message dedup and sort, ~7-12 ms for a slot's million partials: beside the
 // PCIe upload instead of in front of it); then the groups run in chunks of whole groups, each on
@@ -2085,12 +2107,8 @@ constexpr size_t CHUNK_MIN_ITEMS = size_t(1) << 18;
 int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
                  const uint32_t* msg_len, size_t n, uint8_t* status) {
   const double t_start = now_ms();
-  Hc& h0 = hc_acquire(d);
-  struct Rel0 {
-    Dev& d;
-    Hc& h;
-    ~Rel0() { hc_release(d, h); }
-  } rel0{d, h0};
+  HcLease hcs(d);
+  Hc& h0 = *hcs.h[0];
   std::unique_lock<std::mutex> lk(d.mu);
   if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
   const double t_locked0 = now_ms();
@@ -2099,57 +2117,18 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
   if (upload(d, I_PK, pks, 48 * n, &rpk, &h0) || upload(d, I_SIG, sigs, 96 * n, &rsig, &h0)) return -1;
   lk.unlock();
   const double t_up = now_ms();
-  // 2. the grouping on the host, beside the upload: message ids, items ordered by message (a
-  // counting sort), groups of <= g_gmax items over one message
+  // 2. the grouping on the host, beside the upload (hgroup.h): message ids, items ordered by
+  // message, groups of <= HBLS_GROUP_MAX items over one message
   MsgTable all;
-  const unsigned hw = std::thread::hardware_concurrency();
-  if (hw >= 4)
-    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
-  else
-    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
+  dedup_call(msgs, msg_off, msg_len, n, all);
   const size_t nm = all.len.size();
-  std::vector<uint32_t> order32(n), mstart(nm + 1, 0);
-  for (size_t k = 0; k < n; k++) mstart[all.idx[k] + 1]++;
-  for (size_t j = 0; j < nm; j++) mstart[j + 1] += mstart[j];
-  for (size_t k = 0; k < n; k++) order32[mstart[all.idx[k]]++] = (uint32_t)k;
-  std::vector<size_t> gstart;
-  std::vector<uint32_t> midx(n);
-  for (size_t k = 0; k < n; k++) {
-    midx[k] = all.idx[order32[k]];
-    if (k == 0 || midx[k] != midx[k - 1] || k - gstart.back() >= g_gmax.load()) gstart.push_back(k);
-  }
-  const size_t n_groups = gstart.size();
-  gstart.push_back(n);
-  const bool defer = defer_lines(n_groups, nm);
+  const MsgGroups g = group_by_message(all.idx.data(), n, nm, std::max<size_t>(1, g_gmax.load()));
+  const bool defer = defer_lines(g.n_groups(), nm);
   // chunks (one per idle context, messages of one group each) at group starts, ~n / K items each
-  std::vector<Hc*> hcs{&h0};
   const size_t k_want = defer ? std::min<size_t>((size_t)g_ws_sets, std::max<size_t>(1, n / CHUNK_MIN_ITEMS)) : 1;
-  while (hcs.size() < k_want) {
-    Hc* x = hc_try_acquire(d);
-    if (!x) break;
-    hcs.push_back(x);
-  }
-  struct RelExtra {
-    Dev& d;
-    std::vector<Hc*>& h;
-    ~RelExtra() {
-      for (size_t c = 1; c < h.size(); c++) hc_release(d, *h[c]);
-    }
-  } rel{d, hcs};
-  const size_t K = hcs.size();
-  std::vector<size_t> cg{0};
-  for (size_t c = 1; c < K; c++) {
-    const size_t g = (size_t)(std::lower_bound(gstart.begin(), gstart.begin() + n_groups, n * c / K) - gstart.begin());
-    if (g > cg.back() && g < n_groups) cg.push_back(g);
-  }
-  cg.push_back(n_groups);
-  // the chunks' group offsets, concatenated (chunk c's at goff_base[c])
-  std::vector<uint32_t> goffs;
-  std::vector<size_t> goff_base;
-  for (size_t c = 0; c + 1 < cg.size(); c++) {
-    goff_base.push_back(goffs.size());
-    for (size_t g = cg[c]; g <= cg[c + 1]; g++) goffs.push_back((uint32_t)(gstart[g] - gstart[cg[c]]));
-  }
+  for (Hc* x; hcs.h.size() < k_want && (x = hc_try_acquire(d));) hcs.h.push_back(x);
+  const size_t K = hcs.h.size();
+  const ChunkSplit cs = split_chunks(g.gstart.data(), g.n_groups(), K);
   const double t_grouped = now_ms();
   lk.lock();
   const double t_locked = now_ms();
@@ -2159,12 +2138,12 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
   uint64_t* doff;
   void *hmp, *stp, *gp;
   PinnedUploads up;
-  up.add(I_IDX, order32.data(), n, &dord);
-  up.add(I_MIDX, midx.data(), n, &dmidx);
+  up.add(I_IDX, g.order.data(), n, &dord);
+  up.add(I_MIDX, g.midx.data(), n, &dmidx);
   up.add(I_MSG, all.bytes.data(), all.bytes.size(), &dmsg);
   up.add(I_OFF, all.off.data(), all.off.size(), &doff);
   up.add(I_LEN, all.len.data(), all.len.size(), &dlen);
-  up.add(I_VGOFF, goffs.data(), goffs.size(), &dgoffs);
+  up.add(I_VGOFF, cs.goffs.data(), cs.goffs.size(), &dgoffs);
   if (upload_pinned(d, h0, up) || ensure_buf(h0.io[I_HM], nm * sizeof(MsgEntry), &hmp) ||
       ensure_buf(h0.io[I_HM2], n, &stp) || ensure_buf(h0.io[I_OUT], 144 * n, &gp))
     return -1;
@@ -2172,50 +2151,35 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
   uint8_t* dst_out = (uint8_t*)stp;
   uint8_t *gpk = (uint8_t*)gp, *gsig = gpk + 48 * n;  // group order
   HCHK(hipEventRecord(h0.ev, h0.s));
-  for (size_t c = 0; c + 1 < cg.size(); c++) {
-    Hc& hc = *hcs[c];
+  for (size_t c = 0; c < cs.n_chunks(); c++) {
+    Hc& hc = *hcs.h[c];
     hipStream_t sc = hc.s;
     if (c) HCHK(hipStreamWaitEvent(sc, h0.ev, 0));
-    const size_t ib = gstart[cg[c]], m = gstart[cg[c + 1]] - ib, ng = cg[c + 1] - cg[c];
+    const size_t ib = g.gstart[cs.cg[c]], m = g.gstart[cs.cg[c + 1]] - ib;
     // the chunk's messages: all of them for one chunk, else its contiguous range
-    const size_t mfirst = K == 1 ? 0 : midx[ib], mcount = K == 1 ? nm : midx[ib + m - 1] + 1 - midx[ib];
+    const size_t mfirst = K == 1 ? 0 : g.midx[ib], mcount = K == 1 ? nm : g.midx[ib + m - 1] + 1 - g.midx[ib];
+    VerifyCall vc;
+    vc.n = m;
+    vc.n_groups = cs.cg[c + 1] - cs.cg[c];
     // deferred lines per chunk: verify_pipeline decides its batched final exponentiation from the
     // chunk's own group count, so a chunk below that size computes its lines here
-    const bool cdefer = defer && defer_lines(ng, mcount);
+    const bool cdefer = defer && defer_lines(vc.n_groups, mcount);
     Ws& w = ws_acquire(d, sc);
     void* sio;
     if (ensure_buf(hc.io[I_STAT], m, &sio)) return -1;
-    uint8_t* dst = (uint8_t*)sio;
     uint8_t *cpk = gpk + 48 * ib, *csig = gsig + 96 * ib;
-    LAUNCH(k_gather_items, m, sc, (const uint4*)rpk, (const uint4*)rsig, dord + ib, (uint32_t)m, (uint4*)cpk,
-           (uint4*)csig);
-    HCHK(hipEventRecord(w.ev_ta, sc));
-    hipStream_t hs = w.side[2];
-    HCHK(hipStreamWaitEvent(hs, w.ev_ta, 0));
-    TIMED(d, "k_hash_to_g2", hs, launch_hash_to_g2(dmsg, doff + mfirst, dlen + mfirst, (uint32_t)mcount, hm + mfirst, hs));
-    HCHK(hipEventRecord(w.ev_h, hs));
-    if (!cdefer) TIMED(d, "k_lines_msg", hs, launch_lines_msg(hm + mfirst, (uint32_t)mcount, hs));
-    HCHK(hipEventRecord(w.ev_side[2], hs));
-    // the key cache is looked up on the device (k_pk_cached): its tables are only rewritten under
-    // Dev::mu, held while this call enqueues, after every launch that may still read them
-    VerifyCall vc;
+    if (gather_items(rpk, rsig, dord + ib, m, cpk, csig, sc) ||
+        hash_range(d, w, sc, dmsg, doff, dlen, hm, mfirst, mcount, !cdefer))
+      return -1;
     vc.pks = cpk;
     vc.sigs = csig;
     vc.msg_idx = dmidx + ib;
+    vc.grp_off = dgoffs + cs.goff_base[c];
     vc.hm = hm;
-    vc.n = m;
-    vc.grp_off = dgoffs + goff_base[c];
-    vc.n_groups = ng;
-    vc.status = dst;
-    vc.s = sc;
-    vc.hm_ready = w.ev_side[2];
-    vc.h_ready = w.ev_h;
-    vc.key_cache = true;
     vc.defer_hm = hm + mfirst;
     vc.defer_msgs = cdefer ? mcount : 0;
-    // then the decompressed partials into the signature cache (the aggregation of these partials reads them)
-    if (verify_pipeline(d, w, vc) || sc_put_release(d, w, csig, vc.vsig, vc.vsigst, m, sc, h0)) return -1;
-    LAUNCH(k_scatter_status, m, sc, dst, dord + ib, (uint32_t)m, dst_out);
+    vc.status = (uint8_t*)sio;
+    if (verify_chunk(d, w, vc, sc, h0) || scatter_status(vc.status, dord + ib, m, dst_out, sc)) return -1;
     if (c) {
       HCHK(hipEventRecord(hc.ev, sc));
       HCHK(hipStreamWaitEvent(h0.s, hc.ev, 0));
@@ -2227,20 +2191,14 @@ int verify_large(Dev& d, const uint8_t* pks, const uint8_t* sigs, const uint8_t*
   HCHK(hipStreamSynchronize(h0.s));
   if (host_timing())
     fprintf(stderr, "hbls verify_large n=%zu chunks=%zu: lock %.2f ms, upload enqueue %.2f, grouping %.2f (beside the "
-            "upload), lock wait %.2f, enqueue %.2f, device %.2f\n", n, cg.size() - 1, t_locked0 - t_start,
+            "upload), lock wait %.2f, enqueue %.2f, device %.2f\n", n, cs.n_chunks(), t_locked0 - t_start,
             t_up - t_locked0, t_grouped - t_up, t_locked - t_grouped, t_enq - t_locked, now_ms() - t_enq);
   return 0;
 }
 
-// the distinct messages of a host call: the parallel dedup for large calls on hosts with the threads
-void dedup_call(const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n, MsgTable& all) {
-  const unsigned hw = std::thread::hardware_concurrency();
-  if (n >= (1u << 16) && hw >= 4)
-    dedup_messages_par(msgs, msg_off, msg_len, n, all, hw >= 8 ? 8u : 4u);
-  else
-    dedup_messages(msgs, msg_off, msg_len, n, nullptr, all);
-}
-
+// Verify n host-buffer items (tbls.Verify per item): items are ordered by message and grouped
+// (at most HBLS_GROUP_MAX per group, hgroup.h), the groups sharded over the devices, statuses
+// scattered back.
 int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
                 const uint32_t* msg_len, size_t n, uint8_t* status) {
   if (n == 0) return 0;
@@ -2251,114 +2209,82 @@ int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, co
       return verify_large(*ds[0], pks, sigs, msgs, msg_off, msg_len, n, status);
   }
   const double t_start = now_ms();
-  // global message ids, order items by (message, position), groups of <= g_gmax
   MsgTable all;
   dedup_call(msgs, msg_off, msg_len, n, all);
-  // items ordered by message id, stable (a counting sort: one pass, no comparisons)
-  std::vector<size_t> order(n), mstart(all.len.size() + 1, 0);
-  for (size_t k = 0; k < n; k++) mstart[all.idx[k] + 1]++;
-  for (size_t j = 0; j < all.len.size(); j++) mstart[j + 1] += mstart[j];
-  for (size_t k = 0; k < n; k++) order[mstart[all.idx[k]]++] = k;
   // a call below the batched final exponentiation's size (the latency-bound small calls, e.g. the
   // coalesced single-item callers) checks every item alone: a group of several items needs random
   // coefficients, i.e. a 64-bit scalar ladder per item on the call's critical path (~3.7 ms for a
   // lone lane), where separate checks only add lanes to kernels that have them to spare
   // (HBLS_SINGLE_MAX at init, hbls_single_max at run time: items below which every item is its own
   // group; default the batched final exponentiation's group threshold)
-  const size_t sm = g_single_max.load();
-  const size_t single_max = sm == SINGLE_MAX_DEFAULT ? g_fe_batch_min.load() : sm;
-  const size_t gmax = n < single_max ? 1 : std::max<size_t>(1, g_gmax.load());
-  std::vector<size_t> gstart;  // group starts in `order`
-  for (size_t k = 0; k < n; k++)
-    if (k == 0 || all.idx[order[k]] != all.idx[order[k - 1]] || k - gstart.back() >= gmax) gstart.push_back(k);
-  const size_t n_groups = gstart.size();
-  gstart.push_back(n);
-  if (n >= 0xffffffffull) return set_err("verify batch: too many items");
-  std::vector<uint32_t> order32(order.begin(), order.end());
+  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
+  const MsgGroups g = group_by_message(all.idx.data(), n, all.len.size(), gmax);
   const double t_grouped = now_ms();
-  return for_each_device_hc(n_groups, [&](Dev& d, Hc& h, size_t gb, size_t ge, std::unique_lock<std::mutex>& lk) -> int {
-    const size_t ib = gstart[gb], ie = gstart[ge], m = ie - ib;
+  return for_each_device_hc(g.n_groups(), [&](Dev& d, Hc& h, size_t gb, size_t ge, std::unique_lock<std::mutex>& lk) -> int {
+    const size_t ib = g.gstart[gb], ie = g.gstart[ge], m = ie - ib;
     if (m == 0) return 0;
-    const bool whole = gb == 0 && ge == n_groups;
-    // host preparation without the device lock (other callers enqueue meanwhile): the shard's
-    // distinct messages and each item's message index in group order -- the whole call's table
-    // when one device takes every group
+    const bool whole = gb == 0 && ge == g.n_groups();
+    const uint32_t* ord = g.order.data() + ib;  // the shard's items
+    // host preparation without the device lock (other callers enqueue meanwhile).  One device
+    // taking every group uses the whole call's table; several devices each dedup their shard's
+    // messages and upload only its keys and signatures, in group order
     lk.unlock();
     MsgTable tl;
-    std::vector<uint32_t> midx;
-    if (whole) {
-      midx.resize(m);
-      for (size_t k = 0; k < m; k++) midx[k] = all.idx[order[k]];
-    } else {
-      dedup_messages(msgs, msg_off, msg_len, m, order.data() + ib, tl);
-    }
-    const MsgTable& t = whole ? all : tl;
-    const std::vector<uint32_t>& tidx = whole ? midx : tl.idx;
-    std::vector<uint8_t> hpk, hsig;  // several devices: each uploads only its shard, in group order
+    std::vector<uint8_t> hpk, hsig;
     if (!whole) {
+      const std::vector<size_t> items(ord, ord + m);
+      dedup_messages(msgs, msg_off, msg_len, m, items.data(), tl);
       hpk.resize(48 * m);
       hsig.resize(96 * m);
       for (size_t k = 0; k < m; k++) {
-        memcpy(&hpk[48 * k], pks + 48 * order[ib + k], 48);
-        memcpy(&hsig[96 * k], sigs + 96 * order[ib + k], 96);
+        memcpy(&hpk[48 * k], pks + 48 * items[k], 48);
+        memcpy(&hsig[96 * k], sigs + 96 * items[k], 96);
       }
     }
-    std::vector<uint32_t> goff(ge - gb + 1);
-    for (size_t g = gb; g <= ge; g++) goff[g - gb] = (uint32_t)(gstart[g] - ib);
+    const MsgTable& t = whole ? all : tl;
+    const uint32_t* tidx = whole ? g.midx.data() : tl.idx.data();
+    std::vector<uint32_t> goff;
+    rebase_offsets(g.gstart.data(), gb, ge, goff);
     const double t_prep = now_ms();
     lk.lock();
     const double t_locked = now_ms();
     // the messages hash on a side stream while the keys and signatures decompress (latency of
     // one call: the two chains run side by side)
     Ws& w = ws_acquire(d, h.s);
-    MsgEntry* hm;
-    hipEvent_t hm_ready = nullptr, h_ready = nullptr;
-    const bool defer = defer_lines(ge - gb, t.len.size());
-    if (hash_table(d, t, &hm, !defer, &w, &hm_ready, &h, &h_ready)) return -1;
-    uint8_t *dpk, *dsig, *dst, *dst_out = nullptr;
-    uint32_t *didx, *dgoff, *dord = nullptr;
+    VerifyCall vc;
+    vc.n = m;
+    vc.n_groups = ge - gb;
+    const bool defer = defer_lines(vc.n_groups, t.len.size());
+    if (hash_table(d, t, &vc.defer_hm, !defer, &h, &w)) return -1;
+    vc.hm = vc.defer_hm;
+    vc.defer_msgs = defer ? t.len.size() : 0;
+    uint8_t *dpk, *dsig, *dst_out = nullptr;
+    uint32_t* dord = nullptr;
+    void* pst;
     if (whole) {  // caller order up, group order on the device
       uint8_t *rpk, *rsig;
-      void *p1, *p2, *p3;
+      void *p1, *p2;
       if (upload(d, I_PK, pks, 48 * m, &rpk, &h) || upload(d, I_SIG, sigs, 96 * m, &rsig, &h) ||
-          upload(d, I_IDX, order32.data(), m, &dord, &h) || ensure_buf(h.io[I_OUT], 144 * m, &p1) ||
-          ensure_buf(h.io[I_HM2], m, &p2) || ensure_buf(h.io[I_STAT], m, &p3))
+          upload(d, I_IDX, ord, m, &dord, &h) || ensure_buf(h.io[I_OUT], 144 * m, &p1) ||
+          ensure_buf(h.io[I_HM2], m, &p2) || ensure_buf(h.io[I_STAT], m, &pst))
         return -1;
       dpk = (uint8_t*)p1;
       dsig = dpk + 48 * m;
       dst_out = (uint8_t*)p2;
-      dst = (uint8_t*)p3;
-      LAUNCH(k_gather_items, m, h.s, (const uint4*)rpk, (const uint4*)rsig, dord, (uint32_t)m, (uint4*)dpk,
-             (uint4*)dsig);
-    } else {
-      void* p;
-      if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h) ||
-          ensure_buf(h.io[I_STAT], m, &p))
-        return -1;
-      dst = (uint8_t*)p;
-    }
-    if (upload(d, I_MIDX, tidx.data(), m, &didx, &h) || upload(d, I_VGOFF, goff.data(), goff.size(), &dgoff, &h))
+      if (gather_items(rpk, rsig, dord, m, dpk, dsig, h.s)) return -1;
+    } else if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h) ||
+               ensure_buf(h.io[I_STAT], m, &pst)) {
       return -1;
-    // the key cache is looked up on the device (k_pk_cached): its tables are only rewritten under
-    // Dev::mu, held while this call enqueues, after every launch that may still read them
-    VerifyCall vc;
+    }
+    uint32_t *didx, *dgoff;
+    if (upload(d, I_MIDX, tidx, m, &didx, &h) || upload(d, I_VGOFF, goff.data(), goff.size(), &dgoff, &h)) return -1;
     vc.pks = dpk;
     vc.sigs = dsig;
     vc.msg_idx = didx;
-    vc.hm = hm;
-    vc.n = m;
     vc.grp_off = dgoff;
-    vc.n_groups = ge - gb;
-    vc.status = dst;
-    vc.s = h.s;
-    vc.hm_ready = hm_ready;
-    vc.h_ready = h_ready;
-    vc.key_cache = true;
-    vc.defer_hm = hm;
-    vc.defer_msgs = defer ? t.len.size() : 0;
-    // then the decompressed partials into the signature cache (the aggregation of these partials reads them)
-    if (verify_pipeline(d, w, vc) || sc_put_release(d, w, dsig, vc.vsig, vc.vsigst, m, h.s, h)) return -1;
-    if (whole) LAUNCH(k_scatter_status, m, h.s, dst, dord, (uint32_t)m, dst_out);
+    vc.status = (uint8_t*)pst;
+    if (verify_chunk(d, w, vc, h.s, h)) return -1;
+    if (whole && scatter_status(vc.status, dord, m, dst_out, h.s)) return -1;
     lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
     const double t_enq = now_ms();
     if (whole) {
@@ -2370,9 +2296,9 @@ int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, co
       return 0;
     }
     std::vector<uint8_t> hst(m);
-    HCHK(hipMemcpyAsync(hst.data(), dst, m, hipMemcpyDeviceToHost, h.s));
+    HCHK(hipMemcpyAsync(hst.data(), vc.status, m, hipMemcpyDeviceToHost, h.s));
     HCHK(hipStreamSynchronize(h.s));
-    for (size_t k = 0; k < m; k++) status[order[ib + k]] = hst[k];
+    for (size_t k = 0; k < m; k++) status[ord[k]] = hst[k];
     return 0;
   });
 }
@@ -2382,10 +2308,11 @@ int verify_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, co
 // bad partial (core/parsigex/parsigex.go:93-98), sigagg returns on the first failure
 // (core/sigagg/sigagg.go:56-63), validatorapi on the first bad submission
 // (core/validatorapi/validatorapi.go:302-306).  Groups are runs of consecutive items over one
-// message in the caller's order (at most g_gmax items), so batches and groups are in item order
-// and verify_pipeline's first-error mode resolves only the first failing batch's groups and the
-// first failing group's items: under attack O(groups / batch + batch + group) checks instead of
-// one per item of every failing group.  One device (the order must not be split).
+// message in the caller's order (at most HBLS_GROUP_MAX items; hgroup.h split_runs), so batches
+// and groups are in item order and verify_pipeline's first-error mode resolves only the first
+// failing batch's groups and the first failing group's items: under attack O(groups / batch +
+// batch + group) checks instead of one per item of every failing group.  One device (the order
+// must not be split).
 int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
                       const uint32_t* msg_len, size_t n, int64_t* first, uint8_t* first_status, uint8_t* status) {
   *first = -1;
@@ -2395,25 +2322,20 @@ int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* ms
   MsgTable all;
   dedup_call(msgs, msg_off, msg_len, n, all);
   std::vector<uint32_t> goff;
-  for (size_t k = 0; k < n; k++)
-    if (k == 0 || all.idx[k] != all.idx[k - 1] || k - goff.back() >= std::max<size_t>(1, g_gmax.load()))
-      goff.push_back((uint32_t)k);
-  const size_t n_groups = goff.size();
-  goff.push_back((uint32_t)n);
+  split_runs(all.idx.data(), n, std::max<size_t>(1, g_gmax.load()), goff);
   Dev& d = *devs()[0];
-  Hc& h = hc_acquire(d);
-  struct Rel {
-    Dev& d;
-    Hc& h;
-    ~Rel() { hc_release(d, h); }
-  } rel{d, h};
+  HcLease hcs(d);
+  Hc& h = *hcs.h[0];
   std::unique_lock<std::mutex> lk(d.mu);
   if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
   Ws& w = ws_acquire(d, h.s);
-  MsgEntry* hm;
-  hipEvent_t hm_ready = nullptr, h_ready = nullptr;
-  const bool defer = defer_lines(n_groups, all.len.size());
-  if (hash_table(d, all, &hm, !defer, &w, &hm_ready, &h, &h_ready)) return -1;
+  VerifyCall vc;
+  vc.n = n;
+  vc.n_groups = goff.size() - 1;
+  const bool defer = defer_lines(vc.n_groups, all.len.size());
+  if (hash_table(d, all, &vc.defer_hm, !defer, &h, &w)) return -1;
+  vc.hm = vc.defer_hm;
+  vc.defer_msgs = defer ? all.len.size() : 0;
   uint8_t *dpk, *dsig;
   uint32_t *didx, *dgoff;
   void *pst, *pfirst;
@@ -2421,26 +2343,13 @@ int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* ms
       upload(d, I_MIDX, all.idx.data(), n, &didx, &h) || upload(d, I_VGOFF, goff.data(), goff.size(), &dgoff, &h) ||
       ensure_buf(h.io[I_STAT], n, &pst) || ensure_buf(h.io[I_HM2], sizeof(uint32_t), &pfirst))
     return -1;
-  uint8_t* dst = (uint8_t*)pst;
-  uint32_t* dfirst = (uint32_t*)pfirst;
-  VerifyCall vc;
   vc.pks = dpk;
   vc.sigs = dsig;
   vc.msg_idx = didx;
-  vc.hm = hm;
-  vc.n = n;
   vc.grp_off = dgoff;
-  vc.n_groups = n_groups;
-  vc.status = dst;
-  vc.s = h.s;
-  vc.hm_ready = hm_ready;
-  vc.h_ready = h_ready;
-  vc.key_cache = true;
-  vc.defer_hm = hm;
-  vc.defer_msgs = defer ? all.len.size() : 0;
-  vc.first_out = dfirst;
-  // then the decoded signatures enter the signature cache as after hbls_verify_batch
-  if (verify_pipeline(d, w, vc) || sc_put_release(d, w, dsig, vc.vsig, vc.vsigst, n, h.s, h)) return -1;
+  vc.status = (uint8_t*)pst;
+  vc.first_out = (uint32_t*)pfirst;
+  if (verify_chunk(d, w, vc, h.s, h)) return -1;
   lk.unlock();
   uint32_t f = 0;
   std::vector<uint8_t> own;
@@ -2449,8 +2358,8 @@ int verify_first_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* ms
     own.resize(n);
     hst = own.data();
   }
-  HCHK(hipMemcpyAsync(&f, dfirst, sizeof(f), hipMemcpyDeviceToHost, h.s));
-  HCHK(hipMemcpyAsync(hst, dst, n, hipMemcpyDeviceToHost, h.s));
+  HCHK(hipMemcpyAsync(&f, vc.first_out, sizeof(f), hipMemcpyDeviceToHost, h.s));
+  HCHK(hipMemcpyAsync(hst, vc.status, n, hipMemcpyDeviceToHost, h.s));
   HCHK(hipStreamSynchronize(h.s));
   if (f != 0xffffffffu) {
     if (f >= n) return set_err("verify first error: index out of range");
@@ -2476,8 +2385,8 @@ int group_op_host(const uint8_t* sigs, const int64_t* idx, const uint32_t* grp_o
     const size_t ng = ge - gb, pb = grp_off[gb], np = grp_off[ge] - pb;
     if (ng == 0) return 0;
     const double t_locked = now_ms();
-    std::vector<uint32_t> goff(ng + 1);
-    for (size_t g = 0; g <= ng; g++) goff[g] = grp_off[gb + g] - (uint32_t)pb;
+    std::vector<uint32_t> goff;
+    rebase_offsets(grp_off, gb, ge, goff);
     uint8_t* dsig;
     int64_t* didx = nullptr;
     uint32_t* dgoff;
@@ -2784,7 +2693,7 @@ int hbls_verify_aggregate_batch(const uint8_t* pks, const uint32_t* grp_off, con
     if (ensure_buf(h.io[I_HM], ng * sizeof(MsgEntry), &hmp)) return -1;
     MsgEntry* hm = (MsgEntry*)hmp;
     if (va_pipeline(d, w, dpk, np, goff.data(), ng, dsig, hm, dst, h.s,
-                    [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, nullptr, nullptr, &h); }))
+                    [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, &h); }))
       return -1;
     if (ws_release(w, h.s)) return -1;
     lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream

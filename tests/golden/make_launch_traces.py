@@ -1,7 +1,9 @@
 """Generate tests/golden/launch_traces.json: the kernel names a verification enqueues, in order, for
 every path verify_pipeline (charon_amd/csrc/hipbls.hip) can take -- the three group checks, both
 combinations, several chunks of groups, the adaptive skip, the first-error mode, the variants of
-hbls_slot_device and the host path.  hbls_timing(1) / hbls_timing_read give the names of a call
+hbls_slot_device and the host paths (the whole-call form, the per-device shards under
+hbls_debug_split, the first-error form and, with --large, the chunks of a 2^19-item call).
+hbls_timing(1) / hbls_timing_read give the names of a call
 in enqueue order; the sequence depends on the shapes and the knob settings only (data decides
 nothing on the host: the device guards do), the adaptive history excepted, which its case drives
 itself.
@@ -11,7 +13,10 @@ library of the commit BEFORE such a change (HBLS_LIBRARY names it, run from that
 never from the code under test; tests/test_gpu_launch_trace.py runs the same cases (CASES below)
 against the tree's library.  Needs the GPU.
 
-    python tests/golden/make_launch_traces.py [--out FILE]
+    python tests/golden/make_launch_traces.py [--out FILE] [--large]
+
+--large also records LARGE_TRACES (a 530 000-item call: a minute of signing first); without it the
+file's recorded ones are kept.
 
 Every case runs on device 0, makes one warm-up call and records the second (the first call
 allocates the learned-key table and grows buffers), and restores each knob it touches.
@@ -227,11 +232,33 @@ def _adaptive(cx):
                 "adaptive_3_skipped_clean": cx.record_next(clean)}
 
 
+def host_first_error_call(cx):
+    """hbls_verify_batch_first_error over the same cluster: 130 runs of 3 items in the caller's order."""
+    L, d = cx.L, cx.distinct
+    st = np.full(d["NP"], 255, dtype=np.uint8)
+    first, fst = ctypes.c_int64(0), ctypes.c_uint8(255)
+
+    def call():
+        chk(L, L.hbls_verify_batch_first_error(_p(d["pks"]), _p(d["sigs"]), _p(d["item_msgs"]), _p(d["item_off"]),
+                                               _p(d["item_len"]), d["NP"], ctypes.byref(first), ctypes.byref(fst),
+                                               _p(st)))
+        assert first.value == -1 and fst.value == 0 and not st.any()
+    return call
+
+
 def _host(cx):
     L, d = cx.L, cx.distinct
     with knobs(L, fe_batch=128, slot_msm=0):
         chk(L, L.hbls_pubkey_cache_clear())
-        out = {"host_no_key_cache": cx.record(host_call(cx))}
+        out = {"host_no_key_cache": cx.record(host_call(cx)),
+               "host_first_error": cx.record(host_first_error_call(cx))}
+        # the per-device shards: two contexts of device 0, 65 groups each, every context's launches
+        # in its own enqueue order (hbls_timing_read lists context after context)
+        chk(L, L.hbls_debug_split(2))
+        try:
+            out["host_split2"] = cx.record(host_call(cx))
+        finally:
+            chk(L, L.hbls_debug_split(1))
         chk(L, L.hbls_pubkey_cache_add(_p(d["pks"]), d["NP"]))
         try:
             out["host_key_cache"] = cx.record(host_call(cx))
@@ -264,6 +291,32 @@ CASES = {
 }
 
 
+LARGE_TRACES = {"verify_large_deferred": None, "verify_large_chunk_lines": 40_000}  # name -> hbls_fe_batch
+
+
+def large_traces(L, d):
+    """The launches of hbls_verify_batch over d, bench.setup_inputs' 53 000 x 10 cluster with one
+    message per validator (tests/test_gpu_robustness.py `large`): 2^19 items and more, so verify_large
+    runs it as two chunks on two host-call contexts of device 0, in chunk order.  With the default
+    knobs every chunk defers its messages' lines (no k_lines_msg); with hbls_fe_batch(40 000) the
+    call defers and each chunk of ~26 500 groups does not, so computes them."""
+    cx = Ctx.__new__(Ctx)
+    cx.L, cx.dev = L, torch.device("cuda", 0)
+    cx.stream = torch.cuda.Stream(device=cx.dev)
+    st = np.full(d["NP"], 255, dtype=np.uint8)
+
+    def call():
+        chk(L, L.hbls_verify_batch(_p(d["pks"]), _p(d["sigs"]), _p(d["item_msgs"]), _p(d["item_off"]),
+                                   _p(d["item_len"]), d["NP"], _p(st)))
+        assert not st.any()
+    out = {}
+    for name, fe in LARGE_TRACES.items():
+        L.hbls_slot_msm(L.hbls_slot_msm(0))  # the same value again: a clean adaptive history
+        with knobs(L, fe_batch=fe):
+            out[name] = cx.record(call)
+    return out
+
+
 def main(argv=None):
     argv = sys.argv[1:] if argv is None else argv
     out = argv[argv.index("--out") + 1] if "--out" in argv else PATH
@@ -272,9 +325,16 @@ def main(argv=None):
     traces = {}
     for name, run in CASES.items():
         traces.update(run(cx))
+    if "--large" in argv:
+        import bench
+        wl = dict(validators=53_000, n=10, t=7, distinct=True, n_msgs=0)
+        large = large_traces(L, bench.setup_inputs(L, wl, wl["validators"], 0))
+    else:
+        with open(PATH) as f:
+            large = json.load(f)["traces_large"]
     with open(out, "w") as f:
-        json.dump({"recorded_with": L.hbls_build_id().decode(), "traces": traces}, f, indent=1)
-    print("wrote", out, {k: len(v) for k, v in traces.items()})
+        json.dump({"recorded_with": L.hbls_build_id().decode(), "traces": traces, "traces_large": large}, f, indent=1)
+    print("wrote", out, {k: len(v) for k, v in {**traces, **large}.items()})
 
 
 if __name__ == "__main__":

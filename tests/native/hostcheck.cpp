@@ -1039,3 +1039,49 @@ extern "C" int hc_verify_plan(const uint64_t* in, uint64_t* out, char* err, size
   memcpy(out, f, sizeof f);
   return 0;
 }
+
+// hgroup.h: the host-buffer Verify calls' grouping from plain arrays (tests/test_hgroup.py).
+#include "../../charon_amd/csrc/hgroup.h"
+// the group limit of an n-item call and whether it defers its messages' lines
+extern "C" uint64_t hc_call_gmax(uint64_t n, uint64_t single_max, uint64_t fe_min, uint64_t gmax) {
+  return call_gmax((size_t)n, (size_t)single_max, (size_t)fe_min, (size_t)gmax);
+}
+extern "C" int hc_defer_lines(uint64_t n_groups, uint64_t n_msgs, uint64_t fe_min) {
+  return defer_lines((size_t)n_groups, (size_t)n_msgs, (size_t)fe_min) ? 1 : 0;
+}
+// grouping by message: order, midx (n each) and gstart (room for n + 1); returns the group count
+extern "C" uint64_t hc_group_by_message(const uint32_t* idx, uint64_t n, uint64_t n_msgs, uint64_t gmax, uint32_t* order,
+                                        uint32_t* midx, uint64_t* gstart) {
+  const MsgGroups g = group_by_message(idx, (size_t)n, (size_t)n_msgs, (size_t)gmax);
+  if (g.order.size() != n || g.midx.size() != n) return ~uint64_t(0);
+  if (n) memcpy(order, g.order.data(), n * sizeof(uint32_t));
+  if (n) memcpy(midx, g.midx.data(), n * sizeof(uint32_t));
+  for (size_t k = 0; k < g.gstart.size(); k++) gstart[k] = g.gstart[k];
+  return g.n_groups();
+}
+// grouping by runs: goff (room for n + 1); returns the group count
+extern "C" uint64_t hc_group_runs(const uint32_t* idx, uint64_t n, uint64_t gmax, uint32_t* goff) {
+  std::vector<uint32_t> s;
+  split_runs(idx, (size_t)n, (size_t)gmax, s);
+  memcpy(goff, s.data(), s.size() * sizeof(uint32_t));
+  return s.size() - 1;
+}
+// the chunk split: cg (room for K + 1), goff_base (K), goffs (n_groups + K); returns the chunk
+// count, the length of goffs in *n_goffs
+extern "C" uint64_t hc_split_chunks(const uint64_t* gstart, uint64_t n_groups, uint64_t K, uint64_t* cg,
+                                    uint64_t* goff_base, uint32_t* goffs, uint64_t* n_goffs) {
+  const std::vector<size_t> gs(gstart, gstart + n_groups + 1);
+  const ChunkSplit s = split_chunks(gs.data(), (size_t)n_groups, (size_t)K);
+  if (s.goff_base.size() != s.n_chunks() || s.n_chunks() > K || s.goffs.size() > n_groups + K) return ~uint64_t(0);
+  for (size_t c = 0; c < s.cg.size(); c++) cg[c] = s.cg[c];
+  for (size_t c = 0; c < s.goff_base.size(); c++) goff_base[c] = s.goff_base[c];
+  memcpy(goffs, s.goffs.data(), s.goffs.size() * sizeof(uint32_t));
+  *n_goffs = s.goffs.size();
+  return s.n_chunks();
+}
+// one shard's offsets: out (ge - gb + 1) = gstart[gb .. ge] - gstart[gb]
+extern "C" void hc_rebase_offsets(const uint64_t* gstart, uint64_t gb, uint64_t ge, uint32_t* out) {
+  std::vector<uint32_t> r;
+  rebase_offsets(gstart, (size_t)gb, (size_t)ge, r);
+  memcpy(out, r.data(), r.size() * sizeof(uint32_t));
+}

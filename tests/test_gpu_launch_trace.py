@@ -6,8 +6,11 @@ consequences.  The fixture holds the launch sequence (hbls_timing / hbls_timing_
 -- small calls, the per-batch check, the slot-wide check with both combinations, several chunks of
 groups, the adaptive skip, the first-error mode, hbls_slot_device's variants, the host path --
 recorded by tests/golden/make_launch_traces.py with the library of the commit before the pipeline
-was split into a plan and phases; a change that is not meant to alter the sequence must reproduce
-it exactly, name by name.  The cases and their inputs are the generator's own (CASES).
+was split into a plan and phases (the first-error and per-device-shard host traces: of the commit
+before the host paths' grouping moved into hgroup.h; both recorded in two separate processes, which
+agreed); a change that is not meant to alter the sequence must reproduce it exactly, name by name.
+The cases and their inputs are the generator's own (CASES).  The large call's traces of the same
+file (traces_large) are checked by tests/test_gpu_robustness.py, on its fixture.
 """
 import json
 import os
@@ -40,7 +43,8 @@ def golden():
 def test_every_recorded_trace_has_a_case(golden):
     """The fixture and the cases name the same traces (no case dropped, none unrecorded)."""
     want = set(mk.CASES) - {"adaptive", "host"} | {"adaptive_1_failed", "adaptive_2_skipped", "adaptive_3_skipped_clean",
-                                                  "host_no_key_cache", "host_key_cache"}
+                                                  "host_no_key_cache", "host_key_cache", "host_first_error",
+                                                  "host_split2"}
     assert set(golden) == want
 
 
@@ -72,3 +76,7 @@ def test_paths_differ(golden):
     assert "k_first_item" in golden["first_error_small"]
     assert "k_lines_at_p" in golden["slot_deferred_slot_wide"] and "k_lines_at_p" not in golden["slot_deferred_per_batch"]
     assert "k_pk_lookup" not in golden["slot_tables"] and "k_pk_lookup" in golden["slot_dv_src"]
+    assert "k_first_item" in golden["host_first_error"] and "k_first_item" not in golden["host_no_key_cache"]
+    # two contexts, each a small call of 65 groups with its own hashing and signature-cache put
+    assert golden["host_split2"].count("k_hash_to_g2") == 2 and golden["host_split2"].count("k_sc_put") == 2
+    assert "k_batch_verdict" not in golden["host_split2"] and "k_batch_verdict" in golden["host_no_key_cache"]

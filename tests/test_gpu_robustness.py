@@ -134,6 +134,31 @@ def test_verify_large_chunks_below_fe_batch(L, large):
     assert V == 53_000
 
 
+def test_verify_large_launch_sequence(L, large):
+    """verify_large's launches over the fixture, name by name, against the traces recorded
+    (tests/golden/make_launch_traces.py large_traces, launch_traces.json traces_large) with the
+    library of the commit before the host paths' grouping moved into hgroup.h -- in two separate
+    processes, which agreed: two chunks on two host-call contexts, each its own k_hash_to_g2 over
+    its range of the message table, followed at once by k_lines_msg where the chunk does not defer
+    its lines and not where it does, then its verification and its signature-cache put."""
+    import json
+    sys.path.insert(0, os.path.join(ROOT, "tests", "golden"))
+    import make_launch_traces as mk
+    with open(mk.PATH) as f:
+        golden = json.load(f)["traces_large"]
+    assert set(golden) == set(mk.LARGE_TRACES)
+    deferred, lines = golden["verify_large_deferred"], golden["verify_large_chunk_lines"]
+    assert deferred.count("k_hash_to_g2") == 2 and lines.count("k_hash_to_g2") == 2  # two chunks each
+    assert deferred.count("k_sc_put") == 2 and lines.count("k_sc_put") == 2
+    after_hash = lambda t: [t[k + 1] for k, x in enumerate(t) if x == "k_hash_to_g2"]  # noqa: E731
+    assert after_hash(lines) == ["k_lines_msg"] * 2 and after_hash(deferred) == ["k_dec_pk"] * 2
+    assert "k_lines_at_p" in deferred and "k_lines_at_p" not in lines and "k_batch_verdict" not in lines
+    got = mk.large_traces(L, large)
+    for name, names in got.items():
+        assert names == golden[name], (name, [(k, a, b) for k, (a, b) in enumerate(zip(names, golden[name])) if a != b][:3],
+                                       len(names), len(golden[name]))
+
+
 def test_sig_cache_concurrent_callers(L, large):
     """A large Verify (signature-cache puts), ThresholdAggregate batches of the same partials
     (cache gets) and single Verifies from three threads at once, several rounds: every status and
