@@ -38,6 +38,7 @@ EXPORTS = (
     "hbls_debug_split", "hbls_build_id", "hbls_sig_cache", "hbls_duty_signing_roots",
     "hbls_single_max", "hbls_dec_pair_max", "hbls_tune", "hbls_verify_batch_first_error",
     "hbls_verify_device_first_error", "hbls_key_learn_stats", "hbls_key_wide_stats",
+    "hbls_slot_select_device", "hbls_slot_select_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -139,6 +140,8 @@ def _declare(lib):
         "hbls_key_wide_stats": ([P, SZ, P], ctypes.c_int),
         "hbls_debug_split": ([U32], ctypes.c_int),
         "hbls_slot_device": ([ctypes.POINTER(HblsSlot), P], ctypes.c_int),
+        "hbls_slot_select_device": ([ctypes.POINTER(HblsSlot), U32, P, P, P], ctypes.c_int),
+        "hbls_slot_select_stats": ([P, SZ], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
         "hbls_sync": ([P], ctypes.c_int),
         "hbls_status_bitmap": ([P, SZ, P, P], ctypes.c_int),
@@ -232,6 +235,16 @@ def key_wide_stats(L, max_devices: int = 32):
     check(L.hbls_key_wide_stats(out, max_devices, ctypes.byref(n)))
     names = ("built", "wide_chunks", "narrow_chunks", "wide_items", "narrow_items")
     return [dict(zip(names, (int(v) for v in out[5 * k:5 * k + 5]))) for k in range(n.value)]
+
+
+def slot_select_stats(L):
+    """The cumulative counters of hbls_slot_select_device over the devices of the mask, reset by this
+    read (hbls_slot_select_stats; waits for the devices' work): groups seen, groups below threshold,
+    groups whose members are not their first `threshold` candidates, groups the small-scalar path
+    aggregated."""
+    out = (ctypes.c_uint64 * 4)()
+    check(L.hbls_slot_select_stats(out, 4))
+    return dict(zip(("groups", "too_few", "shifted", "small_path"), (int(v) for v in out)))
 
 
 def check(rc: int):

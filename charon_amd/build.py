@@ -163,6 +163,46 @@ def build_widecheck(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+TASELCHECK_PREFIX = "hbls-taselcheck:"
+
+
+def taselcheck_build_id(root: str = "") -> str:
+    """The id embedded in the member-selection harness (tests/native/taselcheck.cpp, `ts_build_id()`):
+    sha256 over its source, the one header it compiles (charon_amd/csrc/tasel.h) and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "taselcheck.cpp"),
+              os.path.join(root, "charon_amd", "csrc", "tasel.h")]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return TASELCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_taselcheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_taselcheck.so (tests/test_tasel_host.py): the verified-member selection
+    rule of hbls_slot_select_device on the CPU; test-only.  Reused when its embedded id equals the
+    tree's, as build_hostcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "taselcheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_taselcheck.so")
+    bid = taselcheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-taselcheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DTS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
 def build_c_client(force: bool = False, verbose: bool = True) -> str:
     """tests/native/cabi_client: a C program linked against libhipbls.so through include/hipbls.h
     (what the Go shim's cgo does), compiled with -std=c99 -Wall -Wextra -Werror so the header is
@@ -402,7 +442,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_widecheck, build_devblocks_all, build_widedev):
+    for fn in (build_c_client, build_widecheck, build_taselcheck, build_devblocks_all, build_widedev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -7,6 +7,9 @@ calls.  INTEGRATION.md §3 gives the same changes as Go patches.
                                   (+ eth2util/signing/signing.go:96-115 zero-signature check)
   sigagg_aggregate                core/sigagg/sigagg.go:48-81 + aggregate :83-122 (TA :105, verify :117,
                                   NewVerifier :124-144)
+  sigagg_slot                     parsigex.go:93-98 -> parsigdb/memory.go:198-225 -> sigagg.go:84-117 for one duty
+                                  in ONE device call (hbls_slot_select_device): verify, pick verified members,
+                                  aggregate, verify the aggregates
   validatorapi_submit             core/validatorapi/validatorapi.go:284-306 + verifyPartialSig :1213-1229
   lock_verify_signatures          cluster/lock.go:151-197 (VerifyAggregate over every pubshare, :185)
   dkg_agg_deposit_data            dkg/dkg.go:820-899 (n x Verify + ThresholdAggregate + Verify per DV)
@@ -139,6 +142,110 @@ def sigagg_aggregate(impl, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
     if pre is not None:
         raise _wrap("threshold aggregate", pre)
     return dict(zip(done, outs))
+
+
+def sigagg_slot(impl_or_L, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
+                pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], sets: Mapping[bytes, Sequence[ParSig]],
+                device: int = 0):
+    """One duty from the exchanged partials to the aggregates, as the node does it in three places:
+    ParSigEx verifies every partial before it is stored (parsigex.go:93-98), the ParSigDB fires with
+    the first `threshold` stored partials of a validator (parsigdb/memory.go:198-225), and the
+    Aggregator aggregates exactly those and verifies the result under the DV key (sigagg.go:84-117).
+    Here the whole duty is one hbls_slot_select_device call: sets[pubkey] lists the validator's
+    partials in arrival order, every one is verified, and the first `threshold` that verify (one per
+    share index) are aggregated -- a corrupted partial costs its operator's vote, not the
+    validator's signature.
+
+    Returns (statuses, aggregates, used): per validator the status of each of its partials (in set
+    order), the 96-byte aggregate, and the positions in its set of the partials that were aggregated.
+    The first validator (in set order) without an aggregate aborts the duty as Aggregator.Aggregate
+    does: "threshold aggregate: require threshold signatures" (sigagg.go:86) when fewer than
+    `threshold` of its partials verified, else the aggregation's or the aggregate verification's error.
+    impl_or_L: a charon_amd.tbls.HIPBLS or the loaded library."""
+    import ctypes
+
+    import numpy as np
+    import torch
+
+    from . import _lib
+    L = getattr(impl_or_L, "_L", impl_or_L)
+    if not sets:
+        raise CallerError("empty partial signed data set")
+    keys = list(sets)
+    roots, root_of = [], {}
+    pks, sigs, midx, idx, goff = [], [], [], [], [0]
+    for pk in keys:
+        for ps in sets[pk]:
+            if len(ps.signature) != 96:
+                raise _wrap("threshold aggregate", "signature from core: " + _LEN_ERR)
+            shares = pubshares_by_key.get(pk)
+            if shares is None or ps.share_idx not in shares:
+                raise _wrap("invalid partial signature",
+                            "unknown pubkey, not part of cluster lock" if shares is None else "invalid shareIdx")
+            if ps.signing_root not in root_of:
+                root_of[ps.signing_root] = len(roots)
+                roots.append(ps.signing_root)
+            pks.append(shares[ps.share_idx])
+            sigs.append(ps.signature)
+            midx.append(root_of[ps.signing_root])
+            idx.append(ps.share_idx)
+        goff.append(len(pks))
+    n, V, M = len(pks), len(keys), len(roots)
+    dev = torch.device("cuda", device)
+
+    def up(a):
+        return torch.from_numpy(a).to(dev)
+
+    def u8(chunks, width):
+        return np.frombuffer(b"".join(chunks), dtype=np.uint8).copy() if chunks else np.zeros(width, dtype=np.uint8)
+
+    g_msgs = up(u8(roots, 32))
+    g_moff = up((np.arange(max(M, 1), dtype=np.int64) * 32))
+    g_mlen = up(np.asarray([len(r) for r in roots] or [0], dtype=np.int32))
+    g_pks, g_sigs = up(u8(pks, 48)), up(u8(sigs, 96))
+    g_midx = up(np.asarray(midx or [0], dtype=np.int32))
+    g_src = up(np.arange(max(n, 1), dtype=np.int32))
+    g_idx = up(np.asarray(idx or [0], dtype=np.int64))
+    g_goff = up(np.asarray(goff, dtype=np.int32))
+    g_dv = up(u8([dv_pubkeys[pk] for pk in keys], 48))
+    hm = torch.zeros(max(M, 1) * L.hbls_hm_entry_bytes(), dtype=torch.uint8, device=dev)
+    vst = torch.full((max(n, 1),), 255, dtype=torch.uint8, device=dev)
+    tout = torch.zeros(V * 96, dtype=torch.uint8, device=dev)
+    tst = torch.full((V,), 255, dtype=torch.uint8, device=dev)
+    ast = torch.full((V,), 255, dtype=torch.uint8, device=dev)
+    chosen = torch.zeros(V * threshold, dtype=torch.int32, device=dev)
+    count = torch.zeros(V, dtype=torch.int32, device=dev)
+    # a validator's partials are consecutive, so when each validator signs one root (and has a
+    # partial) the candidate offsets also serve as the verification groups; else every partial alone
+    grouped = all(goff[k + 1] > goff[k] and len({ps.signing_root for ps in sets[pk]}) == 1
+                  for k, pk in enumerate(keys))
+    ptr = lambda x: x.data_ptr()  # noqa: E731
+    slot = _lib.HblsSlot(msgs=ptr(g_msgs), msg_off=ptr(g_moff), msg_len=ptr(g_mlen), n_msgs=M, hm=ptr(hm),
+                         pks=ptr(g_pks), sigs=ptr(g_sigs), msg_idx=ptr(g_midx), n=n,
+                         vgrp_off=ptr(g_goff) if grouped else None, n_vgroups=V if grouped else n, vstatus=ptr(vst), ta_sigs=None, ta_src=ptr(g_src), ta_idx=ptr(g_idx),
+                         grp_off=ptr(g_goff), n_groups=V, n_ta_partials=n, ta_out=ptr(tout), ta_status=ptr(tst),
+                         dv_pks=ptr(g_dv), agg_vstatus=ptr(ast))
+    stream = torch.cuda.Stream(device=dev)
+    stream.wait_stream(torch.cuda.current_stream(dev))
+    _lib.check(L.hbls_slot_select_device(ctypes.byref(slot), threshold, ctypes.c_void_p(ptr(chosen)),
+                                         ctypes.c_void_p(ptr(count)), ctypes.c_void_p(stream.cuda_stream)))
+    stream.synchronize()
+    vst_h, tst_h, ast_h = vst.cpu().numpy(), tst.cpu().numpy(), ast.cpu().numpy()
+    out_h = tout.cpu().numpy().reshape(V, 96)
+    chosen_h = chosen.cpu().numpy().view(np.uint32).reshape(V, threshold)
+    count_h = count.cpu().numpy()
+    statuses = {pk: [int(x) for x in vst_h[goff[k]:goff[k + 1]]] for k, pk in enumerate(keys)}
+    used = {pk: [int(c) - goff[k] for c in chosen_h[k, :count_h[k]]] for k, pk in enumerate(keys)}
+    for k in range(V):
+        if tst_h[k] == _lib.UNCHECKED:
+            raise _wrap("threshold aggregate", "require threshold signatures")
+        if tst_h[k] == _lib.BAD_INPUT:
+            raise _wrap("threshold aggregate", "partial signatures over different signing roots")
+        if tst_h[k] != OK:
+            raise _wrap("threshold aggregate", status_error("threshold_aggregate", int(tst_h[k])))
+        if ast_h[k] != OK:
+            raise _wrap("threshold aggregate", "aggregate signature verification failed: " + _verr(int(ast_h[k])))
+    return statuses, {pk: bytes(out_h[k]) for k, pk in enumerate(keys)}, used
 
 
 def validatorapi_submit(impl, pubshare_of: Mapping[bytes, bytes],

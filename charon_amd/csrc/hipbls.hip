@@ -318,6 +318,10 @@ enum WsId {
   W_PFIN, W_TBUF, W_F1, W_F1BAD, W_F1S, W_FIRST,                                                                  // final exponentiations' factors
   W_KLMISS, W_KLCNT,  // learned key cache: the call's missing keys (partials' keys, then DV keys) and their two counts
   W_KLENT, W_KLMENT,  // its ladder tables: every key's entry number (lookup), every miss's (learn -> k_pk_wide)
+  // verified-member selection (hbls_slot_select_device): per group in the caller's order, the counting
+  // sort, the tables and the aggregation's outputs in class order, the aggregates to verify
+  W_SELCIDX, W_SELKEY, W_SELSTATE, W_SELGMSG, W_SELHIST, W_SELOFF, W_SELPERM, W_SELPMEM, W_SELPIDX, W_SELPGOFF,
+  W_SELPOUT, W_SELPST, W_SELPPT, W_SELAPT, W_SELAST,
   W_COUNT_
 };
 
@@ -466,6 +470,8 @@ struct Dev {
   hipEvent_t res_ev[N_RES] = {};
   unsigned res_head = 0, res_tail = 0;  // records [tail, head) not yet read
   bool attack = false;                  // the last known call had invalid items a pairing caught
+  // verified-member selection: its cumulative counters (layout.h SEL_*; hbls_slot_select_stats)
+  DevBuf sel_ctr;
   // timing (hbls_timing)
   bool timing = false;
   bool serial = false;  // timing mode 2: every timed launch completes before the next is enqueued
@@ -838,7 +844,9 @@ struct TaFold {
 // decompressed (pts, mst) into ta_out / ta_status; agg_pt (nullable) gets the affine results.
 int ta_tail(Dev& d, Ws& w, const HmEntry* pts, const uint32_t* src, const uint8_t* mst_in, const int64_t* didx,
             const uint32_t* dgoff, size_t n_groups, size_t np, int mode, uint8_t* out, uint8_t* status,
-            HmEntry* agg_pt, hipStream_t s, hipEvent_t mst_ready = nullptr, hipEvent_t pts_ready = nullptr) {
+            HmEntry* agg_pt, hipStream_t s, hipEvent_t mst_ready = nullptr, hipEvent_t pts_ready = nullptr,
+            const uint8_t** sdone_out = nullptr) {
+  if (sdone_out) *sdone_out = nullptr;  // the groups the small-scalar path took, when it ran
   uint8_t* mst;
   TaDigits* dig;
   void* tab;
@@ -881,6 +889,7 @@ int ta_tail(Dev& d, Ws& w, const HmEntry* pts, const uint32_t* src, const uint8_
             launch_ta_small(pts, src, didx, (uint32_t)n_groups, (uint32_t)t_u, csm, sdig, sok, stab, sdone, pj, s,
                             nonuni, pts_ready));
       pts_ready = nullptr;  // waited for inside, after the index-only split
+      if (sdone_out) *sdone_out = sdone;
     }
     if (pts_ready) HCHK(hipStreamWaitEvent(s, pts_ready, 0));
     // the members' statuses are first read by the Lagrange digits: the small-scalar ladders above
@@ -1017,6 +1026,10 @@ struct VerifyCall {
   size_t defer_msgs = 0;
   // first-error mode (vplan.h): the first item whose status is decided and not OK (0xffffffff: none)
   uint32_t* first_out = nullptr;
+  // the items' signatures already decompressed and in G2, with their statuses (sigs is then unused):
+  // hbls_slot_select_device's aggregates, sums of partials it decompressed and subgroup-checked
+  const HmEntry* pre_sig = nullptr;
+  const uint8_t* pre_sigst = nullptr;
   // handed back: the decompressed signatures and their statuses (the host calls' signature-cache put)
   HmEntry* vsig = nullptr;
   uint8_t* vsigst = nullptr;
@@ -1181,8 +1194,14 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
   } else if (n_agg) {
     TIMED(d, "k_dec_pk", w.side[0], launch_dec_pk(fold->dv_pks, (uint32_t)n_agg, b.apk, b.apkst, w.side[0]));
   }
-  TIMED(d, "k_dec_sig_pt", w.side[1],
-        launch_dec_sig_pt(c.sigs, (uint32_t)n, b.vsig, b.vsigst, w.side[1], nullptr, w.ev_dec));
+  if (c.pre_sig) {
+    b.vsig = const_cast<HmEntry*>(c.pre_sig);
+    b.vsigst = const_cast<uint8_t*>(c.pre_sigst);
+    HCHK(hipEventRecord(w.ev_dec, w.side[1]));
+  } else {
+    TIMED(d, "k_dec_sig_pt", w.side[1],
+          launch_dec_sig_pt(c.sigs, (uint32_t)n, b.vsig, b.vsigst, w.side[1], nullptr, w.ev_dec));
+  }
   HCHK(hipEventRecord(w.ev_side[0], w.side[0]));
   HCHK(hipEventRecord(w.ev_side[1], w.side[1]));
   // the misses into the table, behind everything that waits for the keys; the next call's lookup
@@ -3196,6 +3215,187 @@ int hbls_slot_device(const hbls_slot* a, void* stream) {
   if (verify_pipeline(*d, w, vc)) return -1;
   HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
   return ws_release(w, s);
+}
+
+// hbls_slot_device with verified-member selection.  Four phases on the caller's stream, each behind
+// the one before (the aggregation needs the verdicts, the second verification the aggregates):
+//   1. hash, and verify the partials without a fold (workspace set w: the decompressed partials stay)
+//   2. select each group's members and put the groups in class order (threshold.hip k_ta_select ...)
+//   3. ThresholdAggregate over the chosen members through src into the retained points (ta_tail)
+//   4. verify the aggregates under the DV keys: a second verify_pipeline on the next workspace set,
+//      one item per group, handed the affine aggregates in place of signature bytes (pre_sig); a
+//      group without an aggregate is an item with a bad signature status, which costs no pairing
+int hbls_slot_select_device(const hbls_slot* a, uint32_t threshold, uint32_t* chosen, uint32_t* ta_count,
+                            void* stream) {
+  Dev* d;
+  hipStream_t s = (hipStream_t)stream;
+  if (dev_of_stream(s, &d)) return -1;
+  if (!a) return set_err("hbls_slot_select_device: null arguments");
+  if (threshold == 0 || threshold > (uint32_t)TA_SMALL_MAX)
+    return set_err("hbls_slot_select_device: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
+  if (a->ta_sigs) return set_err("hbls_slot_select_device: ta_sigs must be NULL (the candidates are verified partials)");
+  const size_t ng = a->n_groups, t = threshold;
+  if (ng && (!a->ta_src || !a->ta_idx || !a->grp_off || !chosen || !ta_count || !a->ta_out || !a->ta_status))
+    return set_err("hbls_slot_select_device: ta_src, ta_idx, grp_off, chosen, ta_count, ta_out and ta_status are required");
+  if (ng && (!a->dv_pks || !a->agg_vstatus)) return set_err("hbls_slot_select_device: dv_pks and agg_vstatus are required");
+  if (a->n >= 0xffffffffull || ng * t >= 0xffffffffull || a->n_ta_partials >= 0xffffffffull)
+    return set_err("hbls_slot_select_device: too many items");
+  if ((a->pk_table != nullptr) != (a->pk_table_st != nullptr) ||
+      (a->dv_pk_table != nullptr) != (a->dv_pk_table_st != nullptr))
+    return set_err("hbls_slot_select_device: a key table needs its status array");
+  std::lock_guard<std::mutex> lk(d->mu);
+  Ws& w = ws_acquire(*d, s);
+  if (s) {  // behind what the default stream holds now, as hbls_slot_device
+    HCHK(hipEventRecord(w.ev_dflt, nullptr));
+    HCHK(hipStreamWaitEvent(s, w.ev_dflt, 0));
+  }
+  // phase 1
+  bool defer = false;
+  if (a->n) {
+    HCHK(hipEventRecord(w.ev_fork, s));
+    hipStream_t sh = w.side[2];
+    HCHK(hipStreamWaitEvent(sh, w.ev_fork, 0));
+    defer = defer_lines(a->n_vgroups, a->n_msgs);
+    if (hash_messages(*d, a->msgs, a->msg_off, a->msg_len, a->n_msgs, (MsgEntry*)a->hm, sh, !defer)) return -1;
+    HCHK(hipEventRecord(w.ev_side[2], sh));
+  }
+  TaFold tables{};
+  tables.pk_table = (const G1AEntry*)a->pk_table;
+  tables.pk_table_st = a->pk_table_st;
+  VerifyCall vc;
+  vc.pks = a->pks;
+  vc.sigs = a->sigs;
+  vc.msg_idx = a->msg_idx;
+  vc.hm = (const MsgEntry*)a->hm;
+  vc.n = a->n;
+  vc.grp_off = a->vgrp_off;
+  vc.n_groups = a->n_vgroups;
+  vc.status = a->vstatus;
+  vc.s = s;
+  vc.hm_ready = w.ev_side[2];
+  vc.fold = a->pk_table ? &tables : nullptr;
+  vc.defer_hm = (MsgEntry*)a->hm;
+  vc.defer_msgs = defer ? a->n_msgs : 0;
+  if (a->n) {
+    if (verify_pipeline(*d, w, vc)) return -1;
+    HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  }
+  if (!ng) return ws_release(w, s);
+  // phase 2
+  const bool first_use = d->sel_ctr.p == nullptr;
+  uint64_t* ctr;
+  if (ensure_buf(d->sel_ctr, SEL_COUNTERS * sizeof(uint64_t), (void**)&ctr)) return -1;
+  if (first_use) {  // once per device, and complete before any stream's kernel counts
+    HCHK(hipMemset(ctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
+    HCHK(hipStreamSynchronize(nullptr));
+  }
+  TaSelectArgs sa{};
+  uint8_t *pout, *pst, *ast;
+  HmEntry *ppt, *apt;
+  if (wsbuf(w, W_SELCIDX, ng * t, &sa.cidx) || wsbuf(w, W_SELKEY, ng, &sa.key) || wsbuf(w, W_SELSTATE, ng, &sa.state) ||
+      wsbuf(w, W_SELGMSG, ng, &sa.gmsg) || wsbuf(w, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
+      wsbuf(w, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w, W_SELPERM, ng, &sa.perm) ||
+      wsbuf(w, W_SELPMEM, ng * t, &sa.pmem) || wsbuf(w, W_SELPIDX, ng * t, &sa.pidx) ||
+      wsbuf(w, W_SELPGOFF, ng + 1, &sa.pgoff) || wsbuf(w, W_SELPOUT, 96 * ng, &pout) || wsbuf(w, W_SELPST, ng, &pst) ||
+      wsbuf(w, W_SELPPT, ng, &ppt) || wsbuf(w, W_SELAPT, ng, &apt) || wsbuf(w, W_SELAST, ng, &ast))
+    return -1;
+  sa.cur = sa.hist + TASEL_KEYS;
+  sa.vstatus = a->vstatus;
+  sa.msg_idx = a->msg_idx;
+  sa.n = (uint32_t)a->n;
+  sa.src = a->ta_src;
+  sa.idx = a->ta_idx;
+  sa.grp_off = a->grp_off;
+  sa.n_groups = (uint32_t)ng;
+  sa.n_cand = (uint32_t)a->n_ta_partials;
+  sa.t = threshold;
+  sa.chosen = chosen;
+  sa.ta_count = ta_count;
+  sa.ctr = ctr;
+  HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
+  TIMED(*d, "k_ta_select", s, launch_ta_select(sa, s));
+  TaScatterArgs sc{};
+  sc.n_groups = (uint32_t)ng;
+  sc.state = sa.state;
+  sc.ta_out = a->ta_out;
+  sc.ta_status = a->ta_status;
+  sc.ctr = ctr;
+  if (!a->n) {  // no partial: no group has a member
+    TIMED(*d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+    TIMED(*d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a->ta_status, (uint32_t)ng, a->agg_vstatus, s));
+    return ws_release(w, s);
+  }
+  TIMED(*d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
+  TIMED(*d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
+  // phase 3
+  const uint8_t* sdone = nullptr;
+  if (ta_tail(*d, w, vc.vsig, sa.pmem, vc.vsigst, sa.pidx, sa.pgoff, ng, ng * t, 0, pout, pst, ppt, s, nullptr, nullptr,
+              &sdone))
+    return -1;
+  sc.perm = sa.perm;
+  sc.pout = pout;
+  sc.pstatus = pst;
+  sc.ppt = ppt;
+  sc.sdone = sdone;
+  sc.rows16 = (((uintptr_t)a->ta_out | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
+  sc.agg_pt = apt;
+  sc.agg_st = ast;
+  TIMED(*d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+  // phase 4.  The messages' lines: computed by phase 1 unless it deferred them; then this pass
+  // defers them too where its plan can (the batched sizes), else they are computed first
+  Ws& w2 = ws_acquire(*d, s);
+  size_t defer2 = 0;
+  if (defer) {
+    if (vp_bfe(VerifyShape{ng, ng, 0, false, false, 0, d->n_cu, false},
+               VerifyKnobs{g_gcap.load(), g_fbcap.load(), g_fe_batch_min.load(), g_slot_msm_min.load(),
+                           g_rlc_lanes.load(), g_adaptive.load()}))
+      defer2 = a->n_msgs;
+    else
+      TIMED(*d, "k_lines_msg", s, launch_lines_msg((MsgEntry*)a->hm, (uint32_t)a->n_msgs, s));
+  }
+  TaFold tables2{};
+  tables2.pk_table = (const G1AEntry*)a->dv_pk_table;
+  tables2.pk_table_st = a->dv_pk_table_st;
+  VerifyCall v2;
+  v2.pks = a->dv_pks;
+  v2.pre_sig = apt;
+  v2.pre_sigst = ast;
+  v2.msg_idx = sa.gmsg;
+  v2.hm = (const MsgEntry*)a->hm;
+  v2.n = ng;
+  v2.n_groups = ng;
+  v2.status = a->agg_vstatus;
+  v2.s = s;
+  v2.fold = a->dv_pk_table ? &tables2 : nullptr;
+  v2.defer_hm = (MsgEntry*)a->hm;
+  v2.defer_msgs = defer2;
+  if (verify_pipeline(*d, w2, v2)) return -1;
+  TIMED(*d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a->ta_status, (uint32_t)ng, a->agg_vstatus, s));
+  if (ws_release(w, s)) return -1;
+  return &w2 == &w ? 0 : ws_release(w2, s);
+}
+
+// Cumulative per-process counters of hbls_slot_select_device over the devices of the mask, reset by
+// reading: out[0] groups seen, out[1] groups with fewer than `threshold` members, out[2] groups whose
+// members are not their first `threshold` candidates, out[3] groups the small-scalar path aggregated
+// (n <= 4).  Waits for the devices' work.
+int hbls_slot_select_stats(uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  if (!out || n > (size_t)SEL_COUNTERS) return set_err("hbls_slot_select_stats: out is null or n above 4");
+  for (size_t k = 0; k < n; k++) out[k] = 0;
+  for (Dev* d : devs()) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    if (!d->sel_ctr.p) continue;
+    HCHK(hipSetDevice(d->ord));
+    // the counting kernels run on the callers' streams, which the library does not know: the device
+    HCHK(hipDeviceSynchronize());
+    uint64_t c[SEL_COUNTERS];
+    HCHK(hipMemcpy(c, d->sel_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    HCHK(hipMemset(d->sel_ctr.p, 0, sizeof(c)));
+    HCHK(hipDeviceSynchronize());
+    for (size_t k = 0; k < n; k++) out[k] += c[k];
+  }
+  return 0;
 }
 
 int hbls_timing(int enable) {

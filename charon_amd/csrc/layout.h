@@ -5,6 +5,7 @@
 #include <atomic>
 #include "ops.h"
 #include "ta_small.h"
+#include "tasel.h"
 
 // Occupancy targets (waves per SIMD) of the heavy kernels: 1 lets the compiler use all 512
 // registers of a lane, 2 gives each wave 256, 3 gives 168 (spilling the rest to scratch).  Chosen
@@ -110,6 +111,56 @@ void launch_ta_small(const HmEntry* pts, const uint32_t* src, const int64_t* idx
                      hipStream_t s, const uint8_t* nonuni, hipEvent_t pts_ready = nullptr);
 void launch_ta_member_status(const uint8_t* sig_st, const uint32_t* src, uint32_t n_partials, uint8_t* mstat,
                              hipStream_t s);
+
+// Verified-member selection (threshold.hip k_ta_select / k_ta_sel_fill / k_ta_sel_scatter /
+// k_ta_sel_verdicts; the rule is tasel.h's).  ctr: the device's cumulative counters.
+enum { SEL_SEEN = 0, SEL_FEW = 1, SEL_SHIFTED = 2, SEL_SMALL = 3, SEL_COUNTERS = 4 };
+struct TaSelectArgs {
+  // the n verified partials and the groups' candidates [grp_off[g], grp_off[g + 1])
+  const uint8_t* vstatus;
+  const uint32_t* msg_idx;
+  uint32_t n;
+  const uint32_t* src;
+  const int64_t* idx;
+  const uint32_t* grp_off;
+  uint32_t n_groups, t;
+  uint32_t n_cand;  // entries of src / idx: offsets beyond them are cut there
+  // per group, the caller's order: members (n_groups t, the caller's array), their share indices,
+  // the count (the caller's array), class key, state (tasel.h TASEL_*) and message
+  uint32_t* chosen;
+  int64_t* cidx;
+  uint32_t* ta_count;
+  uint32_t* key;
+  uint8_t* state;
+  uint32_t* gmsg;
+  // the counting sort by key: hist / cur (TASEL_KEYS, zeroed by the caller), off (their scan, + 1)
+  uint32_t *hist, *off, *cur;
+  // class order: place p holds group perm[p]; its members, indices and offset p t (n_groups + 1)
+  uint32_t *perm, *pmem, *pgoff;
+  int64_t* pidx;
+  uint64_t* ctr;
+};
+struct TaScatterArgs {
+  uint32_t n_groups;
+  const uint32_t* perm;  // null: nothing was aggregated
+  const uint8_t* state;
+  // the aggregation's outputs in class order: 96-byte rows, statuses, affine points, and the groups
+  // the small-scalar path took (nullable)
+  const uint8_t *pout, *pstatus;
+  const HmEntry* ppt;
+  const uint8_t* sdone;
+  // the caller's group order: rows (rows16: both row arrays are 16-byte aligned), statuses, and for
+  // the aggregates' verification the points with their statuses (0 = an aggregate to verify)
+  uint8_t *ta_out, *ta_status;
+  int rows16;
+  HmEntry* agg_pt;
+  uint8_t* agg_st;
+  uint64_t* ctr;
+};
+void launch_ta_select(const TaSelectArgs& a, hipStream_t s);
+void launch_ta_sel_fill(const TaSelectArgs& a, hipStream_t s);
+void launch_ta_sel_scatter(const TaScatterArgs& a, hipStream_t s);
+void launch_ta_sel_verdicts(const uint8_t* ta_status, uint32_t n_groups, uint8_t* agg_vstatus, hipStream_t s);
 
 // Hashing and the pairing kernel (pipeline.hip).
 constexpr int GROUPS_PER_WAVE = 21;  // k_pair3: 3 lanes per pairing, 21 pairings per wave

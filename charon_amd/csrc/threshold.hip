@@ -882,4 +882,114 @@ void launch_ta_member_status(const uint8_t* sig_st, const uint32_t* src, uint32_
                        n_partials, mstat);
 }
 
+// ---------------------------------------------------------------------------------------
+// Verified-member selection (hbls_slot_select_device; the rule is tasel.h's ta_select).  Behind the
+// verification's final verdicts:
+//   k_ta_select   1 lane / group: the members among the group's candidates -> chosen, ta_count (the
+//                 caller's), their share indices, the group's state, message and 16-bit class key,
+//                 and the key's histogram
+//   k_plan_scan   (vbatch.hip) the classes' offsets
+//   k_ta_sel_fill 1 lane / group: the group's place in class order, its members and indices into
+//                 the uniform tables the aggregation reads (grp_off[p] = p t)
+//   ... the aggregation over those tables (hipbls.hip ta_tail) ...
+//   k_ta_sel_scatter 1 lane / place: rows, statuses and affine aggregates back to the caller's group
+//                 order; groups without an aggregate get theirs here
+//   k_ta_sel_verdicts 1 lane / group, behind the aggregates' verification: the post-aggregate
+//                 verdicts of the groups that had no aggregate to verify
+// Why the order: the small-scalar path (k_ta_small) runs only in waves whose 64 validators share
+// one index set.  With a few members replaced here and there, almost no wave of 64 consecutive
+// validators is uniform; in class order every class fills whole waves but its last.  The order is a
+// matter of speed alone: ta_small_uniform still compares the coefficients themselves.
+// ---------------------------------------------------------------------------------------
+static_assert(TASEL_MAX == (uint32_t)TA_SMALL_MAX, "tasel.h restates ta_small.h");
+
+__device__ __forceinline__ void sel_count(uint64_t* ctr, bool flag) {
+  const uint64_t m = __ballot(flag);
+  if (m && (threadIdx.x & 63u) == (uint32_t)(__ffsll((unsigned long long)m) - 1))
+    atomicAdd((unsigned long long*)ctr, (unsigned long long)__popcll(m));
+}
+
+__global__ __launch_bounds__(64) void k_ta_select(TaSelectArgs a) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = g < a.n_groups;
+  TaSel r{};
+  if (valid) {
+    const uint32_t b = min(a.grp_off[g], a.n_cand), e = min(max(a.grp_off[g + 1], b), a.n_cand);
+    r = ta_select(a.vstatus, a.msg_idx, a.n, a.src, a.idx, b, e, a.t, a.chosen + (size_t)g * a.t,
+                  a.cidx + (size_t)g * a.t);
+    a.ta_count[g] = r.count;
+    a.key[g] = r.key;
+    a.state[g] = r.state;
+    a.gmsg[g] = r.msg;
+    atomicAdd(a.hist + r.key, 1u);
+  }
+  sel_count(a.ctr + SEL_SEEN, valid);
+  sel_count(a.ctr + SEL_FEW, valid && r.state == TASEL_FEW);
+  sel_count(a.ctr + SEL_SHIFTED, valid && r.shifted);
+}
+
+__global__ __launch_bounds__(64) void k_ta_sel_fill(TaSelectArgs a) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g >= a.n_groups) return;
+  const uint32_t key = a.key[g];
+  const uint32_t p = a.off[key] + atomicAdd(a.cur + key, 1u);  // < n_groups: off is the scan of these counts
+  a.perm[p] = g;
+  a.pgoff[p] = p * a.t;
+  if (g == 0) a.pgoff[a.n_groups] = a.n_groups * a.t;
+  const bool ok = a.state[g] == TASEL_OK;
+  // a group without an aggregate keeps the tables uniform with members that exist (partial 0, indices
+  // 1 .. t); what the aggregation makes of them is dropped by k_ta_sel_scatter
+  for (uint32_t k = 0; k < a.t; k++) {
+    a.pmem[(size_t)p * a.t + k] = ok ? a.chosen[(size_t)g * a.t + k] : 0u;
+    a.pidx[(size_t)p * a.t + k] = ok ? a.cidx[(size_t)g * a.t + k] : (int64_t)k + 1;
+  }
+}
+
+// perm == nullptr: nothing was aggregated (a call without partials); every group is without an aggregate
+__global__ __launch_bounds__(64) void k_ta_sel_scatter(TaScatterArgs a) {
+  const uint32_t p = blockIdx.x * blockDim.x + threadIdx.x;
+  const bool valid = p < a.n_groups;
+  const uint32_t g = valid ? (a.perm ? a.perm[p] : p) : 0;
+  const uint8_t state = valid ? a.state[g] : (uint8_t)TASEL_FEW;
+  const bool have = valid && a.perm && state == TASEL_OK;
+  sel_count(a.ctr + SEL_SMALL, have && a.sdone && a.sdone[p] != 0);
+  if (!valid) return;
+  const uint8_t st = have ? a.pstatus[p] : state == TASEL_MIXED ? (uint8_t)ST_BAD_INPUT : (uint8_t)ST_UNCHECKED;
+  a.ta_status[g] = st;
+  if (a.agg_st) a.agg_st[g] = st != ST_OK ? 1 : 0;
+  if (have && a.agg_pt) a.agg_pt[g] = a.ppt[p];
+  if (a.rows16) {
+    uint4* o = reinterpret_cast<uint4*>(a.ta_out) + 6ull * g;
+    const uint4* in = reinterpret_cast<const uint4*>(a.pout) + 6ull * p;
+    HB_UNROLL for (int w = 0; w < 6; w++) o[w] = have ? in[w] : make_uint4(0, 0, 0, 0);
+  } else {
+    for (int k = 0; k < 96; k++) a.ta_out[96ull * g + k] = have ? a.pout[96ull * p + k] : (uint8_t)0;
+  }
+}
+
+__global__ __launch_bounds__(64) void k_ta_sel_verdicts(const uint8_t* __restrict__ ta_status, uint32_t n_groups,
+                                                        uint8_t* __restrict__ agg_vstatus) {
+  const uint32_t g = blockIdx.x * blockDim.x + threadIdx.x;
+  if (g < n_groups && ta_status[g] != ST_OK) agg_vstatus[g] = ta_status[g];
+}
+
+void launch_ta_select(const TaSelectArgs& a, hipStream_t s) {
+  if (!a.n_groups) return;
+  const dim3 grid(blocks_of(a.n_groups, 64));
+  hipLaunchKernelGGL(k_ta_select, grid, dim3(64), 0, s, a);
+}
+void launch_ta_sel_fill(const TaSelectArgs& a, hipStream_t s) {
+  if (!a.n_groups) return;
+  hipLaunchKernelGGL(k_ta_sel_fill, dim3(blocks_of(a.n_groups, 64)), dim3(64), 0, s, a);
+}
+void launch_ta_sel_scatter(const TaScatterArgs& a, hipStream_t s) {
+  if (!a.n_groups) return;
+  hipLaunchKernelGGL(k_ta_sel_scatter, dim3(blocks_of(a.n_groups, 64)), dim3(64), 0, s, a);
+}
+void launch_ta_sel_verdicts(const uint8_t* ta_status, uint32_t n_groups, uint8_t* agg_vstatus, hipStream_t s) {
+  if (!n_groups) return;
+  hipLaunchKernelGGL(k_ta_sel_verdicts, dim3(blocks_of(n_groups, 64)), dim3(64), 0, s, ta_status, n_groups,
+                     agg_vstatus);
+}
+
 }  // namespace hb

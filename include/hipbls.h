@@ -32,7 +32,9 @@ enum hbls_status {
   HBLS_COMBINE_FAILED = 4, /* "cannot combine signatures"                           herumi.go:282 */
   HBLS_BAD_SECRET = 5,     /* "cannot unmarshal secret into Herumi secret key"      herumi.go:310 */
   HBLS_BAD_INPUT = 6,      /* malformed batch description (offsets/lengths)  -- new, batch-only */
-  HBLS_UNCHECKED = 7       /* first-error calls only: after the first failing item, not resolved */
+  HBLS_UNCHECKED = 7       /* not resolved: first-error calls, after the first failing item;
+                              hbls_slot_select_device, a group with fewer than `threshold` verified
+                              members ("require threshold signatures", sigagg.go:86) */
 };
 
 /* Return codes of the entry points themselves: 0 on success, <0 on a HIP/runtime error or a
@@ -304,6 +306,34 @@ typedef struct hbls_slot {
   const uint8_t* dv_pk_table_st;
 } hbls_slot;
 int hbls_slot_device(const hbls_slot* args, void* stream);
+/* hbls_slot_device with verified-member selection (parsigex.go:93-98 -> parsigdb/memory.go:198-225
+ * -> sigagg.go:84-117).  args as for hbls_slot_device, except:
+ *   - ta_src / ta_idx / grp_off list each group's CANDIDATES in the caller's order of preference
+ *     (arrival order); groups may have different candidate counts, 0 included; ta_sigs must be NULL;
+ *   - dv_pks is required; vgrp_off's groups are independent of the aggregation groups (the
+ *     n_vgroups == n_groups rule of the folded form does not apply).
+ * Group g's members are its first `threshold` candidates j, in order, with vstatus[ta_src[j]] == OK
+ * whose share index differs from every member already chosen (sigagg.go:90-97 keys by ShareIdx).
+ * chosen (device, n_groups * threshold uint32): the members as indices among the n partials,
+ * 0xffffffff past the last one.  ta_count (device, n_groups uint32): members found (<= threshold).
+ * A group with fewer than `threshold` members gets ta_status = agg_vstatus = HBLS_UNCHECKED and 96
+ * zero bytes in ta_out (sigagg.go:85-86, 99-101); a group whose candidates do not all carry one
+ * msg_idx gets HBLS_BAD_INPUT in both (and zero bytes).  Otherwise ta_status is as in
+ * hbls_threshold_aggregate_batch over the chosen members and agg_vstatus[g] the verdict of the
+ * aggregate under dv_pks[g] over the members' message (the aggregation status when no aggregate was
+ * produced).  vstatus is what hbls_slot_device writes for the same partials.  The aggregation runs
+ * behind the verdicts and the aggregates' verification behind the aggregation, all stream-ordered
+ * as hbls_slot_device: no host synchronisation, every output valid when later work on `stream`
+ * starts.  threshold: 1 .. 16, anything else is a call error.
+ * hbls_slot_select_stats: cumulative per-process counters over the devices of the mask, reset by
+ * reading (n <= 4): out[0] groups seen, out[1] groups with fewer than `threshold` members, out[2]
+ * groups whose members are not their first `threshold` candidates, out[3] groups aggregated by the
+ * small-scalar path (whole waves of validators with one index set: the call orders the groups by
+ * their chosen positions to keep it that way; a falling share means the slower per-member ladders
+ * ran).  Waits for the devices' work. */
+int hbls_slot_select_device(const hbls_slot* args, uint32_t threshold, uint32_t* chosen,
+                            uint32_t* ta_count, void* stream);
+int hbls_slot_select_stats(uint64_t* out, size_t n);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
