@@ -38,7 +38,7 @@ EXPORTS = (
     "hbls_debug_split", "hbls_build_id", "hbls_sig_cache", "hbls_duty_signing_roots",
     "hbls_single_max", "hbls_dec_pair_max", "hbls_tune", "hbls_verify_batch_first_error",
     "hbls_verify_device_first_error", "hbls_key_learn_stats", "hbls_key_wide_stats",
-    "hbls_slot_select_device", "hbls_slot_select_stats",
+    "hbls_slot_select_device", "hbls_slot_select_stats", "hbls_subgroup_batch", "hbls_subgroup_batch_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -156,6 +156,8 @@ def _declare(lib):
         "hbls_stats": ([P, SZ], ctypes.c_int),
         "hbls_fe_batch": ([SZ], SZ),
         "hbls_slot_msm": ([SZ], SZ),
+        "hbls_subgroup_batch": ([SZ], SZ),
+        "hbls_subgroup_batch_stats": ([P, SZ, P], ctypes.c_int),
         "hbls_adaptive": ([ctypes.c_int], ctypes.c_int),
         "hbls_rlc_lanes": ([SZ], SZ),
         "hbls_ta_joint": ([SZ], SZ),
@@ -235,6 +237,16 @@ def key_wide_stats(L, max_devices: int = 32):
     check(L.hbls_key_wide_stats(out, max_devices, ctypes.byref(n)))
     names = ("built", "wide_chunks", "narrow_chunks", "wide_items", "narrow_items")
     return [dict(zip(names, (int(v) for v in out[5 * k:5 * k + 5]))) for k in range(n.value)]
+
+
+def subgroup_batch_stats(L, max_devices: int = 32):
+    """Per device of the mask: the batched subgroup test's cumulative counters
+    (hbls_subgroup_batch_stats; waits for the library's enqueued work)."""
+    out = (ctypes.c_uint64 * (4 * max_devices))()
+    n = ctypes.c_size_t(0)
+    check(L.hbls_subgroup_batch_stats(out, max_devices, ctypes.byref(n)))
+    names = ("run", "failed", "laddered", "skipped")
+    return [dict(zip(names, (int(v) for v in out[4 * k:4 * k + 4]))) for k in range(n.value)]
 
 
 def slot_select_stats(L):

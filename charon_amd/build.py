@@ -203,6 +203,47 @@ def build_taselcheck(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+SUBGCHECK_PREFIX = "hbls-subgcheck:"
+SUBGCHECK_HEADERS = ("subgbatch.h", "sha256.h", "hd.h", "vplan.h")
+
+
+def subgcheck_build_id(root: str = "") -> str:
+    """The id embedded in the batched subgroup test's harness (tests/native/subgcheck.cpp,
+    `sg_build_id()`): sha256 over its source, the headers it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "subgcheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in SUBGCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return SUBGCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_subgcheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_subgcheck.so (tests/test_subgroup_batch_host.py): the batched subgroup
+    test's digits and its plan on the CPU; test-only.  Reused when its embedded id equals the tree's,
+    as build_hostcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "subgcheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_subgcheck.so")
+    bid = subgcheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-subgcheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DSG_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
 def build_c_client(force: bool = False, verbose: bool = True) -> str:
     """tests/native/cabi_client: a C program linked against libhipbls.so through include/hipbls.h
     (what the Go shim's cgo does), compiled with -std=c99 -Wall -Wextra -Werror so the header is
@@ -395,6 +436,50 @@ def build_widedev(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+SUBGDEV_PREFIX = "hbls-subgdev:"
+
+
+def subgdev_build_id(root: str = "") -> str:
+    """The id embedded in the batched subgroup test's device harness (tests/native/subgdev.hip,
+    tests/test_gpu_subgroup_batch.py; `sd_build_id()`): sha256 over its source, the device
+    harnesses' shared devblocks.h, the product source it compiles (msm.hip), every header of
+    charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "subgdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "msm.hip")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return SUBGDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_subgdev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_subgdev.so: the batched subgroup test's class sums and weighted sums on
+    the device over explicit buckets, a harness of its own like build_widedev; test-only.  Reused
+    when its embedded id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "subgdev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_subgdev.so")
+    bid = subgdev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-subgdev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DSD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -442,7 +527,8 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_widecheck, build_taselcheck, build_devblocks_all, build_widedev):
+    for fn in (build_c_client, build_widecheck, build_taselcheck, build_subgcheck, build_devblocks_all, build_widedev,
+               build_subgdev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -294,6 +294,14 @@ std::atomic<size_t> g_slot_msm_min{32768};
 // saves the signature-side MSM, its lines and Miller loop, the product tree and one final
 // exponentiation per slot.  Verdicts are the same either way.
 std::atomic<bool> g_adaptive{true};
+// HBLS_SUBGROUP_BATCH / hbls_subgroup_batch: device-buffer verifications of at least this many
+// items that decompress all their signatures check them for G2 membership with one batched test
+// (msm.hip k_subg_*: five bucket entries per signature and 20 tested sums instead of a 63-doubling
+// ladder each) and run the per-item ladders only if it fails (0 = never).  2^19: above every call
+// with a pinned launch trace (the largest runs chunks of 265 000 items), and far above the
+// break-even.  With HBLS_ADAPTIVE, after a call whose batched test failed the
+// next calls go straight to the ladders until one of them finds every signature in G2.
+std::atomic<size_t> g_subg_batch_min{size_t(1) << 19};
 // HBLS_SINGLE_MAX / hbls_single_max: host Verify batches of fewer items check every item alone
 // (hgroup.h SINGLE_MAX_DEFAULT: the batched final exponentiation's threshold, g_fe_batch_min)
 std::atomic<size_t> g_single_max{SINGLE_MAX_DEFAULT};
@@ -315,6 +323,7 @@ enum WsId {
   W_FBUF, W_GS, W_BS, W_BLINES, W_BBAD, W_BVER, W_GLIST, W_GCOUNT,  // batched final exponentiation
   W_MCNT, W_MOFF, W_MCUR, W_MORDER, W_MENT, W_MBUCKET, W_MPART, W_MPART2, W_MTOT, W_PBUF1, W_PBUF2, W_PBUF3, W_SFAIL,  // slot-wide check
   W_MLEV,                                                                          // its evaluated Miller lines
+  W_SGDIG, W_SGCNT, W_SGOFF, W_SGCUR, W_SGORDER, W_SGENT, W_SGBUCKET, W_SGCLS, W_SGSUMS, W_SGREC,  // batched subgroup test
   W_PFIN, W_TBUF, W_F1, W_F1BAD, W_F1S, W_FIRST,                                                                  // final exponentiations' factors
   W_KLMISS, W_KLCNT,  // learned key cache: the call's missing keys (partials' keys, then DV keys) and their two counts
   W_KLENT, W_KLMENT,  // its ladder tables: every key's entry number (lookup), every miss's (learn -> k_pk_wide)
@@ -403,6 +412,10 @@ struct SlotRes {
   uint32_t gcount;
 };
 constexpr unsigned N_RES = 16;
+struct SubgRes {
+  uint32_t rec[2];
+  uint32_t skipped, pad;
+};
 
 struct Dev {
   int ord = -1;
@@ -470,6 +483,14 @@ struct Dev {
   hipEvent_t res_ev[N_RES] = {};
   unsigned res_head = 0, res_tail = 0;  // records [tail, head) not yet read
   bool attack = false;                  // the last known call had invalid items a pairing caught
+  // batched subgroup test: its cumulative counters on the device (hbls_subgroup_batch_stats) and
+  // its own adaptive history, kept like the slot-wide check's -- the record of each call that ran
+  // or skipped the test ([0] the test failed, [1] points its ladders found off G2)
+  DevBuf sg_ctr;
+  SubgRes* sres_host = nullptr;
+  hipEvent_t sres_ev[N_RES] = {};
+  unsigned sres_head = 0, sres_tail = 0;
+  bool subg_failed = false;  // the last known call had signatures off G2
   // verified-member selection: its cumulative counters (layout.h SEL_*; hbls_slot_select_stats)
   DevBuf sel_ctr;
   // timing (hbls_timing)
@@ -615,6 +636,14 @@ int dev_create(int ord, Dev** out) {
   HCHK(hipEventCreateWithFlags(&d->kl_ev, hipEventDisableTiming));
   HCHK(hipHostMalloc((void**)&d->res_host, N_RES * sizeof(SlotRes), hipHostMallocDefault));
   for (unsigned k = 0; k < N_RES; k++) HCHK(hipEventCreateWithFlags(&d->res_ev[k], hipEventDisableTiming));
+  HCHK(hipHostMalloc((void**)&d->sres_host, N_RES * sizeof(SubgRes), hipHostMallocDefault));
+  for (unsigned k = 0; k < N_RES; k++) HCHK(hipEventCreateWithFlags(&d->sres_ev[k], hipEventDisableTiming));
+  {
+    void* p;
+    if (ensure_buf(d->sg_ctr, sizeof(SubgCtr), &p)) return -1;
+    HCHK(hipMemset(p, 0, sizeof(SubgCtr)));
+    HCHK(hipStreamSynchronize(nullptr));
+  }
   *out = d;
   return 0;
 }
@@ -646,6 +675,7 @@ int init_mask(uint32_t mask) {
   g_fe_batch_min = env_size("HBLS_FE_BATCH", g_fe_batch_min.load());
   g_slot_msm_min = env_size("HBLS_SLOT_MSM", g_slot_msm_min.load());
   g_adaptive = env_size("HBLS_ADAPTIVE", 1) != 0;
+  g_subg_batch_min = env_size("HBLS_SUBGROUP_BATCH", g_subg_batch_min.load());
   g_single_max = env_size("HBLS_SINGLE_MAX", SINGLE_MAX_DEFAULT);
   g_dec_pair_max = env_size("HBLS_DEC_PAIR_MAX", 0);
   g_ta_pair_max = env_size("HBLS_TA_PAIR_MAX", g_ta_pair_max.load());
@@ -1017,6 +1047,7 @@ struct VerifyCall {
   hipEvent_t h_ready = nullptr;   // host calls: the hashing alone, before the messages' lines
   const TaFold* fold = nullptr;   // the slot's ThresholdAggregate and folded aggregates, key tables
   bool key_cache = false;         // host-buffer call: the keys through the public-key cache
+  bool device_entry = false;      // a device-buffer entry point (the batched subgroup test, vplan.h own_sigs)
   // defer_hm / defer_msgs: the caller hashed the defer_msgs messages at defer_hm (the call's messages
   // or a contiguous range of them) without their Miller lines (callers whose messages have about one
   // verification group each, batched final exponentiation sizes): the slot-wide check evaluates each
@@ -1089,6 +1120,8 @@ struct VerifyBufs {
   // the learned keys' ladder tables for the key sides of the combinations: the partials' keys and
   // the DV keys (ent null unless this call's keys came through the learned cache's lookup)
   KeyWideRef kw, akw;
+  // batched subgroup test (subg_batch; subg_skip: its record alone)
+  SubgArgs sg;
 };
 
 // chunks of the chunked combination (an upper bound: a group's last chunk may be short)
@@ -1125,6 +1158,14 @@ int verify_bufs(Ws& w, const VerifyPlan& p, VerifyBufs& b) {
                  wsbuf(w, W_PBUF3, 3 * p.nb2, &b.pbuf3) || wsbuf(w, W_SFAIL, 2, &b.sfail) ||
                  wsbuf(w, W_MLEV, N_LINES * gcap, &b.mlev)))
     return -1;
+  SubgArgs& sg = b.sg;
+  if (p.subg_batch && (wsbuf(w, W_SGDIG, SG_WINDOWS * n, &sg.dig) || wsbuf(w, W_SGCNT, SG_KEYS, &sg.cnt) ||
+                       wsbuf(w, W_SGOFF, SG_KEYS + 1, &sg.off) || wsbuf(w, W_SGCUR, SG_KEYS, &sg.cur) ||
+                       wsbuf(w, W_SGORDER, SG_KEYS, &sg.order) || wsbuf(w, W_SGENT, SG_WINDOWS * n, &sg.ent) ||
+                       wsbuf(w, W_SGBUCKET, SG_KEYS, &sg.bucket) || wsbuf(w, W_SGCLS, SG_CLASSES, &sg.cls) ||
+                       wsbuf(w, W_SGSUMS, SG_SUMS, &sg.sums)))
+    return -1;
+  if ((p.subg_batch || p.subg_skip) && wsbuf(w, W_SGREC, 2, &sg.rec)) return -1;
   if ((p.rlc_chunked || p.smsm) && wsbuf(w, W_COEF, n + n_agg, &b.coef)) return -1;
   const size_t max_chunks = rlc_chunk_count(p);
   if (p.rlc_chunked &&
@@ -1135,6 +1176,53 @@ int verify_bufs(Ws& w, const VerifyPlan& p, VerifyBufs& b) {
   if (!p.bfe && (wsbuf(w, W_F1, 3 * 2 * gcap, &b.f1) || wsbuf(w, W_F1BAD, gcap, &b.f1bad) || wsbuf(w, W_F1S, gcap, &b.f1S)))
     return -1;
   return rlc_key(b.key) ? -1 : 0;
+}
+
+// The signatures of a large call (plan subg_batch / subg_skip), on side 1: the square roots as ever
+// (ev_dec behind them: the aggregation's ladders start there), then the batched subgroup test --
+// digits, counting sort, bucket sums, class sums, the 20 weighted sums and their verdict -- and the
+// per-item ladders behind its flag: launched always, they return at once when every sum was in G2
+// and run exactly as without the test when one was not, so the host never waits and every status
+// and zeroed point is the ladders' own.  subg_skip (the adaptive history expects a failure): the
+// ladders alone, counting what they find.  Either way the call's record goes to the history.
+int verify_subgroup_batch(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, VerifyBufs& b) {
+  hipStream_t s1 = w.side[1];
+  const uint32_t n = (uint32_t)p.n;
+  SubgArgs& sg = b.sg;
+  SubgCtr* ctr = (SubgCtr*)d.sg_ctr.p;
+  HCHK(hipMemsetAsync(sg.rec, 0, 2 * sizeof(uint32_t), s1));
+  if (p.subg_skip) {
+    TIMED(d, "k_dec_sig_pt", s1, launch_dec_sig_pt(c.sigs, n, b.vsig, b.vsigst, s1, nullptr, w.ev_dec, ctr, sg.rec + 1));
+    TIMED(d, "k_subg_skipped", s1, launch_subg_skipped(ctr, s1));
+  } else {
+    HCHK(hipMemsetAsync(sg.cnt, 0, SG_KEYS * sizeof(uint32_t), s1));
+    HCHK(hipMemsetAsync(sg.cur, 0, SG_KEYS * sizeof(uint32_t), s1));
+    TIMED(d, "k_dec_sig_pt", s1, launch_dec_sig_sqrt(c.sigs, n, b.vsig, b.vsigst, s1, nullptr));
+    HCHK(hipEventRecord(w.ev_dec, s1));
+    sg.sig = b.vsig;
+    sg.sig_st = b.vsigst;
+    sg.n = n;
+    sg.key = b.key;
+    sg.ctr = ctr;
+    TIMED(d, "k_subg_digits", s1, launch_subg_digits(sg, s1));
+    TIMED(d, "k_subg_count", s1, launch_subg_count(sg, s1));
+    TIMED(d, "k_subg_scan", s1, launch_scan(sg.cnt, SG_KEYS, sg.off, s1));
+    TIMED(d, "k_subg_fill", s1, launch_subg_fill(sg, s1));
+    TIMED(d, "k_subg_bucket", s1, launch_subg_bucket(sg, s1));
+    TIMED(d, "k_subg_class", s1, launch_subg_class(sg.bucket, sg.cls, s1));
+    TIMED(d, "k_subg_weigh", s1, launch_subg_weigh(sg.cls, sg.sums, s1));
+    TIMED(d, "k_subg_verdict", s1, launch_subg_verdict(sg.sums, sg.rec, ctr, s1));
+    TIMED(d, "k_g2_subgroup", s1, launch_g2_subgroup(n, b.vsig, b.vsigst, s1, nullptr, sg.rec, ctr, sg.rec + 1));
+  }
+  // the call's outcome for the next calls' choice (read when its event has completed)
+  if (p.adaptive && d.sres_head - d.sres_tail < N_RES) {
+    const unsigned k = d.sres_head % N_RES;
+    d.sres_host[k].skipped = p.subg_skip ? 1 : 0;
+    HCHK(hipMemcpyAsync(d.sres_host[k].rec, sg.rec, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s1));
+    HCHK(hipEventRecord(d.sres_ev[k], s1));
+    d.sres_head++;
+  }
+  return 0;
 }
 
 // Decompress: the fork onto the side streams, the public keys from one of four sources, the
@@ -1198,6 +1286,8 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
     b.vsig = const_cast<HmEntry*>(c.pre_sig);
     b.vsigst = const_cast<uint8_t*>(c.pre_sigst);
     HCHK(hipEventRecord(w.ev_dec, w.side[1]));
+  } else if (p.subg_batch || p.subg_skip) {
+    if (verify_subgroup_batch(d, w, c, p, b)) return -1;
   } else {
     TIMED(d, "k_dec_sig_pt", w.side[1],
           launch_dec_sig_pt(c.sigs, (uint32_t)n, b.vsig, b.vsigst, w.side[1], nullptr, w.ev_dec));
@@ -1734,7 +1824,7 @@ int verify_stats(const VerifyCall& c, const VerifyPlan& p, const VerifyBufs& b) 
 // order they enqueue.  Fills c.vsig / c.vsigst.
 int verify_pipeline(Dev& d, Ws& w, VerifyCall& c) {
   const VerifyKnobs knobs{g_gcap.load(),         g_fbcap.load(),     g_fe_batch_min.load(),
-                          g_slot_msm_min.load(), g_rlc_lanes.load(), g_adaptive.load()};
+                          g_slot_msm_min.load(), g_rlc_lanes.load(), g_adaptive.load(), g_subg_batch_min.load()};
   VerifyShape sh{};
   sh.n = c.n;
   sh.n_groups = c.n_groups;
@@ -1752,6 +1842,16 @@ int verify_pipeline(Dev& d, Ws& w, VerifyCall& c) {
       d.res_tail++;
     }
   sh.attack = d.attack;
+  // likewise the batched subgroup test's: after a failed test the ladders run alone, until a call's
+  // ladders find nothing off G2
+  sh.own_sigs = c.device_entry && !c.pre_sig;
+  if (knobs.adaptive && vp_subg_wide(sh, knobs))
+    while (d.sres_tail != d.sres_head && hipEventQuery(d.sres_ev[d.sres_tail % N_RES]) == hipSuccess) {
+      const SubgRes& r = d.sres_host[d.sres_tail % N_RES];
+      d.subg_failed = r.skipped ? r.rec[1] != 0 : r.rec[0] != 0;
+      d.sres_tail++;
+    }
+  sh.subg_failed = d.subg_failed;
   VerifyPlan p;
   if (const char* refused = verify_plan(sh, knobs, p)) return set_err(refused);
   VerifyBufs b{};
@@ -2916,6 +3016,7 @@ int hbls_verify_device(const uint8_t* pks, const uint8_t* sigs, const uint32_t* 
   vc.n_groups = n_vgroups;
   vc.status = status;
   vc.s = s;
+  vc.device_entry = true;
   if (verify_pipeline(*d, w, vc)) return -1;
   return ws_release(w, s);
 }
@@ -2944,6 +3045,7 @@ int hbls_verify_device_first_error(const uint8_t* pks, const uint8_t* sigs, cons
   vc.n_groups = n_vgroups;
   vc.status = status;
   vc.s = s;
+  vc.device_entry = true;
   vc.first_out = first;
   if (verify_pipeline(*d, w, vc)) return -1;
   return ws_release(w, s);
@@ -3056,6 +3158,31 @@ int hbls_key_wide_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
     out[5 * k + 2] = c.narrow_chunks;
     out[5 * k + 3] = c.wide_items;
     out[5 * k + 4] = c.narrow_items;
+    k++;
+  }
+  *n_devices = k;
+  return 0;
+}
+
+// The batched subgroup test, per device of the mask and cumulative: out[4 k + 0] batched tests run,
+// + 1 batched tests that failed, + 2 signatures that went through the per-item ladders of calls
+// large enough for the test, + 3 calls that skipped the test by the adaptive history.  Waits like
+// hbls_key_wide_stats.
+int hbls_subgroup_batch_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
+  if (ensure_init()) return -1;
+  if (!out || !n_devices) return set_err("hbls_subgroup_batch_stats: null arguments");
+  size_t k = 0;
+  for (Dev* d : devs()) {
+    if (k == max_devices) break;
+    std::lock_guard<std::mutex> lk(d->mu);
+    HCHK(hipSetDevice(d->ord));
+    SubgCtr c{};
+    if (drain_lib_streams(*d)) return -1;
+    HCHK(hipMemcpy(&c, d->sg_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
+    out[4 * k + 0] = c.run;
+    out[4 * k + 1] = c.failed;
+    out[4 * k + 2] = c.laddered;
+    out[4 * k + 3] = c.skipped;
     k++;
   }
   *n_devices = k;
@@ -3208,6 +3335,7 @@ int hbls_slot_device(const hbls_slot* a, void* stream) {
   vc.n_groups = a->n_vgroups;
   vc.status = a->vstatus;
   vc.s = s;
+  vc.device_entry = true;
   vc.hm_ready = w.ev_side[2];
   vc.fold = &fold;
   vc.defer_hm = (MsgEntry*)a->hm;
@@ -3272,6 +3400,7 @@ int hbls_slot_select_device(const hbls_slot* a, uint32_t threshold, uint32_t* ch
   vc.n_groups = a->n_vgroups;
   vc.status = a->vstatus;
   vc.s = s;
+  vc.device_entry = true;
   vc.hm_ready = w.ev_side[2];
   vc.fold = a->pk_table ? &tables : nullptr;
   vc.defer_hm = (MsgEntry*)a->hm;
@@ -3496,6 +3625,15 @@ size_t hbls_slot_msm(size_t min_items) {
     d->attack = false;
   }
   return g_slot_msm_min.exchange(min_items);
+}
+size_t hbls_subgroup_batch(size_t min_items) {
+  // a new setting starts from a clean history (tests count the batched tests that ran)
+  for (Dev* d : devs()) {
+    std::lock_guard<std::mutex> lk(d->mu);
+    for (; d->sres_tail != d->sres_head; d->sres_tail++) (void)hipEventSynchronize(d->sres_ev[d->sres_tail % N_RES]);
+    d->subg_failed = false;
+  }
+  return g_subg_batch_min.exchange(min_items);
 }
 size_t hbls_ta_joint(size_t members) { return g_ta_joint.exchange(std::min<size_t>(members, 8)); }
 size_t hbls_rlc_lanes(size_t lanes) { return g_rlc_lanes.exchange(lanes ? lanes : 65536); }

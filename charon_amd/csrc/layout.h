@@ -6,6 +6,7 @@
 #include "ops.h"
 #include "ta_small.h"
 #include "tasel.h"
+#include "subgbatch.h"
 
 // Occupancy targets (waves per SIMD) of the heavy kernels: 1 lets the compiler use all 512
 // registers of a lane, 2 gives each wave 256, 3 gives 168 (spilling the rest to scratch).  Chosen
@@ -265,7 +266,15 @@ void launch_dec_pk(const uint8_t* pks, uint32_t n, G1AEntry* out, uint8_t* st, h
 // decoded (nullable): recorded between the decompression and the subgroup checks (which set a
 // failing point to infinity and its status)
 void launch_dec_sig_pt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s,
-                       const uint8_t* skip = nullptr, hipEvent_t decoded = nullptr);
+                       const uint8_t* skip = nullptr, hipEvent_t decoded = nullptr, struct SubgCtr* ctr = nullptr,
+                       uint32_t* nbad = nullptr);
+// its two halves (verify_decompress runs the batched subgroup test between them): the square roots,
+// and the per-item ladders.  run_if (nullable): the ladders run only if *run_if is nonzero (the
+// batched test's flag, rec[0]); ctr / nbad (nullable): the items laddered and the points found off
+// G2 are counted (the batched test's statistics and its adaptive history)
+void launch_dec_sig_sqrt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip);
+void launch_g2_subgroup(uint32_t n, HmEntry* pts, uint8_t* st, hipStream_t s, const uint8_t* skip, const uint32_t* run_if,
+                        struct SubgCtr* ctr, uint32_t* nbad);
 void launch_sc_put(const uint8_t* sigs, const HmEntry* pts, const uint8_t* st, uint32_t n, uint32_t base, uint32_t cap,
                    void* key, HmEntry* ent, uint8_t* est, uint32_t* tab, uint32_t tcap, uint64_t k0, uint64_t k1,
                    hipStream_t s);
@@ -447,6 +456,39 @@ void launch_msm_fill(const G2MsmArgs& a, hipStream_t s);
 void launch_msm_bucket(const G2MsmArgs& a, hipStream_t s);
 void launch_msm_reduce(const G2MsmArgs& a, hipStream_t s);
 void launch_msm_sum(const G2MsmArgs& a, hipStream_t s);
+// The batched G2 subgroup test of a large call's signatures (msm.hip k_subg_*, subgbatch.h): the
+// counting sort and the bucket sums of the MSM above over SG_KEYS buckets (window, value), then the
+// class sums, the 20 weighted sums and their subgroup tests.  rec: the call's record, zeroed by the
+// caller -- [0] the flag k_g2_subgroup runs behind (set when a sum is off G2), [1] the points
+// k_g2_subgroup found off G2.  ctr: the device's cumulative counters (hbls_subgroup_batch_stats).
+struct SubgCtr {
+  unsigned long long run, failed, laddered, skipped;
+};
+struct SubgArgs {
+  const HmEntry* sig;     // [n] decompressed, before their subgroup checks
+  const uint8_t* sig_st;  // [n] decode statuses (nonzero: not in the sums)
+  uint32_t n;
+  RlcKey key;
+  uint32_t* dig;     // [SG_WINDOWS n] window values (0: no entry)
+  uint32_t* cnt;     // [SG_KEYS] zeroed
+  uint32_t* off;     // [SG_KEYS + 1]
+  uint32_t* cur;     // [SG_KEYS] zeroed
+  uint32_t* ent;     // [SG_WINDOWS n]
+  uint32_t* order;   // [SG_KEYS]
+  G2JEntry* bucket;  // [SG_KEYS]
+  G2JEntry* cls;     // [SG_CLASSES] class (w, j, c) at (w SG_DIGITS + j) 12 + c - 1
+  G2JEntry* sums;    // [SG_SUMS]
+  uint32_t* rec;     // [2]
+  SubgCtr* ctr;
+};
+void launch_subg_digits(const SubgArgs& a, hipStream_t s);
+void launch_subg_count(const SubgArgs& a, hipStream_t s);
+void launch_subg_fill(const SubgArgs& a, hipStream_t s);
+void launch_subg_bucket(const SubgArgs& a, hipStream_t s);
+void launch_subg_class(const G2JEntry* bucket, G2JEntry* cls, hipStream_t s);
+void launch_subg_weigh(const G2JEntry* cls, G2JEntry* sums, hipStream_t s);
+void launch_subg_verdict(const G2JEntry* sums, uint32_t* rec, SubgCtr* ctr, hipStream_t s);
+void launch_subg_skipped(SubgCtr* ctr, hipStream_t s);
 struct ScatterArgs {
   uint32_t n;
   const uint32_t* item_grp;

@@ -110,12 +110,21 @@ __global__ KB_OCC(HB_OCC_DECSIG) void k_dec_sig_pt(const uint8_t* __restrict__ s
   st[i] = bad;
 }
 
+// run_if (nullable): the batched test's flag (msm.hip k_subg_verdict) -- clear: every checked point
+// is in G2 and the kernel returns at once.  ctr / nbad (nullable): the items laddered (one atomic
+// per wave) and the points found off G2, for hbls_subgroup_batch_stats and the adaptive history.
 __global__ KB_OCC(HB_OCC_SUBG) void k_g2_subgroup(uint32_t n, HmEntry* __restrict__ pts, uint8_t* __restrict__ st,
-                                                   const uint8_t* __restrict__ skip) {
+                                                   const uint8_t* __restrict__ skip, const uint32_t* __restrict__ run_if,
+                                                   SubgCtr* __restrict__ ctr, uint32_t* __restrict__ nbad) {
+  if (run_if && !*run_if) return;
   uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n || (skip && skip[i])) return;
-  const HmEntry e = pts[i];
-  if (st[i] || e.inf) return;
+  bool take = i < n && !(skip && skip[i]);
+  if (take) take = !st[i] && !pts[i].inf;
+  if (ctr) {
+    const uint64_t tm = __ballot(take);
+    if (tm && (threadIdx.x & 63u) == 0) atomicAdd(&ctr->laddered, (unsigned long long)__popcll(tm));
+  }
+  if (!take) return;
   const HmEntry* src = pts + i;
   if (!g2_in_subgroup28_l([src]() { return G2A{src->x, src->y, false}; })) {
     HmEntry z;
@@ -125,6 +134,7 @@ __global__ KB_OCC(HB_OCC_SUBG) void k_g2_subgroup(uint32_t n, HmEntry* __restric
     z.pad[0] = z.pad[1] = z.pad[2] = 0;
     pts[i] = z;
     st[i] = 1;
+    if (nbad) atomicAdd(nbad, 1u);
   }
 }
 
@@ -152,12 +162,18 @@ __global__ KB_OCC(HB_OCC_SUBG) void k_g1_subgroup_h(uint32_t n, G1AEntry* __rest
 #endif
 }
 __global__ KB_OCC(HB_OCC_SUBG) void k_g2_subgroup_h(uint32_t n, HmEntry* __restrict__ pts, uint8_t* __restrict__ st,
-                                                     const uint8_t* __restrict__ skip) {
+                                                     const uint8_t* __restrict__ skip, const uint32_t* __restrict__ run_if,
+                                                     SubgCtr* __restrict__ ctr, uint32_t* __restrict__ nbad) {
 #if defined(__HIP_DEVICE_COMPILE__)
+  if (run_if && !*run_if) return;
   const uint32_t i = (blockIdx.x * blockDim.x + threadIdx.x) >> 1;
-  if (i >= n || (skip && skip[i])) return;
-  const HmEntry e = pts[i];
-  if (st[i] || e.inf) return;
+  bool take = i < n && !(skip && skip[i]);
+  if (take) take = !st[i] && !pts[i].inf;
+  if (ctr) {  // both lanes of a pair vote
+    const uint64_t tm = __ballot(take);
+    if (tm && (threadIdx.x & 63u) == 0) atomicAdd(&ctr->laddered, (unsigned long long)(__popcll(tm) >> 1));
+  }
+  if (!take) return;
   const F2Half m = f2half_make();
   const HmEntry* src = pts + i;
   if (!g2_in_subgroup28_l([src]() { return G2A{src->x, src->y, false}; }, m) && m.h == 0) {
@@ -168,6 +184,7 @@ __global__ KB_OCC(HB_OCC_SUBG) void k_g2_subgroup_h(uint32_t n, HmEntry* __restr
     z.pad[0] = z.pad[1] = z.pad[2] = 0;
     pts[i] = z;
     st[i] = 1;
+    if (nbad) atomicAdd(nbad, 1u);
   }
 #endif
 }
@@ -961,18 +978,22 @@ void launch_pk_learn(const KeyLearnTab& t, const uint8_t* pks, uint32_t n, const
   hipLaunchKernelGGL(k_pk_learn, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, pks, miss, mcount, k0, k1, pts, st, ment);
   if (t.wcap) hipLaunchKernelGGL(k_pk_wide, dim3(blocks_for(n)), dim3(BLOCK), 0, s, t, miss, mcount, ment, pts, st);
 }
-void launch_dec_sig_pt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip,
-                       hipEvent_t decoded) {
-  if (!n) {
-    if (decoded) (void)hipEventRecord(decoded, s);
-    return;
-  }
-  hipLaunchKernelGGL(k_dec_sig_pt, dim3(blocks_for(n)), dim3(BLOCK), 0, s, sigs, n, out, st, skip);
-  if (decoded) (void)hipEventRecord(decoded, s);
+void launch_dec_sig_sqrt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip) {
+  if (n) hipLaunchKernelGGL(k_dec_sig_pt, dim3(blocks_for(n)), dim3(BLOCK), 0, s, sigs, n, out, st, skip);
+}
+void launch_g2_subgroup(uint32_t n, HmEntry* pts, uint8_t* st, hipStream_t s, const uint8_t* skip, const uint32_t* run_if,
+                        SubgCtr* ctr, uint32_t* nbad) {
+  if (!n) return;
   if (n <= dec_pair_max())
-    hipLaunchKernelGGL(k_g2_subgroup_h, dim3(blocks_for(2 * n)), dim3(BLOCK), 0, s, n, out, st, skip);
+    hipLaunchKernelGGL(k_g2_subgroup_h, dim3(blocks_for(2 * n)), dim3(BLOCK), 0, s, n, pts, st, skip, run_if, ctr, nbad);
   else
-    hipLaunchKernelGGL(k_g2_subgroup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, n, out, st, skip);
+    hipLaunchKernelGGL(k_g2_subgroup, dim3(blocks_for(n)), dim3(BLOCK), 0, s, n, pts, st, skip, run_if, ctr, nbad);
+}
+void launch_dec_sig_pt(const uint8_t* sigs, uint32_t n, HmEntry* out, uint8_t* st, hipStream_t s, const uint8_t* skip,
+                       hipEvent_t decoded, SubgCtr* ctr, uint32_t* nbad) {
+  launch_dec_sig_sqrt(sigs, n, out, st, s, skip);
+  if (decoded) (void)hipEventRecord(decoded, s);
+  launch_g2_subgroup(n, out, st, s, skip, nullptr, ctr, nbad);
 }
 void launch_sc_put(const uint8_t* sigs, const HmEntry* pts, const uint8_t* st, uint32_t n, uint32_t base, uint32_t cap,
                    void* key, HmEntry* ent, uint8_t* est, uint32_t* tab, uint32_t tcap, uint64_t k0, uint64_t k1,

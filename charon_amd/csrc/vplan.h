@@ -23,6 +23,7 @@ struct VerifyKnobs {
   size_t slot_msm_min;  // HBLS_SLOT_MSM
   size_t rlc_lanes;     // HBLS_RLC_LANES
   bool adaptive;        // HBLS_ADAPTIVE
+  size_t subg_batch_min = 0;  // HBLS_SUBGROUP_BATCH (0 = never)
 };
 
 struct VerifyShape {
@@ -33,6 +34,10 @@ struct VerifyShape {
   size_t defer_msgs;   // messages whose Miller lines the caller left uncomputed
   int n_cu;            // the device's compute units
   bool attack;         // the device's adaptive history: the last known call had items a pairing caught
+  // the call decompresses its own signatures, all of them, from a device-buffer entry point (no
+  // signatures handed over decompressed, no signature-cache hits to skip)
+  bool own_sigs = false;
+  bool subg_failed = false;  // the adaptive history: the last known call had signatures off G2
 };
 
 struct VerifyPlan {
@@ -50,6 +55,10 @@ struct VerifyPlan {
   uint32_t rlc_cmax;
   bool rlc_chunked;  // the chunked combination (k_plan, k_rlc_msm) instead of the per-item one
   bool keys_only, sparse, lines_at_p;
+  // the signatures' subgroup checks as one batched test (msm.hip k_subg_*), the per-item ladders
+  // behind its flag; subg_skip: ... but the adaptive history says it would fail, so the ladders
+  // run unguarded and count what they find
+  bool subg_batch, subg_skip;
 };
 
 inline size_t vp_groups(const VerifyShape& in) { return in.grouped ? in.n_groups : in.n; }
@@ -65,6 +74,12 @@ inline bool vp_bfe(const VerifyShape& in, const VerifyKnobs& k) {
 // is read only by calls this holds for, before they plan.)
 inline bool vp_slot_wide(const VerifyShape& in, const VerifyKnobs& k) {
   return vp_bfe(in, k) && k.slot_msm_min && vp_groups(in) <= vp_gcap(in, k) && in.n + in.n_agg >= k.slot_msm_min;
+}
+
+// Batched subgroup test: large calls that decompress all their signatures themselves.  (Apart from
+// the plan: its adaptive history is read only by calls this holds for, before they plan.)
+inline bool vp_subg_wide(const VerifyShape& in, const VerifyKnobs& k) {
+  return in.own_sigs && k.subg_batch_min && in.n >= k.subg_batch_min;
 }
 
 // Fills p; returns null, or the reason the call is refused.
@@ -126,6 +141,10 @@ inline const char* verify_plan(const VerifyShape& in, const VerifyKnobs& k, Veri
   // deferred lines: the slot-wide check evaluates each group's chain at P directly (k_lines_at_p);
   // any other path computes the messages' lines first
   p.lines_at_p = in.defer_msgs && p.try_msm;
+  // a failed batched test costs its pass and then the ladders as well: after one, the next calls
+  // ladder every item until one of them finds every signature in G2
+  p.subg_skip = vp_subg_wide(in, k) && k.adaptive && in.subg_failed;
+  p.subg_batch = vp_subg_wide(in, k) && !p.subg_skip;
   return nullptr;
 }
 

@@ -365,6 +365,19 @@ size_t hbls_slot_msm(size_t min_items);
  * slot-wide check failed, the next calls take the per-batch check directly until one passes every
  * batch.  Returns the previous setting.  Verdicts do not depend on it. */
 int hbls_adaptive(int on);
+/* Tuning: device-buffer verifications of at least min_items items that decompress all their
+ * signatures test them for G2 membership at once -- five bucket entries per signature and 20
+ * tested sums, each a combination with random coefficients below 13 -- and run the per-item
+ * ladders only if a sum fails (0 = never; default 524288, HBLS_SUBGROUP_BATCH).  With
+ * hbls_adaptive on, after a call whose batched test failed the next calls take the ladders
+ * directly until one of them finds every signature in G2.  Returns the previous value and clears
+ * that history.  Verdicts, statuses and outputs do not depend on it.
+ * hbls_subgroup_batch_stats: per device (at most max_devices; *n_devices = the number written)
+ * four cumulative values: out[4k] batched tests run, out[4k+1] batched tests that failed,
+ * out[4k+2] signatures of such calls that went through the per-item ladders, out[4k+3] calls that
+ * skipped the test by the history.  Waits for the library's enqueued work on each device. */
+size_t hbls_subgroup_batch(size_t min_items);
+int hbls_subgroup_batch_stats(uint64_t* out, size_t max_devices, size_t* n_devices);
 /* Host Verify batches of fewer than `items` check every item alone (no random-combination ladder
  * on the latency path); SIZE_MAX = the default (the batched final exponentiation's threshold).
  * Returns the previous setting (HBLS_SINGLE_MAX at init).  Verdicts never depend on it. */

@@ -18,6 +18,10 @@ LABELS = {  # bench.py / TIMED label -> kernel symbols of the slot
     "k_group_sum": ["k_group_sum"], "k_rlc": ["k_rlc_msm<1>", "k_rlc<1>", "k_rlc_msm<2>", "k_rlc<2>", "k_rlc_msm<3>", "k_rlc<3>", "k_rlc_msm", "k_rlc",
               "k_rlc_msm<1, 0>", "k_rlc_msm<1, 1>", "k_rlc_msm<1, 2>", "k_rlc_msm<2, 0>", "k_rlc_msm<2, 1>",
               "k_rlc_msm<2, 2>", "k_rlc_msm<3, 0>", "k_rlc_msm<3, 1>"], "k_group_prep": ["k_group_prep_p", "k_group_prep_b"],
+    # the batched subgroup test of large calls (its guarded ladders stay under k_dec_sig_pt)
+    "k_subg_digits": ["k_subg_digits"], "k_subg_count": ["k_subg_count"], "k_subg_fill": ["k_subg_fill"],
+    "k_subg_bucket": ["k_subg_order", "k_subg_bucket"], "k_subg_class": ["k_subg_class"],
+    "k_subg_weigh": ["k_subg_weigh"], "k_subg_verdict": ["k_subg_verdict"],
     "k_msm_bucket": ["k_msm_bucket"], "k_msm_reduce": ["k_msm_reduce"], "k_msm_sum": ["k_msm_sum"],
     "k_slines": ["k_slines"], "k_lines_at_p": ["k_lines_at_p"], "k_pair3_mml": ["k_pair3<4>"], "k_pair3_prod": ["k_pair3<3>"],
     "k_pair3_fin": ["k_pair3<2>", "k_pair6_fin", "k_pair6_fin<3>", "k_pair6_fin<10>"], "k_pair3_ml": ["k_pair3<1>"], "k_attestation_roots": ["k_attestation_roots"],
