@@ -286,10 +286,19 @@ DEVBLOCKS_CURVE_UNITS = [("devblocks_curve.hip", [f"-DDB_CV={k}"], f"cv{k}") for
 DEVBLOCKS_HASH = "hash"
 DEVBLOCKS_HASH_UNITS = [("devblocks_h2c.hip", [f"-DDB_H2C={k}"], f"h2c{k}") for k in (1, 2)] + \
     [("devblocks_h2c_std.hip", [], "h2cstd")]
+# The Miller-loop kernels and the group stage (tests/test_gpu_pairing.py) are a fourth harness,
+# libhbls_devblockspair.so: one unit compiles the product's pipeline.hip itself (which sets its own
+# HB_FAST_FPMUL and HB_ARG_LANES 128: the build passes neither), the other vgroup.hip with fp.h's
+# default lanes, as the library compiles the two.  The pipeline unit is not split: it includes
+# pipeline.hip whole, so its compile time is that file's own.
+DEVBLOCKS_PAIR = "pair"
+DEVBLOCKS_PAIR_UNITS = [("devblocks_pair.hip", [], "pair"), ("devblocks_vgroup.hip", [], "vgroup")]
 # the product sources a harness's units compile themselves, hashed into that harness's id
-DEVBLOCKS_PRODUCT_SOURCES = {DEVBLOCKS_CURVE: ["msm.hip"], DEVBLOCKS_HASH: ["hashsplit.hip"]}
+DEVBLOCKS_PRODUCT_SOURCES = {DEVBLOCKS_CURVE: ["msm.hip"], DEVBLOCKS_HASH: ["hashsplit.hip"],
+                             DEVBLOCKS_PAIR: ["pipeline.hip", "vgroup.hip"]}
 # the harnesses with a library and an id of their own, next to the block builds
-DEVBLOCKS_OWN = {DEVBLOCKS_CURVE: DEVBLOCKS_CURVE_UNITS, DEVBLOCKS_HASH: DEVBLOCKS_HASH_UNITS}
+DEVBLOCKS_OWN = {DEVBLOCKS_CURVE: DEVBLOCKS_CURVE_UNITS, DEVBLOCKS_HASH: DEVBLOCKS_HASH_UNITS,
+                 DEVBLOCKS_PAIR: DEVBLOCKS_PAIR_UNITS}
 
 
 def devblocks_units(build: str) -> list:
@@ -306,10 +315,10 @@ def devblocks_path(build: str, root: str = "") -> str:
 
 def devblocks_build_id(build: str = "64", root: str = "") -> str:
     """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
-    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py): sha256 (16 hex
+    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py, tests/test_gpu_pairing.py): sha256 (16 hex
     digits) over the harness sources, every header of charon_amd/csrc and the flags of that build --
     what its `db_build_id()` returns.  The block builds ("64", "128") hash every
-    tests/native/devblocks* file but the sources of the curve and hash harnesses; each of those two
+    tests/native/devblocks* file but the sources of the curve, hash and pair harnesses; each of those
     hashes its own sources, the shared devblocks*.h and the product sources its units compile
     themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
     import hashlib
@@ -490,8 +499,13 @@ def build_devblocks_hash(force: bool = False, verbose: bool = True) -> str:
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_HASH])[DEVBLOCKS_HASH]
 
 
+def build_devblocks_pair(force: bool = False, verbose: bool = True) -> str:
+    """The pair harness (tests/test_gpu_pairing.py), built and reused as build_devblocks' builds."""
+    return build_devblocks(force, verbose, builds=[DEVBLOCKS_PAIR])[DEVBLOCKS_PAIR]
+
+
 def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
-    """The block harnesses, the curve harness and the hash harness, their units compiled side by side"""
+    """The block harnesses and the curve, hash and pair harnesses, their units compiled side by side"""
     return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + list(DEVBLOCKS_OWN))
 
 

@@ -622,3 +622,114 @@ def msm_reference(points, coefs):
         total = B.g2_add(total, B.g2_mul(pt, a))
         total = B.g2_add(total, B.g2_mul(B.g2_neg(B.g2_psi(B.g2_psi(pt))), b))
     return total
+
+
+# ---- Miller loops (tests/native/devblocks_pair.hip, devblocks_vgroup.hip; tests/test_gpu_pairing.py) ----
+# The loop order comes from X_PARAM alone: bit 62 .. 0 of |x| below its top bit, a doubling per bit
+# and an addition after each set one.
+X_ABS = -B.X_PARAM
+MILLER_BITS = bin(X_ABS)[3:]
+N_LINES = len(MILLER_BITS) + MILLER_BITS.count("1")
+G1_NEG = B.g1_neg(B.G1_GEN)
+_CHAINS, _PAIRINGS, _POWS, _ATINV = {}, {}, {}, {}
+
+
+def miller_chain(Q):
+    """The affine chain of the oracle's miller_loop over Q: per line (kind, lambda, x_T, y_T), T the
+    point the line is taken at (the formulas are miller_loop's own), memoised"""
+    if Q in _CHAINS:
+        return _CHAINS[Q]
+    out, T = [], Q
+    for bit in MILLER_BITS:
+        xt, yt = T
+        lam = B.f2_mul(B.f2_mul(B.f2(3), B.f2_sqr(xt)), B.f2_inv(B.f2_mul(B.f2(2), yt)))
+        out.append(("dbl", lam, xt, yt))
+        x3 = B.f2_sub(B.f2_sub(B.f2_sqr(lam), xt), xt)
+        T = (x3, B.f2_sub(B.f2_mul(lam, B.f2_sub(xt, x3)), yt))
+        if bit == "1":
+            xt, yt = T
+            lam = B.f2_mul(B.f2_sub(Q[1], yt), B.f2_inv(B.f2_sub(Q[0], xt)))
+            out.append(("add", lam, xt, yt))
+            x3 = B.f2_sub(B.f2_sub(B.f2_sqr(lam), xt), Q[0])
+            T = (x3, B.f2_sub(B.f2_mul(lam, B.f2_sub(xt, x3)), yt))
+    assert len(out) == N_LINES
+    _CHAINS[Q] = out
+    return out
+
+
+def line_matches(line, step, at=None):
+    """Is the device line (a0, c1, c2) -- Fp2 field elements -- the oracle's line of `step` up to the
+    factor w^3 c2 (in Fp4: the final exponentiation removes it)?  c2 != 0, a0 = c2 (lambda x_T - y_T),
+    c1 = -c2 lambda.  at = (x_P, y_P): the line came evaluated, (a0, c1 x_P, c2 y_P)."""
+    a0, c1, c2 = line
+    if at is not None:
+        if at not in _ATINV:
+            _ATINV[at] = (B.fp_inv(at[0]), B.fp_inv(at[1]))
+        c1 = B.f2_mul(c1, (_ATINV[at][0], 0))
+        c2 = B.f2_mul(c2, (_ATINV[at][1], 0))
+    _, lam, xt, yt = step
+    if B.f2_is_zero(c2):
+        return False
+    return tuple(a0) == B.f2_mul(c2, B.f2_sub(B.f2_mul(lam, xt), yt)) and tuple(c1) == B.f2_neg(B.f2_mul(c2, lam))
+
+
+def miller_from_lines(*chains):
+    """The Miller value of evaluated lines (a0, a1, b1), N_LINES per chain, in the schedule X_PARAM
+    gives: f^2 in front of every doubling line but the first, then the line of every chain -- one
+    chain, or several sharing the squarings (a multi-Miller loop)"""
+    assert chains and all(len(c) == N_LINES for c in chains)
+    f, i = B.P12_ONE, 0
+
+    def step(f, i):
+        for c in chains:
+            f = B._p12_mul(f, line_poly(*c[i]))
+        return f
+    for k, bit in enumerate(MILLER_BITS):
+        if k:
+            f = B._p12_mul(f, f)
+        f, i = step(f, i), i + 1
+        if bit == "1":
+            f, i = step(f, i), i + 1
+    assert i == N_LINES
+    return f
+
+
+def pow3(f):
+    """f^FEXP3, memoised by value"""
+    key = tuple(f)
+    if key not in _POWS:
+        _POWS[key] = B._p12_pow(list(f), FEXP3)
+    return _POWS[key]
+
+
+def pairing3(Pt, Q):
+    """e(P, Q)^3 as the device computes it: the oracle's Miller value to the power FEXP3, memoised"""
+    if (Pt, Q) not in _PAIRINGS:
+        _PAIRINGS[(Pt, Q)] = pow3(B.miller_loop(Pt, Q))
+    return _PAIRINGS[(Pt, Q)]
+
+
+def eval_line(line, Pt):
+    """(a0, c1, c2) at P: (a0, c1 x_P, c2 y_P)"""
+    return line[0], B.f2_mul(line[1], (Pt[0], 0)), B.f2_mul(line[2], (Pt[1], 0))
+
+
+LINE_WORDS, F12_WORDS, HM_WORDS, MSG_WORDS = 72, 144, 52, 52 + 72 * N_LINES
+
+
+def line_of_words(w):
+    """(a0, a1, b1) as field elements and the six raw values of a LineEntry's 72 words"""
+    raw = [from_words(w[12 * k:12 * k + 12]) for k in range(6)]
+    v = [unmont(r) for r in raw]
+    return ((v[0], v[1]), (v[2], v[3]), (v[4], v[5])), raw
+
+
+def f12_of_words(w):
+    """the Fp12 element (oracle polynomial) and the twelve raw values of a stored value's 144 words
+    (three Fp4Entry: role k holds x.c0, x.c1, y.c0, y.c1)"""
+    raw = [from_words(w[12 * k:12 * k + 12]) for k in range(12)]
+    return raw_to_poly([tuple(raw[4 * k:4 * k + 4]) for k in range(3)]), raw
+
+
+def f12_words(c, upper=False):
+    return [x for lane in poly_to_raw(c, upper) for v in lane for x in words(v)]

@@ -67,6 +67,52 @@ struct DbDev {  // device buffers of one call, freed when it returns
     if (db_rc_) return db_rc_;                                          \
   } while (0)
 
+// The buffers of a call that has more than eight (the pair harness: a whole argument struct of the
+// product): device copies of host arrays -- a null array stays a null device pointer -- and the
+// in/out ones, uploaded as the caller filled them (a sentinel pattern) and copied back IN FULL by
+// fetch(), so that what a kernel must not write is visible to the caller.
+struct DbIo {
+  DbDev dev[4];
+  struct Out {
+    void *host, *devp;
+    size_t bytes;
+  } outs[12];
+  int n = 0, n_out = 0;
+  int in(void** out, const void* src, size_t bytes) {
+    *out = nullptr;
+    if (!src) return 0;
+    if (n >= 32) return DB_E_ARG;
+    return dev[n++ / 8].make(out, src, bytes);
+  }
+  int io(void** out, void* host, size_t bytes) {
+    if (host && n_out >= 12) return DB_E_ARG;
+    const int rc = in(out, host, bytes);
+    if (!rc && host) outs[n_out++] = {host, *out, bytes};
+    return rc;
+  }
+  // guard < 0: no guard byte (null); else a device byte of that value
+  int guard(const uint8_t** out, int g) {
+    const uint8_t b = (uint8_t)g;
+    return in((void**)out, g < 0 ? nullptr : &b, 1);
+  }
+  int fetch() {
+    for (int i = 0; i < n_out; i++)
+      if (outs[i].bytes && hipMemcpy(outs[i].host, outs[i].devp, outs[i].bytes, hipMemcpyDeviceToHost) != hipSuccess)
+        return DB_E_DOWNLOAD;
+    return 0;
+  }
+};
+#define DB_IN(io_, ptr, src, bytes)                                     \
+  do {                                                                  \
+    const int db_rc_ = (io_).in((void**)&(ptr), (src), (bytes));        \
+    if (db_rc_) return db_rc_;                                          \
+  } while (0)
+#define DB_IO(io_, ptr, host, bytes)                                    \
+  do {                                                                  \
+    const int db_rc_ = (io_).io((void**)&(ptr), (host), (bytes));       \
+    if (db_rc_) return db_rc_;                                          \
+  } while (0)
+
 // every message i = (off[i], len[i]) inside an uploaded buffer of msgs_bytes bytes
 static inline bool db_ranges_ok(int n, size_t msgs_bytes, const uint64_t* off, const uint32_t* len) {
   for (int i = 0; i < n; i++)

@@ -163,3 +163,59 @@ def test_hash_helpers():
     assert len(rnd) == 40 and squares >= 8 and len(rnd) - squares >= 8
     assert all((R.unmont(raw[0]), R.unmont(raw[1])) == u and max(raw) < 2 * R.P for _, u, raw in inputs)
     assert B.ec_is_on_curve(R.sswu_reference((0, 0)), B._Fp2Ops, B.B_G2)
+
+
+def _be(v):
+    return b"".join(int(c).to_bytes(48, "big") for c in v)
+
+
+def _hc_lines(hc, Q, ev):
+    """hc_line_chain28's 68 lines of Q (pair28.h's lazy-limb chain), as field elements"""
+    stored, lazy = ctypes.create_string_buffer(288 * R.N_LINES), ctypes.create_string_buffer(288 * R.N_LINES)
+    cnt = (ctypes.c_ulonglong * 2)()
+    assert hc.hc_line_chain28(_be(Q[0] + Q[1]), ev, stored, lazy, cnt) == 0
+    out = []
+    for buf in (stored.raw, lazy.raw):
+        v = [int.from_bytes(buf[48 * i:48 * i + 48], "big") for i in range(6 * R.N_LINES)]
+        out.append([((v[6 * j], v[6 * j + 1]), (v[6 * j + 2], v[6 * j + 3]), (v[6 * j + 4], v[6 * j + 5]))
+                    for j in range(R.N_LINES)])
+    return out
+
+
+def test_miller_reference_matches_host_lines(hc):
+    """tests/test_gpu_pairing.py's reference against the g++ build: the chain has X_PARAM's 68 steps;
+    every line of both host chains satisfies line_matches against it, unevaluated and evaluated at
+    -g1, and a changed line does not; the Python schedule over the host's evaluated lines, and the
+    oracle's own Miller value, give hc_pairing's e(-g1, Q)^3 after exponentiation."""
+    rng = random.Random(8)
+    Q = B.g2_mul(B.G2_GEN, rng.randrange(1, B.R))
+    chain = R.miller_chain(Q)
+    assert R.N_LINES == 68 and [s[0] for s in chain].count("dbl") == 63 and chain[0][2:] == Q
+    assert [s[0] for s in chain[:6]] == ["dbl", "add", "dbl", "dbl", "add", "dbl"]  # |x| = 0b1101...
+    neg = R.G1_NEG
+    for ev, at in ((0, None), (1, neg)):
+        for lines in _hc_lines(hc, Q, ev):
+            assert all(R.line_matches(l, s, at) for l, s in zip(lines, chain))
+            assert not R.line_matches(lines[1], chain[2], at)
+            a0, c1, c2 = lines[5]
+            assert not R.line_matches((a0, B.f2_add(c1, (1, 0)), c2), chain[5], at)
+            assert not R.line_matches(((0, 0), (0, 0), (0, 0)), chain[5], at)  # c2 = 0 matches nothing
+    stored, lazy = _hc_lines(hc, Q, 1)
+    unev = _hc_lines(hc, Q, 0)[1]
+    assert [R.eval_line(l, neg) for l in unev] == lazy
+    f = R.miller_from_lines(lazy)
+    want = R.pairing3(neg, Q)
+    assert f != B.miller_loop(neg, Q)  # the raw values differ by the lines' Fp4 factors
+    assert R.pow3(f) == want == R.pow3(R.miller_from_lines(stored))
+    o = ctypes.create_string_buffer(576)
+    assert hc.hc_pairing(B.g1_compress(neg), B.g2_compress(Q), o) == 0
+    assert R.lanes_tower_order(R.poly_to_lanes(want)) == [int.from_bytes(o.raw[48 * i:48 * i + 48], "big") for i in range(12)]
+    # several chains share the squarings: the product of the single loops
+    Q2 = B.g2_mul(B.G2_GEN, 77)
+    l2 = [R.eval_line(l, B.G1_GEN) for l in _hc_lines(hc, Q2, 0)[0]]
+    assert R.miller_from_lines(lazy, l2) == B._p12_mul(f, R.miller_from_lines(l2))
+    # the stored-word formats round-trip
+    w = R.f12_words(f, upper=True)
+    assert len(w) == R.F12_WORDS and R.f12_of_words(w)[0] == f and min(R.f12_of_words(w)[1]) >= B.P
+    lw = [x for c in lazy[3] for v in c for x in R.words(R.mont(v))]
+    assert len(lw) == R.LINE_WORDS and R.line_of_words(lw)[0] == lazy[3]

@@ -128,8 +128,8 @@ def test_curve_harness_id_is_its_own(tmp_path):
         shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
     curve = build.DEVBLOCKS_CURVE
     assert {u[0] for u in build.devblocks_units(curve)} == {"devblocks_curve.hip", "devblocks_msm.hip"}
-    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH] for u in build.devblocks_units(b)} == \
-        {f for f in mine if f.endswith(".hip")}  # every source is built
+    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR]
+            for u in build.devblocks_units(b)} == {f for f in mine if f.endswith(".hip")}  # every source is built
     cid = build.devblocks_build_id(curve, root=root)
     assert cid == build.devblocks_build_id(curve) and cid.startswith(build.DEVBLOCKS_PREFIX)
     blocks = {b: build.devblocks_build_id(b, root=root) for b in build.DEVBLOCKS_BUILDS}
@@ -211,4 +211,73 @@ def test_hash_harness_id_is_its_own(tmp_path):
         build.build_devblocks_all()
     finally:
         build.build_devblocks = real
-    assert sorted(seen["builds"]) == sorted(others + [hsh])
+    assert sorted(seen["builds"]) == sorted(others + [hsh, build.DEVBLOCKS_PAIR])
+
+
+def test_pair_harness_id_is_its_own(tmp_path):
+    """The pair harness (tests/native/devblocks_pair.hip, devblocks_vgroup.hip; tests/test_gpu_pairing.py)
+    on the same terms: its two sources, the shared devblocks.h, every csrc header and the product
+    sources its units compile themselves (pipeline.hip, vgroup.hip) change its id; an unrelated file or
+    another harness's source does not.  The other harnesses' ids do not move with a pair source,
+    pipeline.hip or vgroup.hip; all the ids differ; every devblocks*.hip belongs to exactly one
+    harness; build_devblocks_all builds it."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    pair = build.DEVBLOCKS_PAIR
+    assert pair == "pair" and pair in build.DEVBLOCKS_OWN
+    assert {u[0] for u in build.devblocks_units(pair)} == {"devblocks_pair.hip", "devblocks_vgroup.hip"}
+    assert len({u[2] for u in build.devblocks_units(pair)}) == len(build.devblocks_units(pair))  # one object each
+    assert build.DEVBLOCKS_PRODUCT_SOURCES[pair] == ["pipeline.hip", "vgroup.hip"]
+    # pipeline.hip sets its own HB_FAST_FPMUL and HB_ARG_LANES; vgroup.hip takes the default lanes: no such flag
+    assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(pair) for d in u[1])
+    assert build.devblocks_flags(pair) == []
+    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH]
+    every = others + [pair]
+    owner = {}
+    for b in every:  # every source in exactly one harness (the two block builds share theirs)
+        for src in {u[0] for u in build.devblocks_units(b)}:
+            owner.setdefault(src, set()).add("blocks" if b in build.DEVBLOCKS_BUILDS else b)
+    assert set(owner) == {f for f in mine if f.endswith(".hip")} and all(len(v) == 1 for v in owner.values())
+
+    def ids(which):
+        return {b: build.devblocks_build_id(b, root=root) for b in which}
+    pid = build.devblocks_build_id(pair, root=root)
+    assert pid == build.devblocks_build_id(pair) and pid.startswith(build.DEVBLOCKS_PREFIX)
+    assert len(set(ids(every).values())) == 5
+    for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
+                "charon_amd/csrc/vbatch.hip", "tests/native/hostcheck.cpp", "include/hipbls.h",
+                "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip",
+                "tests/native/devblocks_msm.hip", "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    assert build.devblocks_build_id(pair, root=root) == pid
+    before_others = ids(others)
+    for rel in ("tests/native/devblocks_pair.hip", "tests/native/devblocks_vgroup.hip", "charon_amd/csrc/pipeline.hip",
+                "charon_amd/csrc/vgroup.hip"):
+        before = build.devblocks_build_id(pair, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(pair, root=root) != before, rel
+        assert ids(others) == before_others, rel
+    for rel in ("tests/native/devblocks.h", "charon_amd/csrc/pair28.h", "charon_amd/csrc/lines.h", "charon_amd/csrc/layout.h",
+                "charon_amd/csrc/fp.h"):
+        before = build.devblocks_build_id(pair, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(pair, root=root) != before, rel
+    path = build.devblocks_path(pair)
+    assert os.path.basename(path) == "libhbls_devblockspair.so"
+    if os.path.exists(path):  # what build() left in the tree is this tree's
+        assert build.embedded_devblocks_id(path) == build.devblocks_build_id(pair)
+    seen = {}
+    real = build.build_devblocks
+    try:
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: seen.setdefault("builds", list(builds))
+        build.build_devblocks_all()
+    finally:
+        build.build_devblocks = real
+    assert pair in seen["builds"] and sorted(seen["builds"]) == sorted(every)
