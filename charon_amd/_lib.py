@@ -39,6 +39,7 @@ EXPORTS = (
     "hbls_single_max", "hbls_dec_pair_max", "hbls_tune", "hbls_verify_batch_first_error",
     "hbls_verify_device_first_error", "hbls_key_learn_stats", "hbls_key_wide_stats",
     "hbls_slot_select_device", "hbls_slot_select_stats", "hbls_subgroup_batch", "hbls_subgroup_batch_stats",
+    "hbls_slot_select_batch",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -142,6 +143,7 @@ def _declare(lib):
         "hbls_slot_device": ([ctypes.POINTER(HblsSlot), P], ctypes.c_int),
         "hbls_slot_select_device": ([ctypes.POINTER(HblsSlot), U32, P, P, P], ctypes.c_int),
         "hbls_slot_select_stats": ([P, SZ], ctypes.c_int),
+        "hbls_slot_select_batch": ([P, P, P, P, P, SZ, P, P, P, SZ, P, U32, P, P, P, P, P, P], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
         "hbls_sync": ([P], ctypes.c_int),
         "hbls_status_bitmap": ([P, SZ, P, P], ctypes.c_int),

@@ -203,6 +203,47 @@ def build_taselcheck(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+SLOTHOSTCHECK_PREFIX = "hbls-slothostcheck:"
+SLOTHOSTCHECK_HEADERS = ("hslot.h", "hgroup.h", "msgtable.h", "tasel.h")
+
+
+def slothostcheck_build_id(root: str = "") -> str:
+    """The id embedded in the host-buffer duty's harness (tests/native/slothostcheck.cpp,
+    `hs_build_id()`): sha256 over its source, the headers it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "slothostcheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in SLOTHOSTCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return SLOTHOSTCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_slothostcheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_slothostcheck.so (tests/test_hslot.py): the host plan of
+    hbls_slot_select_batch and its matching rule on the CPU; test-only.  Reused when its embedded id
+    equals the tree's, as build_hostcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "slothostcheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_slothostcheck.so")
+    bid = slothostcheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-slothostcheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DHS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
 SUBGCHECK_PREFIX = "hbls-subgcheck:"
 SUBGCHECK_HEADERS = ("subgbatch.h", "sha256.h", "hd.h", "vplan.h")
 
@@ -541,7 +582,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_widecheck, build_taselcheck, build_subgcheck, build_devblocks_all, build_widedev,
+    for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_subgcheck, build_devblocks_all, build_widedev,
                build_subgdev):
         try:
             fn(force, verbose)

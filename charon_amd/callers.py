@@ -10,6 +10,8 @@ calls.  INTEGRATION.md §3 gives the same changes as Go patches.
   sigagg_slot                     parsigex.go:93-98 -> parsigdb/memory.go:198-225 -> sigagg.go:84-117 for one duty
                                   in ONE device call (hbls_slot_select_device): verify, pick verified members,
                                   aggregate, verify the aggregates
+  sigagg_slot_host                the same duty through the host-buffer call the Go shim binds (hbls_slot_select_batch),
+                                  under parsigdb's matching rule (memory.go:149-160, 197-225); numpy only
   validatorapi_submit             core/validatorapi/validatorapi.go:284-306 + verifyPartialSig :1213-1229
   lock_verify_signatures          cluster/lock.go:151-197 (VerifyAggregate over every pubshare, :185)
   dkg_agg_deposit_data            dkg/dkg.go:820-899 (n x Verify + ThresholdAggregate + Verify per DV)
@@ -246,6 +248,75 @@ def sigagg_slot(impl_or_L, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
         if ast_h[k] != OK:
             raise _wrap("threshold aggregate", "aggregate signature verification failed: " + _verr(int(ast_h[k])))
     return statuses, {pk: bytes(out_h[k]) for k, pk in enumerate(keys)}, used
+
+
+def sigagg_slot_host(impl_or_L, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
+                     pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], sets: Mapping[bytes, Sequence[ParSig]]):
+    """sigagg_slot through the host-buffer entry point the Go shim calls (hbls_slot_select_batch):
+    the same contract -- arguments, the (statuses, aggregates, used) it returns, the errors and their
+    order -- over numpy arrays only, with no torch and no device memory of the caller's.
+
+    One difference follows from the entry point: its members follow the ParSigDB's matching rule
+    (parsigdb/memory.go:197-225), which groups a validator's stored partials by signing root and
+    fires for the first root to hold `threshold` of them.  A validator whose partials span several
+    roots is therefore aggregated over the winning root, or fails with "require threshold
+    signatures" when no root gets there; the "partial signatures over different signing roots" error
+    of sigagg_slot cannot arise here.
+    impl_or_L: a charon_amd.tbls.HIPBLS or the loaded library."""
+    import ctypes
+
+    import numpy as np
+
+    from . import _lib
+    L = getattr(impl_or_L, "_L", impl_or_L)
+    if not sets:
+        raise CallerError("empty partial signed data set")
+    keys = list(sets)
+    pks, sigs, msgs, idx, goff = [], [], [], [], [0]
+    for pk in keys:
+        for ps in sets[pk]:
+            if len(ps.signature) != 96:
+                raise _wrap("threshold aggregate", "signature from core: " + _LEN_ERR)
+            shares = pubshares_by_key.get(pk)
+            if shares is None or ps.share_idx not in shares:
+                raise _wrap("invalid partial signature",
+                            "unknown pubkey, not part of cluster lock" if shares is None else "invalid shareIdx")
+            pks.append(shares[ps.share_idx])
+            sigs.append(ps.signature)
+            msgs.append(ps.signing_root)
+            idx.append(ps.share_idx)
+        goff.append(len(pks))
+    n, V = len(pks), len(keys)
+
+    def u8(chunks):
+        return np.frombuffer(b"".join(chunks) or bytes(1), dtype=np.uint8).copy()
+
+    a_pks, a_sigs, a_msgs, a_dv = u8(pks), u8(sigs), u8(msgs), u8([dv_pubkeys[pk] for pk in keys])
+    a_len = np.asarray([len(m) for m in msgs] or [0], dtype=np.uint32)
+    a_off = (np.cumsum(a_len, dtype=np.uint64) - a_len).astype(np.uint64)
+    a_cand = np.arange(max(n, 1), dtype=np.uint32)
+    a_idx = np.asarray(idx or [0], dtype=np.int64)
+    a_goff = np.asarray(goff, dtype=np.uint32)
+    vst = np.full(max(n, 1), 255, dtype=np.uint8)
+    chosen = np.zeros(V * threshold, dtype=np.uint32)
+    count = np.zeros(V, dtype=np.uint32)
+    out = np.zeros(V * 96, dtype=np.uint8)
+    tst, ast = np.full(V, 255, dtype=np.uint8), np.full(V, 255, dtype=np.uint8)
+    p = lambda x: ctypes.c_void_p(x.ctypes.data)  # noqa: E731
+    if L.hbls_slot_select_batch(p(a_pks), p(a_sigs), p(a_msgs), p(a_off), p(a_len), n, p(a_cand), p(a_idx), p(a_goff), V,
+                                p(a_dv), threshold, p(vst), p(chosen), p(count), p(out), p(tst), p(ast)) != 0:
+        raise _lib.HipBlsRuntimeError("hipbls: " + L.hbls_last_error().decode(errors="replace"))
+    chosen, out = chosen.reshape(V, threshold), out.reshape(V, 96)
+    statuses = {pk: [int(x) for x in vst[goff[k]:goff[k + 1]]] for k, pk in enumerate(keys)}
+    used = {pk: [int(c) - goff[k] for c in chosen[k, :count[k]]] for k, pk in enumerate(keys)}
+    for k in range(V):
+        if tst[k] == _lib.UNCHECKED:
+            raise _wrap("threshold aggregate", "require threshold signatures")
+        if tst[k] != OK:
+            raise _wrap("threshold aggregate", status_error("threshold_aggregate", int(tst[k])))
+        if ast[k] != OK:
+            raise _wrap("threshold aggregate", "aggregate signature verification failed: " + _verr(int(ast[k])))
+    return statuses, {pk: bytes(out[k]) for k, pk in enumerate(keys)}, used
 
 
 def validatorapi_submit(impl, pubshare_of: Mapping[bytes, bytes],

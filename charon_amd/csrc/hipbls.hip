@@ -11,6 +11,7 @@
 #include "../../include/hipbls.h"
 #include "coalesce.h"
 #include "hgroup.h"
+#include "hslot.h"
 #include "msgtable.h"
 #include "vplan.h"
 
@@ -355,7 +356,13 @@ struct Ws {
 };
 
 // host-call staging buffers (inputs and outputs of the host-buffer entry points)
-enum IoId { I_PK, I_SIG, I_MSG, I_OFF, I_LEN, I_MIDX, I_HM, I_STAT, I_IDX, I_GOFF, I_OUT, I_SK, I_VGOFF, I_HM2, I_COUNT };
+enum IoId {
+  I_PK, I_SIG, I_MSG, I_OFF, I_LEN, I_MIDX, I_HM, I_STAT, I_IDX, I_GOFF, I_OUT, I_SK, I_VGOFF, I_HM2,
+  // hbls_slot_select_batch: the candidates, their share indices and offsets, the DV keys; the members, their counts,
+  // the aggregates and the two statuses per group
+  I_CAND, I_CIDX, I_SGOFF, I_DVPK, I_CHOSEN, I_TACNT, I_TAOUT, I_TAST, I_AGGST,
+  I_COUNT
+};
 
 constexpr int N_WS_MAX = 8;  // workspace sets per device: HBLS_WS_SETS (default 3)
 int g_ws_sets = 3;
@@ -1933,18 +1940,20 @@ struct HcLease {
 
 // Run fn(dev, shard) for each device's shard of n_units concurrently (one host thread per extra
 // device); a failing shard's error is reported with its device.  fn locks the device itself.
+// fan_out_k: fn also learns which shard it runs, k of nd.
 using ShardFn = std::function<int(Dev&, size_t, size_t)>;
-int fan_out(size_t n_units, const ShardFn& fn) {
+using ShardKFn = std::function<int(Dev&, size_t, size_t, size_t, size_t)>;
+int fan_out_k(size_t n_units, const ShardKFn& fn) {
   const std::vector<Dev*> ds = devs();
   const size_t nd = std::min(ds.size(), std::max<size_t>(n_units, 1));
-  if (nd <= 1) return fn(*ds[0], 0, n_units);
+  if (nd <= 1) return fn(*ds[0], 0, 1, 0, n_units);
   std::vector<int> rc(nd, 0);
   std::vector<std::string> errs(nd);
   std::vector<std::thread> th;
   for (size_t k = 0; k < nd; k++) {
     const size_t b = n_units * k / nd, e = n_units * (k + 1) / nd;
     th.emplace_back([&, k, b, e]() {
-      rc[k] = fn(*ds[k], b, e);
+      rc[k] = fn(*ds[k], k, nd, b, e);
       if (rc[k]) errs[k] = g_err;
     });
   }
@@ -1952,6 +1961,9 @@ int fan_out(size_t n_units, const ShardFn& fn) {
   for (size_t k = 0; k < nd; k++)
     if (rc[k]) return set_err("device " + std::to_string(ds[k]->ord) + ": " + errs[k]);
   return 0;
+}
+int fan_out(size_t n_units, const ShardFn& fn) {
+  return fan_out_k(n_units, [&fn](Dev& d, size_t, size_t, size_t b, size_t e) -> int { return fn(d, b, e); });
 }
 
 // fan_out with the device locked throughout (the small entry points)
@@ -2720,6 +2732,299 @@ int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* go
   return 0;
 }
 
+// The core of hbls_slot_select_device and hbls_slot_select_batch: hbls_slot_device with
+// verified-member selection, over device buffers (a: as the device entry takes it, checked by the
+// caller, who holds d.mu) on stream s.  mode: how members are picked (tasel.h TASEL_MODE_*).
+// behind_default: the device entry, whose caller may have prepared its buffers on the default stream;
+// it takes the next workspace set for phase 4.  The host entry keeps phase 4 on the set of phases
+// 1-3 (what HBLS_WS_SETS=1 does to the device entry): its calls come from several threads, one set
+// each then holds a whole call, and no call enqueues onto streams still busy with another call's work
+// (measured: that enqueue held the calling thread, and the device lock, until the other call ended).
+// Four phases on the stream, each behind the one before (the aggregation needs the verdicts, the
+// second verification the aggregates):
+//   1. hash, and verify the partials without a fold (workspace set w: the decompressed partials stay)
+//   2. select each group's members and put the groups in class order (threshold.hip k_ta_select ...)
+//   3. ThresholdAggregate over the chosen members through src into the retained points (ta_tail)
+//   4. verify the aggregates under the DV keys: a second verify_pipeline on the next workspace set,
+//      one item per group, handed the affine aggregates in place of signature bytes (pre_sig); a
+//      group without an aggregate is an item with a bad signature status, which costs no pairing
+thread_local double g_core_marks[3];  // HBLS_HOST_TIMING: phase 1, phases 2-3 and phase 4 enqueued
+int slot_select_core(Dev& d, hipStream_t s, const hbls_slot& a, uint32_t threshold, uint32_t* chosen,
+                     uint32_t* ta_count, uint32_t mode, bool behind_default) {
+  const size_t ng = a.n_groups, t = threshold;
+  g_core_marks[0] = g_core_marks[1] = g_core_marks[2] = 0;
+  Ws& w = ws_acquire(d, s);
+  if (behind_default && s) {  // behind what the default stream holds now, as hbls_slot_device
+    HCHK(hipEventRecord(w.ev_dflt, nullptr));
+    HCHK(hipStreamWaitEvent(s, w.ev_dflt, 0));
+  }
+  // phase 1
+  bool defer = false;
+  if (a.n) {
+    HCHK(hipEventRecord(w.ev_fork, s));
+    hipStream_t sh = w.side[2];
+    HCHK(hipStreamWaitEvent(sh, w.ev_fork, 0));
+    defer = defer_lines(a.n_vgroups, a.n_msgs);
+    if (hash_messages(d, a.msgs, a.msg_off, a.msg_len, a.n_msgs, (MsgEntry*)a.hm, sh, !defer)) return -1;
+    HCHK(hipEventRecord(w.ev_side[2], sh));
+  }
+  TaFold tables{};
+  tables.pk_table = (const G1AEntry*)a.pk_table;
+  tables.pk_table_st = a.pk_table_st;
+  VerifyCall vc;
+  vc.pks = a.pks;
+  vc.sigs = a.sigs;
+  vc.msg_idx = a.msg_idx;
+  vc.hm = (const MsgEntry*)a.hm;
+  vc.n = a.n;
+  vc.grp_off = a.vgrp_off;
+  vc.n_groups = a.n_vgroups;
+  vc.status = a.vstatus;
+  vc.s = s;
+  vc.device_entry = true;
+  vc.hm_ready = w.ev_side[2];
+  vc.fold = a.pk_table ? &tables : nullptr;
+  vc.defer_hm = (MsgEntry*)a.hm;
+  vc.defer_msgs = defer ? a.n_msgs : 0;
+  if (a.n) {
+    if (verify_pipeline(d, w, vc)) return -1;
+    HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  }
+  if (!ng) return ws_release(w, s);
+  if (host_timing()) g_core_marks[0] = now_ms();
+  // phase 2
+  const bool first_use = d.sel_ctr.p == nullptr;
+  uint64_t* ctr;
+  if (ensure_buf(d.sel_ctr, SEL_COUNTERS * sizeof(uint64_t), (void**)&ctr)) return -1;
+  if (first_use) {  // once per device, and complete before any stream's kernel counts
+    HCHK(hipMemset(ctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
+    HCHK(hipStreamSynchronize(nullptr));
+  }
+  TaSelectArgs sa{};
+  uint8_t *pout, *pst, *ast;
+  HmEntry *ppt, *apt;
+  if (wsbuf(w, W_SELCIDX, ng * t, &sa.cidx) || wsbuf(w, W_SELKEY, ng, &sa.key) || wsbuf(w, W_SELSTATE, ng, &sa.state) ||
+      wsbuf(w, W_SELGMSG, ng, &sa.gmsg) || wsbuf(w, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
+      wsbuf(w, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w, W_SELPERM, ng, &sa.perm) ||
+      wsbuf(w, W_SELPMEM, ng * t, &sa.pmem) || wsbuf(w, W_SELPIDX, ng * t, &sa.pidx) ||
+      wsbuf(w, W_SELPGOFF, ng + 1, &sa.pgoff) || wsbuf(w, W_SELPOUT, 96 * ng, &pout) || wsbuf(w, W_SELPST, ng, &pst) ||
+      wsbuf(w, W_SELPPT, ng, &ppt) || wsbuf(w, W_SELAPT, ng, &apt) || wsbuf(w, W_SELAST, ng, &ast))
+    return -1;
+  sa.cur = sa.hist + TASEL_KEYS;
+  sa.vstatus = a.vstatus;
+  sa.msg_idx = a.msg_idx;
+  sa.n = (uint32_t)a.n;
+  sa.src = a.ta_src;
+  sa.idx = a.ta_idx;
+  sa.grp_off = a.grp_off;
+  sa.n_groups = (uint32_t)ng;
+  sa.n_cand = (uint32_t)a.n_ta_partials;
+  sa.t = threshold;
+  sa.mode = mode;
+  sa.chosen = chosen;
+  sa.ta_count = ta_count;
+  sa.ctr = ctr;
+  HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
+  TIMED(d, "k_ta_select", s, launch_ta_select(sa, s));
+  TaScatterArgs sc{};
+  sc.n_groups = (uint32_t)ng;
+  sc.state = sa.state;
+  sc.ta_out = a.ta_out;
+  sc.ta_status = a.ta_status;
+  sc.ctr = ctr;
+  if (!a.n) {  // no partial: no group has a member
+    TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+    TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a.ta_status, (uint32_t)ng, a.agg_vstatus, s));
+    return ws_release(w, s);
+  }
+  TIMED(d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
+  TIMED(d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
+  // phase 3
+  const uint8_t* sdone = nullptr;
+  if (ta_tail(d, w, vc.vsig, sa.pmem, vc.vsigst, sa.pidx, sa.pgoff, ng, ng * t, 0, pout, pst, ppt, s, nullptr, nullptr,
+              &sdone))
+    return -1;
+  sc.perm = sa.perm;
+  sc.pout = pout;
+  sc.pstatus = pst;
+  sc.ppt = ppt;
+  sc.sdone = sdone;
+  sc.rows16 = (((uintptr_t)a.ta_out | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
+  sc.agg_pt = apt;
+  sc.agg_st = ast;
+  TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+  if (host_timing()) g_core_marks[1] = now_ms();
+  // phase 4.  The messages' lines: computed by phase 1 unless it deferred them; then this pass
+  // defers them too where its plan can (the batched sizes), else they are computed first
+  Ws& w2 = behind_default ? ws_acquire(d, s) : w;
+  size_t defer2 = 0;
+  if (defer) {
+    if (vp_bfe(VerifyShape{ng, ng, 0, false, false, 0, d.n_cu, false},
+               VerifyKnobs{g_gcap.load(), g_fbcap.load(), g_fe_batch_min.load(), g_slot_msm_min.load(),
+                           g_rlc_lanes.load(), g_adaptive.load()}))
+      defer2 = a.n_msgs;
+    else
+      TIMED(d, "k_lines_msg", s, launch_lines_msg((MsgEntry*)a.hm, (uint32_t)a.n_msgs, s));
+  }
+  TaFold tables2{};
+  tables2.pk_table = (const G1AEntry*)a.dv_pk_table;
+  tables2.pk_table_st = a.dv_pk_table_st;
+  VerifyCall v2;
+  v2.pks = a.dv_pks;
+  v2.pre_sig = apt;
+  v2.pre_sigst = ast;
+  v2.msg_idx = sa.gmsg;
+  v2.hm = (const MsgEntry*)a.hm;
+  v2.n = ng;
+  v2.n_groups = ng;
+  v2.status = a.agg_vstatus;
+  v2.s = s;
+  v2.fold = a.dv_pk_table ? &tables2 : nullptr;
+  v2.defer_hm = (MsgEntry*)a.hm;
+  v2.defer_msgs = defer2;
+  if (verify_pipeline(d, w2, v2)) return -1;
+  if (host_timing()) g_core_marks[2] = now_ms();
+  TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a.ta_status, (uint32_t)ng, a.agg_vstatus, s));
+  if (ws_release(w, s)) return -1;
+  return &w2 == &w ? 0 : ws_release(w2, s);
+}
+
+// hbls_slot_select_batch: one duty from host buffers to aggregates (hslot.h is the plan).  The
+// aggregation groups are sharded over the devices; each shard plans on the host without the device
+// lock, uploads on its context's stream, runs slot_select_core under the matching rule, and waits
+// for that stream only.  A shard that is the whole call uploads the caller's keys and signatures as
+// they are, plans beside that transfer, and reorders them on the device (gather_items /
+// scatter_status, as verify_host and verify_large); several shards copy their items on the host.
+// Nothing is entered into the decompressed-signature cache: the aggregation reads the partials the
+// verification left in its workspace.
+int slot_select_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                     const uint32_t* msg_len, size_t n, const uint32_t* cand, const int64_t* cand_idx,
+                     const uint32_t* grp_off, size_t n_groups, const uint8_t* dv_pks, uint32_t threshold,
+                     uint8_t* vstatus, uint32_t* chosen, uint32_t* ta_count, uint8_t* ta_out, uint8_t* ta_status,
+                     uint8_t* agg_vstatus) {
+  const double t_start = now_ms();
+  const size_t t = threshold;
+  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
+  std::vector<uint8_t> listed;  // several shards: which partials some group lists
+  if (slot_shards(devs().size(), n_groups) > 1) listed = slot_listed(cand + grp_off[0], grp_off[n_groups] - grp_off[0], n);
+  return fan_out_k(n_groups, [&](Dev& d, size_t k, size_t nd, size_t gb, size_t ge) -> int {
+    HcLease hcs(d);
+    Hc& h = *hcs.h[0];
+    if (nd > 1 && listed.size() != n) return set_err("hbls_slot_select_batch: the devices changed during the call");
+    std::unique_lock<std::mutex> lk(d.mu, std::defer_lock);
+    // a shard that is the whole call: the caller's keys and signatures go up as they are, the first
+    // work on the context's stream, and the plan is made beside that transfer (as verify_large)
+    uint8_t *rpk = nullptr, *rsig = nullptr;
+    if (nd == 1) {
+      lk.lock();
+      if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+      if (upload(d, I_PK, pks, 48 * n, &rpk, &h) || upload(d, I_SIG, sigs, 96 * n, &rsig, &h)) return -1;
+      lk.unlock();
+    }
+    SlotShard sh;
+    const unsigned hw = std::thread::hardware_concurrency();
+    slot_plan_shard(msgs, msg_off, msg_len, n, cand, grp_off, gb, ge, k, nd, listed, gmax,
+                    nd == 1 && n >= (1u << 16) && hw >= 4 ? (hw >= 8 ? 8u : 4u) : 0u, sh);
+    const size_t m = sh.m(), ng = ge - gb, nm = sh.tab.len.size(), nc = sh.cand.size();
+    std::vector<uint8_t> hpk, hsig;
+    if (!sh.whole) {  // the shard's keys and signatures in verification order
+      hpk.resize(48 * m);
+      hsig.resize(96 * m);
+      for (size_t q = 0; q < m; q++) {
+        memcpy(&hpk[48 * q], pks + 48ull * sh.order[q], 48);
+        memcpy(&hsig[96 * q], sigs + 96ull * sh.order[q], 96);
+      }
+    }
+    const double t_prep = now_ms();
+    lk.lock();
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    const double t_locked = now_ms();
+    hbls_slot a{};
+    uint8_t *dmsg, *dpk, *dsig, *ddv, *dst_out = nullptr;
+    uint64_t* doff;
+    uint32_t *dlen, *dmidx, *dvgoff, *dcand, *dgoff, *dord = nullptr;
+    int64_t* dcidx;
+    void *hm, *pst, *pchosen, *pcount, *pout, *ptst, *past;
+    if (!sh.whole && (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)))
+      return -1;
+    // everything else through the context's pinned staging: a pageable copy queued behind the call's
+    // kernels, or beside another call's, holds the calling thread (Hc::pin)
+    PinnedUploads up;
+    up.add(I_MSG, sh.tab.bytes.data(), sh.tab.bytes.size(), &dmsg);
+    up.add(I_OFF, sh.tab.off.data(), nm, &doff);
+    up.add(I_LEN, sh.tab.len.data(), nm, &dlen);
+    if (sh.whole) up.add(I_IDX, sh.order.data(), m, &dord);
+    up.add(I_MIDX, sh.vg.midx.data(), m, &dmidx);
+    up.add(I_VGOFF, sh.vgoff.data(), sh.vgoff.size(), &dvgoff);
+    up.add(I_CAND, sh.cand.data(), nc, &dcand);
+    up.add(I_CIDX, ng ? cand_idx + grp_off[gb] : (const int64_t*)nullptr, nc, &dcidx);
+    up.add(I_SGOFF, sh.goff.data(), sh.goff.size(), &dgoff);
+    up.add(I_DVPK, ng ? dv_pks + 48 * gb : (const uint8_t*)nullptr, 48 * ng, &ddv);
+    if (upload_pinned(d, h, up) || ensure_buf(h.io[I_HM], nm * sizeof(MsgEntry), &hm) || ensure_buf(h.io[I_STAT], m, &pst) ||
+        ensure_buf(h.io[I_CHOSEN], ng * t * sizeof(uint32_t), &pchosen) ||
+        ensure_buf(h.io[I_TACNT], ng * sizeof(uint32_t), &pcount) || ensure_buf(h.io[I_TAOUT], 96 * ng, &pout) ||
+        ensure_buf(h.io[I_TAST], ng, &ptst) || ensure_buf(h.io[I_AGGST], ng, &past))
+      return -1;
+    if (sh.whole) {  // verification order on the device
+      void *p1, *p2;
+      if (ensure_buf(h.io[I_OUT], 144 * m, &p1) || ensure_buf(h.io[I_HM2], m, &p2)) return -1;
+      dpk = (uint8_t*)p1;
+      dsig = dpk + 48 * m;
+      dst_out = (uint8_t*)p2;
+      if (gather_items(rpk, rsig, dord, m, dpk, dsig, h.s)) return -1;
+    }
+    a.msgs = dmsg;
+    a.msg_off = doff;
+    a.msg_len = dlen;
+    a.n_msgs = nm;
+    a.hm = hm;
+    a.pks = dpk;
+    a.sigs = dsig;
+    a.msg_idx = dmidx;
+    a.n = m;
+    a.vgrp_off = dvgoff;
+    a.n_vgroups = sh.vg.n_groups();
+    a.vstatus = (uint8_t*)pst;
+    a.ta_src = dcand;
+    a.ta_idx = dcidx;
+    a.grp_off = dgoff;
+    a.n_groups = ng;
+    a.n_ta_partials = nc;
+    a.ta_out = (uint8_t*)pout;
+    a.ta_status = (uint8_t*)ptst;
+    a.dv_pks = ddv;
+    a.agg_vstatus = (uint8_t*)past;
+    const double t_up = now_ms();
+    if (slot_select_core(d, h.s, a, threshold, (uint32_t*)pchosen, (uint32_t*)pcount, TASEL_MODE_MATCHING, false)) return -1;
+    if (sh.whole && scatter_status(a.vstatus, dord, m, dst_out, h.s)) return -1;
+    lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+    const double t_enq = now_ms();
+    std::vector<uint8_t> hst;
+    if (sh.whole) {
+      if (m) HCHK(hipMemcpyAsync(vstatus, dst_out, m, hipMemcpyDeviceToHost, h.s));
+    } else if (m) {
+      hst.resize(m);
+      HCHK(hipMemcpyAsync(hst.data(), a.vstatus, m, hipMemcpyDeviceToHost, h.s));
+    }
+    if (ng) {
+      HCHK(hipMemcpyAsync(chosen + gb * t, pchosen, ng * t * sizeof(uint32_t), hipMemcpyDeviceToHost, h.s));
+      HCHK(hipMemcpyAsync(ta_count + gb, pcount, ng * sizeof(uint32_t), hipMemcpyDeviceToHost, h.s));
+      HCHK(hipMemcpyAsync(ta_out + 96 * gb, pout, 96 * ng, hipMemcpyDeviceToHost, h.s));
+      HCHK(hipMemcpyAsync(ta_status + gb, ptst, ng, hipMemcpyDeviceToHost, h.s));
+      HCHK(hipMemcpyAsync(agg_vstatus + gb, past, ng, hipMemcpyDeviceToHost, h.s));
+    }
+    HCHK(hipStreamSynchronize(h.s));
+    for (size_t q = 0; q < hst.size(); q++) vstatus[sh.order[q]] = hst[q];
+    slot_chosen_to_caller(sh, chosen + gb * t, ng * t);
+    if (host_timing())
+      fprintf(stderr, "hbls slot_select_host shard %zu/%zu n=%zu groups=%zu: plan %.2f ms, lock wait %.2f, enqueue+upload "
+              "%.2f (uploads %.2f, verify %.2f, select+aggregate %.2f, aggregates' verify %.2f), device %.2f\n", k, nd, m, ng,
+              t_prep - t_start, t_locked - t_prep, t_enq - t_locked, t_up - t_locked, g_core_marks[0] - t_up,
+              g_core_marks[1] - g_core_marks[0], g_core_marks[2] - g_core_marks[1], now_ms() - t_enq);
+    return 0;
+  });
+}
+
 // ---------------------------------------------------------------------------------------
 // RCCL: one communicator per process (one GPU each) for the exchange of slot results
 // ---------------------------------------------------------------------------------------
@@ -3345,14 +3650,7 @@ int hbls_slot_device(const hbls_slot* a, void* stream) {
   return ws_release(w, s);
 }
 
-// hbls_slot_device with verified-member selection.  Four phases on the caller's stream, each behind
-// the one before (the aggregation needs the verdicts, the second verification the aggregates):
-//   1. hash, and verify the partials without a fold (workspace set w: the decompressed partials stay)
-//   2. select each group's members and put the groups in class order (threshold.hip k_ta_select ...)
-//   3. ThresholdAggregate over the chosen members through src into the retained points (ta_tail)
-//   4. verify the aggregates under the DV keys: a second verify_pipeline on the next workspace set,
-//      one item per group, handed the affine aggregates in place of signature bytes (pre_sig); a
-//      group without an aggregate is an item with a bad signature status, which costs no pairing
+// hbls_slot_device with verified-member selection: slot_select_core with ta_select
 int hbls_slot_select_device(const hbls_slot* a, uint32_t threshold, uint32_t* chosen, uint32_t* ta_count,
                             void* stream) {
   Dev* d;
@@ -3372,136 +3670,35 @@ int hbls_slot_select_device(const hbls_slot* a, uint32_t threshold, uint32_t* ch
       (a->dv_pk_table != nullptr) != (a->dv_pk_table_st != nullptr))
     return set_err("hbls_slot_select_device: a key table needs its status array");
   std::lock_guard<std::mutex> lk(d->mu);
-  Ws& w = ws_acquire(*d, s);
-  if (s) {  // behind what the default stream holds now, as hbls_slot_device
-    HCHK(hipEventRecord(w.ev_dflt, nullptr));
-    HCHK(hipStreamWaitEvent(s, w.ev_dflt, 0));
-  }
-  // phase 1
-  bool defer = false;
-  if (a->n) {
-    HCHK(hipEventRecord(w.ev_fork, s));
-    hipStream_t sh = w.side[2];
-    HCHK(hipStreamWaitEvent(sh, w.ev_fork, 0));
-    defer = defer_lines(a->n_vgroups, a->n_msgs);
-    if (hash_messages(*d, a->msgs, a->msg_off, a->msg_len, a->n_msgs, (MsgEntry*)a->hm, sh, !defer)) return -1;
-    HCHK(hipEventRecord(w.ev_side[2], sh));
-  }
-  TaFold tables{};
-  tables.pk_table = (const G1AEntry*)a->pk_table;
-  tables.pk_table_st = a->pk_table_st;
-  VerifyCall vc;
-  vc.pks = a->pks;
-  vc.sigs = a->sigs;
-  vc.msg_idx = a->msg_idx;
-  vc.hm = (const MsgEntry*)a->hm;
-  vc.n = a->n;
-  vc.grp_off = a->vgrp_off;
-  vc.n_groups = a->n_vgroups;
-  vc.status = a->vstatus;
-  vc.s = s;
-  vc.device_entry = true;
-  vc.hm_ready = w.ev_side[2];
-  vc.fold = a->pk_table ? &tables : nullptr;
-  vc.defer_hm = (MsgEntry*)a->hm;
-  vc.defer_msgs = defer ? a->n_msgs : 0;
-  if (a->n) {
-    if (verify_pipeline(*d, w, vc)) return -1;
-    HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
-  }
-  if (!ng) return ws_release(w, s);
-  // phase 2
-  const bool first_use = d->sel_ctr.p == nullptr;
-  uint64_t* ctr;
-  if (ensure_buf(d->sel_ctr, SEL_COUNTERS * sizeof(uint64_t), (void**)&ctr)) return -1;
-  if (first_use) {  // once per device, and complete before any stream's kernel counts
-    HCHK(hipMemset(ctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
-    HCHK(hipStreamSynchronize(nullptr));
-  }
-  TaSelectArgs sa{};
-  uint8_t *pout, *pst, *ast;
-  HmEntry *ppt, *apt;
-  if (wsbuf(w, W_SELCIDX, ng * t, &sa.cidx) || wsbuf(w, W_SELKEY, ng, &sa.key) || wsbuf(w, W_SELSTATE, ng, &sa.state) ||
-      wsbuf(w, W_SELGMSG, ng, &sa.gmsg) || wsbuf(w, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
-      wsbuf(w, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w, W_SELPERM, ng, &sa.perm) ||
-      wsbuf(w, W_SELPMEM, ng * t, &sa.pmem) || wsbuf(w, W_SELPIDX, ng * t, &sa.pidx) ||
-      wsbuf(w, W_SELPGOFF, ng + 1, &sa.pgoff) || wsbuf(w, W_SELPOUT, 96 * ng, &pout) || wsbuf(w, W_SELPST, ng, &pst) ||
-      wsbuf(w, W_SELPPT, ng, &ppt) || wsbuf(w, W_SELAPT, ng, &apt) || wsbuf(w, W_SELAST, ng, &ast))
-    return -1;
-  sa.cur = sa.hist + TASEL_KEYS;
-  sa.vstatus = a->vstatus;
-  sa.msg_idx = a->msg_idx;
-  sa.n = (uint32_t)a->n;
-  sa.src = a->ta_src;
-  sa.idx = a->ta_idx;
-  sa.grp_off = a->grp_off;
-  sa.n_groups = (uint32_t)ng;
-  sa.n_cand = (uint32_t)a->n_ta_partials;
-  sa.t = threshold;
-  sa.chosen = chosen;
-  sa.ta_count = ta_count;
-  sa.ctr = ctr;
-  HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
-  TIMED(*d, "k_ta_select", s, launch_ta_select(sa, s));
-  TaScatterArgs sc{};
-  sc.n_groups = (uint32_t)ng;
-  sc.state = sa.state;
-  sc.ta_out = a->ta_out;
-  sc.ta_status = a->ta_status;
-  sc.ctr = ctr;
-  if (!a->n) {  // no partial: no group has a member
-    TIMED(*d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
-    TIMED(*d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a->ta_status, (uint32_t)ng, a->agg_vstatus, s));
-    return ws_release(w, s);
-  }
-  TIMED(*d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
-  TIMED(*d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
-  // phase 3
-  const uint8_t* sdone = nullptr;
-  if (ta_tail(*d, w, vc.vsig, sa.pmem, vc.vsigst, sa.pidx, sa.pgoff, ng, ng * t, 0, pout, pst, ppt, s, nullptr, nullptr,
-              &sdone))
-    return -1;
-  sc.perm = sa.perm;
-  sc.pout = pout;
-  sc.pstatus = pst;
-  sc.ppt = ppt;
-  sc.sdone = sdone;
-  sc.rows16 = (((uintptr_t)a->ta_out | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
-  sc.agg_pt = apt;
-  sc.agg_st = ast;
-  TIMED(*d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
-  // phase 4.  The messages' lines: computed by phase 1 unless it deferred them; then this pass
-  // defers them too where its plan can (the batched sizes), else they are computed first
-  Ws& w2 = ws_acquire(*d, s);
-  size_t defer2 = 0;
-  if (defer) {
-    if (vp_bfe(VerifyShape{ng, ng, 0, false, false, 0, d->n_cu, false},
-               VerifyKnobs{g_gcap.load(), g_fbcap.load(), g_fe_batch_min.load(), g_slot_msm_min.load(),
-                           g_rlc_lanes.load(), g_adaptive.load()}))
-      defer2 = a->n_msgs;
-    else
-      TIMED(*d, "k_lines_msg", s, launch_lines_msg((MsgEntry*)a->hm, (uint32_t)a->n_msgs, s));
-  }
-  TaFold tables2{};
-  tables2.pk_table = (const G1AEntry*)a->dv_pk_table;
-  tables2.pk_table_st = a->dv_pk_table_st;
-  VerifyCall v2;
-  v2.pks = a->dv_pks;
-  v2.pre_sig = apt;
-  v2.pre_sigst = ast;
-  v2.msg_idx = sa.gmsg;
-  v2.hm = (const MsgEntry*)a->hm;
-  v2.n = ng;
-  v2.n_groups = ng;
-  v2.status = a->agg_vstatus;
-  v2.s = s;
-  v2.fold = a->dv_pk_table ? &tables2 : nullptr;
-  v2.defer_hm = (MsgEntry*)a->hm;
-  v2.defer_msgs = defer2;
-  if (verify_pipeline(*d, w2, v2)) return -1;
-  TIMED(*d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a->ta_status, (uint32_t)ng, a->agg_vstatus, s));
-  if (ws_release(w, s)) return -1;
-  return &w2 == &w ? 0 : ws_release(w2, s);
+  return slot_select_core(*d, s, *a, threshold, chosen, ta_count, TASEL_MODE_FIRST, true);
+}
+
+int hbls_slot_select_batch(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                           const uint32_t* msg_len, size_t n, const uint32_t* cand, const int64_t* cand_idx,
+                           const uint32_t* grp_off, size_t n_groups, const uint8_t* dv_pks, uint32_t threshold,
+                           uint8_t* vstatus, uint32_t* chosen, uint32_t* ta_count, uint8_t* ta_out, uint8_t* ta_status,
+                           uint8_t* agg_vstatus) {
+  if (ensure_init()) return -1;
+  if (threshold == 0 || threshold > (uint32_t)TA_SMALL_MAX)
+    return set_err("hbls_slot_select_batch: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
+  if (n >= 0xffffffffull || n_groups >= 0xffffffffull || n_groups * threshold >= 0xffffffffull)
+    return set_err("hbls_slot_select_batch: too many items");
+  if (n && (!pks || !sigs || !msg_off || !msg_len || !vstatus))
+    return set_err("hbls_slot_select_batch: pks, sigs, msg_off, msg_len and vstatus are required");
+  if (n && !msgs)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i]) return set_err("hbls_slot_select_batch: msgs is required");
+  if (n_groups && (!grp_off || !dv_pks || !chosen || !ta_count || !ta_out || !ta_status || !agg_vstatus))
+    return set_err("hbls_slot_select_batch: grp_off, dv_pks, chosen, ta_count, ta_out, ta_status and agg_vstatus are required");
+  static const uint32_t no_groups[1] = {0};
+  if (!n_groups) grp_off = no_groups;
+  for (size_t g = 0; g < n_groups; g++)
+    if (grp_off[g + 1] < grp_off[g]) return set_err("hbls_slot_select_batch: grp_off must be non-decreasing");
+  if (grp_off[n_groups] > grp_off[0] && (!cand || !cand_idx))
+    return set_err("hbls_slot_select_batch: cand and cand_idx are required");
+  if (n == 0 && n_groups == 0) return 0;
+  return slot_select_host(pks, sigs, msgs, msg_off, msg_len, n, cand, cand_idx, grp_off, n_groups, dv_pks, threshold,
+                          vstatus, chosen, ta_count, ta_out, ta_status, agg_vstatus);
 }
 
 // Cumulative per-process counters of hbls_slot_select_device over the devices of the mask, reset by

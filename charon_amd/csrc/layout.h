@@ -126,6 +126,7 @@ struct TaSelectArgs {
   const uint32_t* grp_off;
   uint32_t n_groups, t;
   uint32_t n_cand;  // entries of src / idx: offsets beyond them are cut there
+  uint32_t mode;    // tasel.h TASEL_MODE_*: ta_select (0, the device entry) or ta_select_matching
   // per group, the caller's order: members (n_groups t, the caller's array), their share indices,
   // the count (the caller's array), class key, state (tasel.h TASEL_*) and message
   uint32_t* chosen;

@@ -85,4 +85,80 @@ TASEL_HD TaSel ta_select(const uint8_t* vstatus, const uint32_t* msg_idx, uint32
   return r;
 }
 
+// How k_ta_select picks a group's members: ta_select, or ta_select_matching below.
+enum : uint32_t { TASEL_MODE_FIRST = 0, TASEL_MODE_MATCHING = 1 };
+
+// Whether candidate j of [b, e) is stored, the reference's parsigdb/memory.go:149-160: it is verified
+// and no earlier verified candidate has its share index (a second partial under a stored share index
+// is dropped whatever its root).
+TASEL_HD bool ta_stored(const uint8_t* vstatus, uint32_t n, const uint32_t* src, const int64_t* idx, uint32_t b,
+                        uint32_t j) {
+  if (src[j] >= n || vstatus[src[j]] != 0) return false;
+  for (uint32_t i = b; i < j; i++)
+    if (src[i] < n && vstatus[src[i]] == 0 && idx[i] == idx[j]) return false;
+  return true;
+}
+
+// The reference's matching rule (parsigdb/memory.go:197-225 getThresholdMatching) for candidates
+// that may span several messages; arguments and outputs as ta_select.  Walking the candidates in
+// order, the stored ones are counted per message; the first message to hold t of them wins, and
+// those t, in candidate order, are the members (TaSel::msg is their message; key and shifted come
+// from their positions as in ta_select).  Candidates over one message give ta_select's result,
+// by calling it: also below t, where its count and chosen report the stored candidates found.
+// Candidates over several messages of which none holds t give no members: TASEL_FEW, count 0,
+// chosen all TASEL_NONE.  TASEL_MIXED never arises.  A lane keeps no table of what it has seen: it
+// walks its candidates again (cubic in their number at worst, a handful in practice), so their
+// number has no bound.
+TASEL_HD TaSel ta_select_matching(const uint8_t* vstatus, const uint32_t* msg_idx, uint32_t n, const uint32_t* src,
+                                  const int64_t* idx, uint32_t b, uint32_t e, uint32_t t, uint32_t* chosen,
+                                  int64_t* cidx) {
+  bool have_msg = false, several = false;
+  uint32_t m0 = 0;
+  for (uint32_t j = b; j < e; j++) {
+    if (src[j] >= n) continue;
+    const uint32_t m = msg_idx[src[j]];
+    if (!have_msg) {
+      m0 = m;
+      have_msg = true;
+    } else if (m != m0) {
+      several = true;
+    }
+  }
+  if (!several) return ta_select(vstatus, msg_idx, n, src, idx, b, e, t, chosen, cidx);
+  TaSel r;
+  r.count = 0;
+  r.key = TASEL_KEY_NONE;
+  r.msg = m0;
+  r.state = TASEL_FEW;
+  r.shifted = 0;
+  for (uint32_t k = 0; k < t; k++) {
+    chosen[k] = TASEL_NONE;
+    cidx[k] = 0;
+  }
+  for (uint32_t j = b; j < e; j++) {
+    if (!ta_stored(vstatus, n, src, idx, b, j)) continue;
+    const uint32_t m = msg_idx[src[j]];
+    // the stored candidates over m up to j: the message is compared first, it is the cheap test
+    uint32_t c = 1;
+    for (uint32_t i = b; i < j && c < t; i++)
+      if (src[i] < n && msg_idx[src[i]] == m && ta_stored(vstatus, n, src, idx, b, i)) c++;
+    if (c < t) continue;
+    uint32_t last = 0;
+    r.key = 0;
+    for (uint32_t i = b; i <= j && r.count < t; i++) {  // exactly t: an earlier t-th would have ended the walk
+      if (src[i] >= n || msg_idx[src[i]] != m || !ta_stored(vstatus, n, src, idx, b, i)) continue;
+      chosen[r.count] = src[i];
+      cidx[r.count] = idx[i];
+      r.count++;
+      last = i - b;
+      r.key = ta_class_key(r.key, last);
+    }
+    r.msg = m;
+    r.state = TASEL_OK;
+    r.shifted = last != t - 1 ? 1 : 0;
+    return r;
+  }
+  return r;
+}
+
 }  // namespace hb

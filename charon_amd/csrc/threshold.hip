@@ -883,7 +883,8 @@ void launch_ta_member_status(const uint8_t* sig_st, const uint32_t* src, uint32_
 }
 
 // ---------------------------------------------------------------------------------------
-// Verified-member selection (hbls_slot_select_device; the rule is tasel.h's ta_select).  Behind the
+// Verified-member selection (hbls_slot_select_device: the rule is tasel.h's ta_select;
+// hbls_slot_select_batch: ta_select_matching, TaSelectArgs::mode).  Behind the
 // verification's final verdicts:
 //   k_ta_select   1 lane / group: the members among the group's candidates -> chosen, ta_count (the
 //                 caller's), their share indices, the group's state, message and 16-bit class key,
@@ -915,8 +916,10 @@ __global__ __launch_bounds__(64) void k_ta_select(TaSelectArgs a) {
   TaSel r{};
   if (valid) {
     const uint32_t b = min(a.grp_off[g], a.n_cand), e = min(max(a.grp_off[g + 1], b), a.n_cand);
-    r = ta_select(a.vstatus, a.msg_idx, a.n, a.src, a.idx, b, e, a.t, a.chosen + (size_t)g * a.t,
-                  a.cidx + (size_t)g * a.t);
+    uint32_t* chosen = a.chosen + (size_t)g * a.t;
+    int64_t* cidx = a.cidx + (size_t)g * a.t;
+    r = a.mode == TASEL_MODE_MATCHING ? ta_select_matching(a.vstatus, a.msg_idx, a.n, a.src, a.idx, b, e, a.t, chosen, cidx)
+                                      : ta_select(a.vstatus, a.msg_idx, a.n, a.src, a.idx, b, e, a.t, chosen, cidx);
     a.ta_count[g] = r.count;
     a.key[g] = r.key;
     a.state[g] = r.state;

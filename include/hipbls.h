@@ -334,6 +334,46 @@ int hbls_slot_device(const hbls_slot* args, void* stream);
 int hbls_slot_select_device(const hbls_slot* args, uint32_t threshold, uint32_t* chosen,
                             uint32_t* ta_count, void* stream);
 int hbls_slot_select_stats(uint64_t* out, size_t n);
+/* One duty from host buffers to aggregates: hbls_verify_batch over the n partials, the choice of
+ * each validator's members among its verified candidates, hbls_threshold_aggregate_batch over the
+ * members and hbls_verify_batch of the aggregates under the DV keys, in one blocking, thread-safe
+ * call with flat arguments (what the Go shim can pass; hbls_slot's pointers to Go memory it cannot).
+ *   pks, sigs, msgs, msg_off, msg_len, n: the partials, exactly as hbls_verify_batch takes them;
+ *   cand, cand_idx, grp_off (n_groups + 1 entries): group g's candidates in arrival order are
+ *     cand[j], an index among the n partials, under share index cand_idx[j], for j in
+ *     [grp_off[g], grp_off[g + 1]); a candidate with cand[j] >= n counts as not verified;
+ *   dv_pks: 48 bytes per group; threshold: 1 .. 16.
+ * Outputs, all host memory: vstatus (n), one per partial as hbls_verify_batch writes it, whether
+ * or not a group lists the partial; chosen (n_groups * threshold), the members as indices among the
+ * n partials, 0xffffffff past the last one; ta_count (n_groups); ta_out (96 bytes per group);
+ * ta_status and agg_vstatus (n_groups each).
+ * The members follow the reference's matching rule (parsigdb/memory.go:149-160, 197-225).  Walking
+ * a group's candidates in order, candidate j is stored iff its vstatus is OK and no earlier
+ * candidate with OK status has its share index (whatever that one's message).  The first message
+ * to hold `threshold` stored candidates wins; those, in candidate order, are the members.  A group
+ * whose candidates are all over one message gets what hbls_slot_select_device gives it: also below
+ * `threshold`, where chosen and ta_count report the stored candidates found.  A group whose
+ * candidates span several messages of which none reaches `threshold` has no members: ta_count 0.
+ * HBLS_BAD_INPUT for candidates over two messages does not arise here.
+ * ta_status is as hbls_threshold_aggregate_batch over the members, agg_vstatus[g] the aggregate's
+ * verdict under dv_pks[g] over the members' message (the aggregation status when there is no
+ * aggregate).  A group without `threshold` members gets HBLS_UNCHECKED in both and 96 zero bytes.
+ * n_groups == 0 verifies the partials and returns; n == 0 gives every group HBLS_UNCHECKED.
+ * Call errors (-1): threshold outside 1..16, grp_off not non-decreasing, n or n_groups * threshold
+ * of 2^32 - 1 or more, a required pointer that is NULL while its count is not zero.
+ * The aggregation groups are sharded over the devices of the mask; a shard verifies the partials
+ * its groups list (one listed by groups of two shards is verified in both) and its share of the
+ * partials no group lists.  The call runs the device entry's pipeline: learned key cache, ladder
+ * tables, batched subgroup test, the aggregation reading the partials the verification
+ * decompressed.  It does not write into the decompressed-signature cache (hbls_sig_cache): a later
+ * hbls_threshold_aggregate_batch over the same partials decompresses them again.  One shard is not
+ * chunked: a call beyond the workspace's reach fails, as hbls_slot_select_device does. */
+int hbls_slot_select_batch(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                           const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                           const uint32_t* cand, const int64_t* cand_idx, const uint32_t* grp_off,
+                           size_t n_groups, const uint8_t* dv_pks, uint32_t threshold,
+                           uint8_t* vstatus, uint32_t* chosen, uint32_t* ta_count, uint8_t* ta_out,
+                           uint8_t* ta_status, uint8_t* agg_vstatus);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
