@@ -40,6 +40,7 @@ EXPORTS = (
     "hbls_verify_device_first_error", "hbls_key_learn_stats", "hbls_key_wide_stats",
     "hbls_slot_select_device", "hbls_slot_select_stats", "hbls_subgroup_batch", "hbls_subgroup_batch_stats",
     "hbls_slot_select_batch",
+    "hbls_duty_open", "hbls_duty_add", "hbls_duty_state", "hbls_duty_stats", "hbls_duty_close",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -144,6 +145,11 @@ def _declare(lib):
         "hbls_slot_select_device": ([ctypes.POINTER(HblsSlot), U32, P, P, P], ctypes.c_int),
         "hbls_slot_select_stats": ([P, SZ], ctypes.c_int),
         "hbls_slot_select_batch": ([P, P, P, P, P, SZ, P, P, P, SZ, P, U32, P, P, P, P, P, P], ctypes.c_int),
+        "hbls_duty_open": ([P, SZ, U32, U32, P], ctypes.c_int),
+        "hbls_duty_add": ([ctypes.c_uint64, P, P, P, P, P, P, P, SZ, P, P, P, P, P, P, P, P, P], ctypes.c_int),
+        "hbls_duty_state": ([ctypes.c_uint64, P, P], ctypes.c_int),
+        "hbls_duty_stats": ([ctypes.c_uint64, P, SZ], ctypes.c_int),
+        "hbls_duty_close": ([ctypes.c_uint64], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
         "hbls_sync": ([P], ctypes.c_int),
         "hbls_status_bitmap": ([P, SZ, P, P], ctypes.c_int),

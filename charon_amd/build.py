@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "lib", "libhipbls.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["hipbls.hip", "pipeline.hip", "threshold.hip", "vbatch.hip", "vgroup.hip", "roots.hip", "hash.hip", "msm.hip",
-           "hashsplit.hip"]
+           "hashsplit.hip", "duty.hip"]
 
 
 def build_id(defines=()) -> str:
@@ -237,6 +237,47 @@ def build_slothostcheck(force: bool = False, verbose: bool = True) -> str:
         if m and m.group(0).decode() == bid:
             return out
     cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DHS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
+DUTYCHECK_PREFIX = "hbls-dutycheck:"
+DUTYCHECK_HEADERS = ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h", "tasel.h")
+
+
+def dutycheck_build_id(root: str = "") -> str:
+    """The id embedded in the duty sessions' harness (tests/native/dutycheck.cpp, `dc_build_id()`):
+    sha256 over its source, the headers it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "dutycheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return DUTYCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_dutycheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_dutycheck.so (tests/test_duty_host.py): the storing and firing rule of a
+    duty session and the host plan of hbls_duty_add on the CPU; test-only.  Reused when its embedded
+    id equals the tree's, as build_hostcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "dutycheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_dutycheck.so")
+    bid = dutycheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-dutycheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
     subprocess.run(cmd, check=True, timeout=900)
     os.replace(out + ".tmp", out)
     if verbose:
@@ -582,7 +623,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     """The test-only artefacts the product does not depend on (the C client of the ABI, the device
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
-    for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_subgcheck, build_devblocks_all, build_widedev,
+    for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
                build_subgdev):
         try:
             fn(force, verbose)

@@ -12,6 +12,8 @@ calls.  INTEGRATION.md §3 gives the same changes as Go patches.
                                   aggregate, verify the aggregates
   sigagg_slot_host                the same duty through the host-buffer call the Go shim binds (hbls_slot_select_batch),
                                   under parsigdb's matching rule (memory.go:149-160, 197-225); numpy only
+  ParSigDuty                      the same chain as the sets arrive: one duty session (hbls_duty_*), one call per
+                                  peer's set, aggregates for the validators that reach the threshold through it
   validatorapi_submit             core/validatorapi/validatorapi.go:284-306 + verifyPartialSig :1213-1229
   lock_verify_signatures          cluster/lock.go:151-197 (VerifyAggregate over every pubshare, :185)
   dkg_agg_deposit_data            dkg/dkg.go:820-899 (n x Verify + ThresholdAggregate + Verify per DV)
@@ -317,6 +319,97 @@ def sigagg_slot_host(impl_or_L, threshold: int, dv_pubkeys: Mapping[bytes, bytes
         if ast[k] != OK:
             raise _wrap("threshold aggregate", "aggregate signature verification failed: " + _verr(int(ast[k])))
     return statuses, {pk: bytes(out[k]) for k, pk in enumerate(keys)}, used
+
+
+class ParSigDuty:
+    """ParSigEx.handle -> MemDB.StoreExternal -> Aggregator.Aggregate for ONE duty under the
+    reference's arrival pattern (parsigex.go:93-98, parsigdb/memory.go:80-123 and 197-225,
+    sigagg.go:84-117): every peer's set is one call of a duty session (hbls_duty_add), which verifies
+    it, stores what the ParSigDB would store, and aggregates the validators that reach the threshold
+    through this very set from the partials resident on the device.
+
+    store_external(set) takes a peer's {pubkey: ParSig} and returns {pubkey: aggregate} for the
+    validators that fired; it raises the reference's error chain as sigagg_slot_host does: the first
+    entry of the set (in set order) that fails its pre-checks or its verification aborts with
+    "invalid partial signature: ..." (parsigex.go:96), a fired validator whose aggregation or
+    aggregate verification fails with "threshold aggregate: ..." (sigagg.go:105-119).  A context
+    manager: close() frees the device state, where MemDB.Trim deletes the duty."""
+
+    def __init__(self, impl, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
+                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16):
+        self._keys = list(dv_pubkeys)
+        self._group = {pk: g for g, pk in enumerate(self._keys)}
+        self._shares = pubshares_by_key
+        self._duty = impl.duty_open([dv_pubkeys[pk] for pk in self._keys], threshold, max_stored)
+
+    def __enter__(self) -> "ParSigDuty":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def close(self) -> None:
+        self._duty.close()
+
+    def state(self):
+        cnt, fired = self._duty.state()
+        return {pk: (cnt[g], fired[g]) for g, pk in enumerate(self._keys)}
+
+    def store_external(self, signed_set: Mapping[bytes, ParSig]) -> Dict[bytes, bytes]:
+        pks, msgs, sigs, groups, idx = [], [], [], [], []
+        pre: Optional[str] = None
+        for pk, ps in signed_set.items():  # the pre-checks in set order, up to the first failing one
+            shares = self._shares.get(pk)
+            if shares is None or pk not in self._group:
+                pre = "unknown pubkey, not part of cluster lock"
+            elif ps.share_idx not in shares:
+                pre = "invalid shareIdx"
+            elif len(ps.signature) != 96:
+                pre = "signature from core: " + _LEN_ERR
+            elif ps.signature == ZERO_SIG:
+                pre = "invalid signature: no signature found"  # signing.go:107-110
+            if pre is not None:
+                break
+            pks.append(shares[ps.share_idx])
+            msgs.append(ps.signing_root)
+            sigs.append(ps.signature)
+            groups.append(self._group[pk])
+            idx.append(ps.share_idx)
+        if pre is not None or not pks:
+            # nothing of a set with a failing entry is stored (parsigex.go:93-98 returns before StoreExternal):
+            # the entries before it are verified only, for the error the reference's loop returns first
+            if pks:
+                r = self._duty.add(pks, msgs, sigs, [0xFFFFFFFF] * len(pks), idx)
+                for st in r.vstatus:
+                    if st != OK:
+                        raise _wrap("invalid partial signature", "invalid signature: " + _verr(st))
+            if pre is not None:
+                raise _wrap("invalid partial signature", pre)
+            return {}
+        # One call verifies and stores.  Where an entry fails verification the reference drops the whole
+        # set (handle returns before StoreExternal); the session has by then stored the set's verified
+        # entries, each of which is a partial the ParSigDB would accept from that peer on its own.
+        # The error then carries, as `fired`, the aggregates of the validators those entries brought to the
+        # threshold: they fire once, so the caller must not lose them.
+        r = self._duty.add(pks, msgs, sigs, groups, idx)
+        out: Dict[bytes, bytes] = {}
+        err: Optional[CallerError] = None
+        for k, g in enumerate(r.fired):
+            if r.ta_status[k] != OK:
+                err = err or _wrap("threshold aggregate", status_error("threshold_aggregate", int(r.ta_status[k])))
+            elif r.agg_vstatus[k] != OK:
+                err = err or _wrap("threshold aggregate",
+                                   "aggregate signature verification failed: " + _verr(int(r.agg_vstatus[k])))
+            else:
+                out[self._keys[g]] = r.aggregates[k]
+        for st in r.vstatus:  # the verification loop runs first in the reference: its error wins
+            if st != OK:
+                err = _wrap("invalid partial signature", "invalid signature: " + _verr(st))
+                break
+        if err is not None:
+            err.fired = out
+            raise err
+        return out
 
 
 def validatorapi_submit(impl, pubshare_of: Mapping[bytes, bytes],

@@ -10,6 +10,8 @@
 #include "layout.h"
 #include "../../include/hipbls.h"
 #include "coalesce.h"
+#include "dutysel.h"
+#include "hduty.h"
 #include "hgroup.h"
 #include "hslot.h"
 #include "msgtable.h"
@@ -24,6 +26,7 @@
 #include <condition_variable>
 #include <deque>
 #include <functional>
+#include <memory>
 #include <mutex>
 #include <numeric>
 #include <string>
@@ -361,6 +364,10 @@ enum IoId {
   // hbls_slot_select_batch: the candidates, their share indices and offsets, the DV keys; the members, their counts,
   // the aggregates and the two statuses per group
   I_CAND, I_CIDX, I_SGOFF, I_DVPK, I_CHOSEN, I_TACNT, I_TAOUT, I_TAST, I_AGGST,
+  // hbls_duty_add: the items' serials, the touched groups (CSR), the per-item and per-touched-group outputs of
+  // k_duty_store, its two lists and counters, the sorted fired rows and their group ids
+  I_DSERIAL, I_DTGRP, I_DTOFF, I_DTPOS, I_DTIDX, I_DSTORED, I_DSLOT, I_DMSLOT, I_DMSER, I_DMIDX, I_DFMSG, I_DFKEY,
+  I_DCOPY, I_DFIRED, I_DCTR, I_DFROW, I_DFGRP,
   I_COUNT
 };
 
@@ -3026,6 +3033,434 @@ int slot_select_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msg
 }
 
 // ---------------------------------------------------------------------------------------
+// Duty sessions (hbls_duty_open / _add / _state / _stats / _close; hduty.h is the host plan,
+// dutysel.h the rule, duty.hip the kernels): hbls_slot_select_batch's pipeline under the arrival
+// pattern of the reference node, one call per peer's set.  A duty keeps in device memory, per shard
+// (a contiguous range of its groups on one device, the rule of hslot.h and fan_out): the hashed
+// messages with their lines, and per group max_stored slots of decompressed partials with their
+// share indices, message ids and serials, the count and the fired flag.
+// ---------------------------------------------------------------------------------------
+struct DutyShard {
+  Dev* d = nullptr;
+  size_t gb = 0, ge = 0;
+  DutyMsgTable tab;   // the shard's messages (host); ids index hm
+  size_t hashed = 0;  // messages resident in hm (a failed add may leave the table ahead of it)
+  MsgEntry* hm = nullptr;
+  size_t hm_cap = 0;
+  HmEntry* store = nullptr;     // (ge - gb) max_stored points
+  uint8_t* store_st = nullptr;  // their member statuses: zero, a stored partial was verified
+  int64_t* rec_idx = nullptr;
+  uint32_t *rec_msg = nullptr, *rec_serial = nullptr, *count = nullptr;
+  uint8_t *fired = nullptr, *dvpk = nullptr;
+  uint64_t* selctr = nullptr;  // what k_ta_sel_scatter counts (the device's own counters stay hbls_slot_select's)
+};
+// INVARIANT: no two streams ever touch a duty's device buffers.  Every call on a duty holds `mu`
+// from before its first enqueue until its stream (a host-call context's, with the workspace side
+// streams joined into it) has drained; the next call, on whatever stream, is ordered behind it by
+// that host-side wait alone.  Nothing else in the library knows these buffers.
+struct Duty {
+  std::mutex mu;
+  bool closed = false, broken = false;
+  size_t n_groups = 0;
+  uint32_t t = 0, max_stored = 0, next_serial = 0;
+  std::vector<DutyShard> sh;
+  uint64_t stats[6] = {};
+};
+std::mutex g_duty_mu;
+std::unordered_map<uint64_t, std::shared_ptr<Duty>> g_duties;
+uint64_t g_duty_next = 1;
+
+std::shared_ptr<Duty> duty_find(uint64_t handle) {
+  std::lock_guard<std::mutex> l(g_duty_mu);
+  auto it = g_duties.find(handle);
+  return it == g_duties.end() ? nullptr : it->second;
+}
+
+void duty_free_shard(DutyShard& s) {
+  if (!s.d) return;
+  std::lock_guard<std::mutex> lk(s.d->mu);
+  if (hipSetDevice(s.d->ord) != hipSuccess) return;
+  for (void* p : {(void*)s.hm, (void*)s.store, (void*)s.store_st, (void*)s.rec_idx, (void*)s.rec_msg, (void*)s.rec_serial,
+                  (void*)s.count, (void*)s.fired, (void*)s.dvpk, (void*)s.selctr})
+    if (p) (void)hipFree(p);
+  s = DutyShard{};
+}
+
+int duty_alloc_shard(DutyShard& s, const uint8_t* dv_pks, uint32_t max_stored) {
+  Dev& d = *s.d;
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  const size_t ng = s.ge - s.gb, slots = std::max<size_t>(ng * max_stored, 1), g1 = std::max<size_t>(ng, 1);
+  HCHK(hipMalloc((void**)&s.store, slots * sizeof(HmEntry)));
+  HCHK(hipMalloc((void**)&s.store_st, slots));
+  HCHK(hipMalloc((void**)&s.rec_idx, slots * sizeof(int64_t)));
+  HCHK(hipMalloc((void**)&s.rec_msg, slots * sizeof(uint32_t)));
+  HCHK(hipMalloc((void**)&s.rec_serial, slots * sizeof(uint32_t)));
+  HCHK(hipMalloc((void**)&s.count, g1 * sizeof(uint32_t)));
+  HCHK(hipMalloc((void**)&s.fired, g1));
+  HCHK(hipMalloc((void**)&s.dvpk, 48 * g1));
+  HCHK(hipMalloc((void**)&s.selctr, SEL_COUNTERS * sizeof(uint64_t)));
+  HCHK(hipMemset(s.store_st, 0, slots));
+  HCHK(hipMemset(s.count, 0, g1 * sizeof(uint32_t)));
+  HCHK(hipMemset(s.fired, 0, g1));
+  HCHK(hipMemset(s.selctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
+  if (ng) HCHK(hipMemcpy(s.dvpk, dv_pks + 48 * s.gb, 48 * ng, hipMemcpyHostToDevice));
+  HCHK(hipStreamSynchronize(nullptr));  // complete before any stream's kernel reads them
+  return 0;
+}
+
+int duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored, uint64_t* handle) {
+  auto du = std::make_shared<Duty>();
+  du->n_groups = n_groups;
+  du->t = threshold;
+  du->max_stored = max_stored;
+  const std::vector<Dev*> ds = devs();
+  const size_t nd = slot_shards(ds.size(), n_groups);
+  du->sh.resize(nd);
+  for (size_t k = 0; k < nd; k++) {
+    du->sh[k].d = ds[k];
+    du->sh[k].gb = n_groups * k / nd;
+    du->sh[k].ge = n_groups * (k + 1) / nd;
+    if (duty_alloc_shard(du->sh[k], dv_pks, max_stored)) {
+      const std::string err = g_err;
+      for (size_t j = 0; j <= k; j++) duty_free_shard(du->sh[j]);  // nothing is left behind
+      return set_err("hbls_duty_open: device " + std::to_string(ds[k]->ord) + ": " + err);
+    }
+  }
+  std::lock_guard<std::mutex> l(g_duty_mu);
+  *handle = g_duty_next++;
+  g_duties[*handle] = du;
+  return 0;
+}
+
+// What one shard's add hands back: its fired groups, ascending, with their rows
+struct DutyShardOut {
+  std::vector<uint32_t> fired, chosen;
+  std::vector<uint8_t> ta_out, ta_status, agg_vstatus;
+  uint64_t n_stored = 0, n_full = 0, n_new_msgs = 0, resident = 0;
+};
+
+// One shard's part of an add: its items (caller indices, increasing).  As with
+// hbls_slot_select_batch, the shard's add is one verification: it is not chunked.
+int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                   const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx,
+                   const std::vector<uint32_t>& items, uint32_t first_serial, size_t gmax, uint8_t* vstatus,
+                   uint8_t* stored, DutyShardOut& out) {
+  const size_t m = items.size(), t = du.t, ng = sh.ge - sh.gb;
+  if (!m) return 0;
+  const double t_start = now_ms();
+  Dev& d = *sh.d;
+  HcLease hcs(d);
+  Hc& h = *hcs.h[0];
+  DutyShardPlan p;
+  duty_plan_shard(msgs, msg_off, msg_len, group, share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p);
+  const size_t nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
+  out.n_new_msgs = nnew;
+  out.resident = p.resident;
+  std::vector<uint8_t> hpk(48 * m), hsig(96 * m);
+  for (size_t q = 0; q < m; q++) {
+    memcpy(&hpk[48 * q], pks + 48ull * p.order[q], 48);
+    memcpy(&hsig[96 * q], sigs + 96ull * p.order[q], 96);
+  }
+  std::vector<uint64_t> noff(nnew);  // the new messages' offsets, from the first new byte
+  const uint64_t nb0 = nnew ? sh.tab.t.off[sh.hashed] : 0;
+  for (size_t j = 0; j < nnew; j++) noff[j] = sh.tab.t.off[sh.hashed + j] - nb0;
+  const double t_prep = now_ms();
+  std::unique_lock<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  hipStream_t s = h.s;
+  if (nm > sh.hm_cap) {  // grow geometrically, keeping the resident entries (hash and lines)
+    const size_t cap = std::max<size_t>(std::max<size_t>(nm, 2 * sh.hm_cap), 16);
+    MsgEntry* nh;
+    HCHK(hipMalloc((void**)&nh, cap * sizeof(MsgEntry)));
+    if (sh.hashed) HCHK(hipMemcpyAsync(nh, sh.hm, sh.hashed * sizeof(MsgEntry), hipMemcpyDeviceToDevice, s));
+    HCHK(hipStreamSynchronize(s));
+    if (sh.hm) HCHK(hipFree(sh.hm));
+    sh.hm = nh;
+    sh.hm_cap = cap;
+  }
+  uint8_t *dpk, *dsig, *dmsg;
+  uint64_t* doff;
+  uint32_t *dlen, *dmidx, *dvgoff, *dserial, *dtgrp, *dtoff, *dtpos;
+  int64_t* dtidx;
+  if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
+  PinnedUploads up;
+  up.add(I_MSG, sh.tab.t.bytes.data() + nb0, sh.tab.t.bytes.size() - (nnew ? nb0 : sh.tab.t.bytes.size()), &dmsg);
+  up.add(I_OFF, noff.data(), nnew, &doff);
+  up.add(I_LEN, sh.tab.t.len.data() + sh.hashed, nnew, &dlen);
+  up.add(I_MIDX, p.midx.data(), m, &dmidx);
+  up.add(I_VGOFF, p.vgoff.data(), p.vgoff.size(), &dvgoff);
+  up.add(I_DSERIAL, p.serial.data(), m, &dserial);
+  up.add(I_DTGRP, p.tgroup.data(), nt, &dtgrp);
+  up.add(I_DTOFF, p.toff.data(), p.toff.size(), &dtoff);
+  up.add(I_DTPOS, p.tpos.data(), np, &dtpos);
+  up.add(I_DTIDX, p.tidx.data(), np, &dtidx);
+  void *pst, *pstored, *pslot, *pmslot, *pmser, *pmidx, *pfmsg, *pfkey, *pcopy, *pfired, *pctr;
+  if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_DSTORED], m, &pstored) ||
+      ensure_buf(h.io[I_DSLOT], m * sizeof(uint32_t), &pslot) || ensure_buf(h.io[I_DMSLOT], nt * t * sizeof(uint32_t), &pmslot) ||
+      ensure_buf(h.io[I_DMSER], nt * t * sizeof(uint32_t), &pmser) || ensure_buf(h.io[I_DMIDX], nt * t * sizeof(int64_t), &pmidx) ||
+      ensure_buf(h.io[I_DFMSG], nt * sizeof(uint32_t), &pfmsg) || ensure_buf(h.io[I_DFKEY], nt * sizeof(uint32_t), &pfkey) ||
+      ensure_buf(h.io[I_DCOPY], m * sizeof(uint2), &pcopy) || ensure_buf(h.io[I_DFIRED], nt * sizeof(uint32_t), &pfired) ||
+      ensure_buf(h.io[I_DCTR], DUTY_CTRS * sizeof(uint32_t), &pctr))
+    return -1;
+  // phase 1: hash the messages new to the shard (with their lines: the entries stay), verify the set
+  Ws& w = ws_acquire(d, s);
+  HCHK(hipEventRecord(w.ev_fork, s));
+  hipStream_t shs = w.side[2];
+  HCHK(hipStreamWaitEvent(shs, w.ev_fork, 0));
+  if (nnew && hash_messages(d, dmsg, doff, dlen, nnew, sh.hm + sh.hashed, shs, true)) return -1;
+  HCHK(hipEventRecord(w.ev_side[2], shs));
+  VerifyCall vc;
+  vc.pks = dpk;
+  vc.sigs = dsig;
+  vc.msg_idx = dmidx;
+  vc.hm = sh.hm;
+  vc.n = m;
+  vc.grp_off = dvgoff;
+  vc.n_groups = p.n_vgroups();
+  vc.status = (uint8_t*)pst;
+  vc.s = s;
+  vc.device_entry = true;
+  vc.hm_ready = w.ev_side[2];
+  if (verify_pipeline(d, w, vc)) return -1;
+  HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  // store: the rule per touched group, then the stored partials' points out of the workspace
+  HCHK(hipMemsetAsync(pstored, 0, m, s));
+  HCHK(hipMemsetAsync(pctr, 0, DUTY_CTRS * sizeof(uint32_t), s));
+  DutyStoreArgs st{};
+  st.rec_idx = sh.rec_idx;
+  st.rec_msg = sh.rec_msg;
+  st.rec_serial = sh.rec_serial;
+  st.count = sh.count;
+  st.fired = sh.fired;
+  st.n_groups = (uint32_t)ng;
+  st.max_stored = du.max_stored;
+  st.t = du.t;
+  st.vstatus = (const uint8_t*)pst;
+  st.msg_idx = dmidx;
+  st.serial = dserial;
+  st.n = (uint32_t)m;
+  st.tgroup = dtgrp;
+  st.toff = dtoff;
+  st.tpos = dtpos;
+  st.tidx = dtidx;
+  st.n_touched = (uint32_t)nt;
+  st.n_pos = (uint32_t)np;
+  st.stored = (uint8_t*)pstored;
+  st.slot = (uint32_t*)pslot;
+  st.mslot = (uint32_t*)pmslot;
+  st.mserial = (uint32_t*)pmser;
+  st.midx = (int64_t*)pmidx;
+  st.fmsg = (uint32_t*)pfmsg;
+  st.fkey = (uint32_t*)pfkey;
+  st.copies = (uint2*)pcopy;
+  st.fired_u = (uint32_t*)pfired;
+  st.ctr = (uint32_t*)pctr;
+  TIMED(d, "k_duty_store", s, launch_duty_store(st, s));
+  TIMED(d, "k_duty_copy", s,
+        launch_duty_copy(vc.vsig, (uint32_t)m, st.copies, st.ctr + DUTY_CTR_COPIES, (uint32_t)m, sh.store,
+                         (uint32_t)(ng * du.max_stored), s));
+  HCHK(hipGetLastError());
+  if (ws_release(w, s)) return -1;
+  lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+  const double t_enq1 = now_ms();
+  std::vector<uint8_t> hst(m), hstored(m);
+  std::vector<uint32_t> hfired(nt);
+  uint32_t hctr[DUTY_CTRS] = {};
+  HCHK(hipMemcpyAsync(hst.data(), pst, m, hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(hstored.data(), pstored, m, hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(hctr, pctr, sizeof(hctr), hipMemcpyDeviceToHost, s));
+  if (nt) HCHK(hipMemcpyAsync(hfired.data(), pfired, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  sh.hashed = nm;
+  const double t_dev1 = now_ms();
+  for (size_t q = 0; q < m; q++) {
+    vstatus[p.order[q]] = hst[q];
+    stored[p.order[q]] = hstored[q];
+    out.n_stored += hstored[q] ? 1 : 0;
+  }
+  out.n_full = hctr[DUTY_CTR_FULL];
+  const size_t nf = hctr[DUTY_CTR_FIRED];
+  if (nf > nt) return set_err("hbls_duty_add: the fired list is longer than the touched groups");
+  double t_enq2 = t_dev1;
+  if (nf) {
+    // phases 3 and 4 of slot_select_core over the fired groups, ascending: their members are in the store
+    std::sort(hfired.begin(), hfired.begin() + nf);
+    for (size_t k = 0; k < nf; k++)
+      if (hfired[k] >= nt) return set_err("hbls_duty_add: a fired row names no touched group");
+    lk.lock();
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    uint32_t* dfrow;
+    PinnedUploads up2;
+    up2.add(I_DFROW, hfired.data(), nf, &dfrow);
+    void *pmem, *pser, *pfg, *pdv, *ptout, *ptst, *past;
+    if (upload_pinned(d, h, up2) || ensure_buf(h.io[I_CAND], nf * t * sizeof(uint32_t), &pmem) ||
+        ensure_buf(h.io[I_CHOSEN], nf * t * sizeof(uint32_t), &pser) || ensure_buf(h.io[I_DFGRP], nf * sizeof(uint32_t), &pfg) ||
+        ensure_buf(h.io[I_DVPK], 48 * nf, &pdv) || ensure_buf(h.io[I_TAOUT], 96 * nf, &ptout) ||
+        ensure_buf(h.io[I_TAST], nf, &ptst) || ensure_buf(h.io[I_AGGST], nf, &past))
+      return -1;
+    Ws& w2 = ws_acquire(d, s);
+    TaSelectArgs sa{};
+    uint8_t *pout, *pstt, *ast;
+    HmEntry *ppt, *apt;
+    if (wsbuf(w2, W_SELCIDX, nf * t, &sa.cidx) || wsbuf(w2, W_SELKEY, nf, &sa.key) || wsbuf(w2, W_SELSTATE, nf, &sa.state) ||
+        wsbuf(w2, W_SELGMSG, nf, &sa.gmsg) || wsbuf(w2, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
+        wsbuf(w2, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w2, W_SELPERM, nf, &sa.perm) ||
+        wsbuf(w2, W_SELPMEM, nf * t, &sa.pmem) || wsbuf(w2, W_SELPIDX, nf * t, &sa.pidx) ||
+        wsbuf(w2, W_SELPGOFF, nf + 1, &sa.pgoff) || wsbuf(w2, W_SELPOUT, 96 * nf, &pout) || wsbuf(w2, W_SELPST, nf, &pstt) ||
+        wsbuf(w2, W_SELPPT, nf, &ppt) || wsbuf(w2, W_SELAPT, nf, &apt) || wsbuf(w2, W_SELAST, nf, &ast))
+      return -1;
+    sa.cur = sa.hist + TASEL_KEYS;
+    sa.n_groups = (uint32_t)nf;
+    sa.t = du.t;
+    sa.chosen = (uint32_t*)pmem;
+    HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
+    DutyGatherArgs ga{};
+    ga.n_fired = (uint32_t)nf;
+    ga.n_touched = (uint32_t)nt;
+    ga.n_groups = (uint32_t)ng;
+    ga.max_stored = du.max_stored;
+    ga.t = du.t;
+    ga.group_base = (uint32_t)sh.gb;
+    ga.frow = dfrow;
+    ga.tgroup = dtgrp;
+    ga.mslot = st.mslot;
+    ga.mserial = st.mserial;
+    ga.midx = st.midx;
+    ga.fmsg = st.fmsg;
+    ga.fkey = st.fkey;
+    ga.dv_pks = sh.dvpk;
+    ga.chosen = sa.chosen;
+    ga.cidx = sa.cidx;
+    ga.key = sa.key;
+    ga.state = sa.state;
+    ga.gmsg = sa.gmsg;
+    ga.hist = sa.hist;
+    ga.serials = (uint32_t*)pser;
+    ga.fired_g = (uint32_t*)pfg;
+    ga.dv_out = (uint8_t*)pdv;
+    TIMED(d, "k_duty_gather", s, launch_duty_gather(ga, s));
+    TIMED(d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
+    TIMED(d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
+    const uint8_t* sdone = nullptr;
+    if (ta_tail(d, w2, sh.store, sa.pmem, sh.store_st, sa.pidx, sa.pgoff, nf, nf * t, 0, pout, pstt, ppt, s, nullptr, nullptr,
+                &sdone))
+      return -1;
+    TaScatterArgs sc{};
+    sc.n_groups = (uint32_t)nf;
+    sc.perm = sa.perm;
+    sc.state = sa.state;
+    sc.pout = pout;
+    sc.pstatus = pstt;
+    sc.ppt = ppt;
+    sc.sdone = sdone;
+    sc.ta_out = (uint8_t*)ptout;
+    sc.ta_status = (uint8_t*)ptst;
+    sc.rows16 = (((uintptr_t)ptout | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
+    sc.agg_pt = apt;
+    sc.agg_st = ast;
+    sc.ctr = sh.selctr;
+    TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+    VerifyCall v2;  // the aggregates under the DV keys gathered by group id; the messages' lines are resident
+    v2.pks = (const uint8_t*)pdv;
+    v2.pre_sig = apt;
+    v2.pre_sigst = ast;
+    v2.msg_idx = sa.gmsg;
+    v2.hm = sh.hm;
+    v2.n = nf;
+    v2.n_groups = nf;
+    v2.status = (uint8_t*)past;
+    v2.s = s;
+    if (verify_pipeline(d, w2, v2)) return -1;
+    TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts((const uint8_t*)ptst, (uint32_t)nf, (uint8_t*)past, s));
+    if (ws_release(w2, s)) return -1;
+    lk.unlock();
+    t_enq2 = now_ms();
+    out.fired.resize(nf);
+    out.chosen.resize(nf * t);
+    out.ta_out.resize(96 * nf);
+    out.ta_status.resize(nf);
+    out.agg_vstatus.resize(nf);
+    HCHK(hipMemcpyAsync(out.fired.data(), pfg, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HCHK(hipMemcpyAsync(out.chosen.data(), pser, nf * t * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+    HCHK(hipMemcpyAsync(out.ta_out.data(), ptout, 96 * nf, hipMemcpyDeviceToHost, s));
+    HCHK(hipMemcpyAsync(out.ta_status.data(), ptst, nf, hipMemcpyDeviceToHost, s));
+    HCHK(hipMemcpyAsync(out.agg_vstatus.data(), past, nf, hipMemcpyDeviceToHost, s));
+    HCHK(hipStreamSynchronize(s));
+  }
+  if (host_timing())
+    fprintf(stderr, "hbls duty_add shard groups %zu..%zu n=%zu touched=%zu new msgs=%zu fired=%zu: plan %.2f ms, "
+            "enqueue verify+store %.2f, device %.2f, enqueue aggregate+verify %.2f, device %.2f\n", sh.gb, sh.ge, m, nt,
+            nnew, nf, t_prep - t_start, t_enq1 - t_prep, t_dev1 - t_enq1, t_enq2 - t_dev1, now_ms() - t_enq2);
+  return 0;
+}
+
+int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+             const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
+             uint8_t* stored, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status,
+             uint8_t* agg_vstatus) {
+  const size_t nd = du.sh.size(), t = du.t;
+  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
+  std::vector<std::vector<uint32_t>> items;
+  duty_route(group, n, du.n_groups, nd, items);
+  std::vector<DutyShardOut> outs(nd);
+  std::vector<int> rc(nd, 0);
+  std::vector<std::string> errs(nd);
+  auto run = [&](size_t k) {
+    rc[k] = duty_add_shard(du, du.sh[k], pks, sigs, msgs, msg_off, msg_len, group, share_idx, items[k], du.next_serial, gmax,
+                           vstatus, stored, outs[k]);
+    if (rc[k]) errs[k] = g_err;
+  };
+  if (nd == 1) {
+    run(0);
+  } else {
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
+    for (auto& x : th) x.join();
+  }
+  for (size_t k = 0; k < nd; k++)
+    if (rc[k]) {
+      du.broken = true;  // a shard may have stored what another did not verify: the duty's state is no longer one stream's
+      return set_err("hbls_duty_add: device " + std::to_string(du.sh[k].d->ord) + ": " + errs[k]);
+    }
+  size_t nf = 0;  // the shards own ascending ranges of the groups: their lists concatenate in order
+  for (size_t k = 0; k < nd; k++) {
+    const DutyShardOut& o = outs[k];
+    const size_t f = o.fired.size();
+    if (f) {
+      memcpy(fired + nf, o.fired.data(), f * sizeof(uint32_t));
+      memcpy(chosen + nf * t, o.chosen.data(), f * t * sizeof(uint32_t));
+      memcpy(ta_out + 96 * nf, o.ta_out.data(), 96 * f);
+      memcpy(ta_status + nf, o.ta_status.data(), f);
+      memcpy(agg_vstatus + nf, o.agg_vstatus.data(), f);
+      nf += f;
+    }
+    du.stats[1] += o.n_stored;
+    du.stats[2] += o.n_new_msgs;
+    du.stats[3] += o.resident;
+    du.stats[5] += o.n_full;
+  }
+  du.stats[0] += n;
+  du.stats[4] += nf;
+  du.next_serial += (uint32_t)n;
+  *n_fired = nf;
+  return 0;
+}
+
+int duty_state(Duty& du, uint32_t* stored_count, uint8_t* fired_flag) {
+  for (DutyShard& s : du.sh) {
+    const size_t ng = s.ge - s.gb;
+    if (!ng) continue;
+    std::lock_guard<std::mutex> lk(s.d->mu);
+    if (hipSetDevice(s.d->ord) != hipSuccess) return set_err("hipSetDevice failed");
+    // every add has drained its stream (the duty's invariant): a plain copy sees the final records
+    HCHK(hipMemcpy(stored_count + s.gb, s.count, ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
+    HCHK(hipMemcpy(fired_flag + s.gb, s.fired, ng, hipMemcpyDeviceToHost));
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------
 // RCCL: one communicator per process (one GPU each) for the exchange of slot results
 // ---------------------------------------------------------------------------------------
 ncclComm_t g_comm = nullptr;
@@ -3721,6 +4156,81 @@ int hbls_slot_select_stats(uint64_t* out, size_t n) {
     HCHK(hipDeviceSynchronize());
     for (size_t k = 0; k < n; k++) out[k] += c[k];
   }
+  return 0;
+}
+
+int hbls_duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored, uint64_t* duty) {
+  if (ensure_init()) return -1;
+  if (!duty) return set_err("hbls_duty_open: duty is required");
+  if (threshold < 1 || threshold > (uint32_t)TA_SMALL_MAX)
+    return set_err("hbls_duty_open: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
+  if (max_stored < 1 || max_stored > DUTY_MAX_STORED)
+    return set_err("hbls_duty_open: max_stored must be in 1.." + std::to_string(DUTY_MAX_STORED));
+  if (n_groups && !dv_pks) return set_err("hbls_duty_open: dv_pks is required");
+  if (n_groups >= 0xffffffffull / DUTY_MAX_STORED) return set_err("hbls_duty_open: too many groups");
+  return duty_open(dv_pks, n_groups, threshold, max_stored, duty);
+}
+
+int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                  const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
+                  uint8_t* stored, uint32_t* first_serial, uint32_t* fired, size_t* n_fired, uint32_t* chosen,
+                  uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_add: no such duty (never opened, or closed)");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_add: the duty is closed");
+  if (du->broken) return set_err("hbls_duty_add: an earlier add failed on a device; close the duty");
+  if (!first_serial || !n_fired) return set_err("hbls_duty_add: first_serial and n_fired are required");
+  if (n >= 0xffffffffull - du->next_serial) return set_err("hbls_duty_add: the duty would reach 2^32 - 1 partials");
+  if (n && (!pks || !sigs || !msg_off || !msg_len || !group || !share_idx || !vstatus || !stored))
+    return set_err("hbls_duty_add: pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
+  if (!msgs)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i]) return set_err("hbls_duty_add: msgs is required");
+  if (std::min(n, du->n_groups) && (!fired || !chosen || !ta_out || !ta_status || !agg_vstatus))
+    return set_err("hbls_duty_add: fired, chosen, ta_out, ta_status and agg_vstatus are required");
+  *first_serial = du->next_serial;
+  *n_fired = 0;
+  if (!n) return 0;
+  return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
+                  ta_out, ta_status, agg_vstatus);
+}
+
+int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_state: no such duty (never opened, or closed)");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_state: the duty is closed");
+  if (du->n_groups && (!stored_count || !fired_flag)) return set_err("hbls_duty_state: stored_count and fired_flag are required");
+  return duty_state(*du, stored_count, fired_flag);
+}
+
+int hbls_duty_stats(uint64_t duty, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_stats: no such duty (never opened, or closed)");
+  if (!out || n > 6) return set_err("hbls_duty_stats: out is null or n above 6");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_stats: the duty is closed");
+  for (size_t k = 0; k < n; k++) out[k] = du->stats[k];
+  return 0;
+}
+
+int hbls_duty_close(uint64_t duty) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du;
+  {
+    std::lock_guard<std::mutex> l(g_duty_mu);
+    auto it = g_duties.find(duty);
+    if (it == g_duties.end()) return set_err("hbls_duty_close: no such duty (never opened, or closed)");
+    du = it->second;
+    g_duties.erase(it);
+  }
+  std::lock_guard<std::mutex> l(du->mu);  // behind the duty's call in flight, if any
+  du->closed = true;
+  for (DutyShard& s : du->sh) duty_free_shard(s);
   return 0;
 }
 

@@ -164,6 +164,55 @@ void launch_ta_sel_fill(const TaSelectArgs& a, hipStream_t s);
 void launch_ta_sel_scatter(const TaScatterArgs& a, hipStream_t s);
 void launch_ta_sel_verdicts(const uint8_t* ta_status, uint32_t n_groups, uint8_t* agg_vstatus, hipStream_t s);
 
+// Duty sessions (duty.hip k_duty_store / k_duty_copy / k_duty_gather; the rule is dutysel.h's).
+enum { DUTY_CTR_COPIES = 0, DUTY_CTR_FIRED = 1, DUTY_CTR_FULL = 2, DUTY_CTRS = 4 };
+struct DutyStoreArgs {
+  // the shard's resident records: per group max_stored slots, the count and the fired flag
+  int64_t* rec_idx;
+  uint32_t *rec_msg, *rec_serial, *count;
+  uint8_t* fired;
+  uint32_t n_groups, max_stored, t;
+  // the add's n items in verification order: verdicts, message ids, serials
+  const uint8_t* vstatus;
+  const uint32_t *msg_idx, *serial;
+  uint32_t n;
+  // the touched groups in CSR form (hduty.h DutyShardPlan): n_touched groups (toff: n_touched + 1), n_pos partials
+  const uint32_t *tgroup, *toff, *tpos;
+  const int64_t* tidx;
+  uint32_t n_touched, n_pos;
+  // out, per item: stored flag (zeroed by the caller: an item of no group is not walked) and record slot
+  uint8_t* stored;
+  uint32_t* slot;
+  // out, per touched group that fired: t member slots, serials and share indices, message, class key
+  uint32_t *mslot, *mserial;
+  int64_t* midx;
+  uint32_t *fmsg, *fkey;
+  // out, compacted: copies (x: slot in the store, y: item; n at most), the fired touched groups (n_touched
+  // at most), and ctr (DUTY_CTR_*, zeroed by the caller)
+  uint2* copies;
+  uint32_t *fired_u, *ctr;
+};
+struct DutyGatherArgs {
+  uint32_t n_fired, n_touched, n_groups, max_stored, t, group_base;
+  const uint32_t *frow, *tgroup;  // fired row k is touched group frow[k] (ascending), group tgroup[.] of the shard
+  const uint32_t *mslot, *mserial;
+  const int64_t* midx;
+  const uint32_t *fmsg, *fkey;
+  const uint8_t* dv_pks;  // the shard's DV keys, by group
+  // per fired row: members as indices into the store, share indices, class key, state, message (what
+  // k_ta_sel_fill reads; hist: the keys' histogram, zeroed by the caller), serials, group id, DV key
+  uint32_t* chosen;
+  int64_t* cidx;
+  uint32_t* key;
+  uint8_t* state;
+  uint32_t *gmsg, *hist, *serials, *fired_g;
+  uint8_t* dv_out;
+};
+void launch_duty_store(const DutyStoreArgs& a, hipStream_t s);
+void launch_duty_copy(const HmEntry* src, uint32_t n_src, const uint2* copies, const uint32_t* count, uint32_t max_copies,
+                      HmEntry* store, uint32_t n_slots, hipStream_t s);
+void launch_duty_gather(const DutyGatherArgs& a, hipStream_t s);
+
 // Hashing and the pairing kernel (pipeline.hip).
 constexpr int GROUPS_PER_WAVE = 21;  // k_pair3: 3 lanes per pairing, 21 pairings per wave
 void launch_hash_to_g2(const uint8_t* msgs, const uint64_t* off, const uint32_t* len, uint32_t n, MsgEntry* hm,

@@ -17,7 +17,7 @@ import ctypes
 import os
 import secrets
 import threading
-from typing import Dict, Iterable, List, Mapping, Sequence, Tuple
+from typing import Dict, Iterable, List, Mapping, Optional, Sequence, Tuple
 
 from . import _lib
 from ._lib import (BAD_INPUT, BAD_PUBKEY, BAD_SECRET, BAD_SIGNATURE, COMBINE_FAILED, NOT_VERIFIED, OK,
@@ -312,6 +312,89 @@ class HIPBLS:
         check(self._L.hbls_verify_aggregate_batch(_buf(bytes(pk_blob)), _u32_array(off), _buf(sig_blob), mb, mo, ml,
                                                   g, st))
         return list(st.raw[:g])
+
+    # ------------------------------------------------------------------ duty sessions
+    def duty_open(self, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16) -> "Duty":
+        """A duty session over validators 0 .. len(dv_pks) - 1 (hbls_duty_open): each peer's set is one
+        Duty.add, which verifies it, stores what the ParSigDB would store and returns the validators
+        that reached `threshold` through it with their verified aggregates."""
+        return Duty(self._L, dv_pks, threshold, max_stored)
+
+
+class DutyAdd:
+    """What one Duty.add returns: per partial of the set `vstatus` and `stored`, its first partial's
+    serial `first_serial`, and for the validators that fired in this add, ascending: `fired` (their
+    numbers), `chosen` (their members' serials), `aggregates`, `ta_status` and `agg_vstatus`."""
+
+    __slots__ = ("vstatus", "stored", "first_serial", "fired", "chosen", "aggregates", "ta_status", "agg_vstatus")
+
+
+class Duty:
+    """One duty's state in device memory between calls (include/hipbls.h hbls_duty_*).  A context
+    manager; calls on one Duty are serialised by the library."""
+
+    def __init__(self, L, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16):
+        self._L, self.n_groups, self.threshold = L, len(dv_pks), threshold
+        blob = b"".join(_need(p, PUBKEY_LEN, "public key") for p in dv_pks)
+        h = ctypes.c_uint64(0)
+        check(L.hbls_duty_open(_buf(blob), self.n_groups, threshold, max_stored, ctypes.byref(h)))
+        self._h: Optional[int] = h.value
+
+    def __enter__(self) -> "Duty":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def _handle(self) -> int:
+        if self._h is None:
+            raise TblsError("the duty is closed")
+        return self._h
+
+    def add(self, pks: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], groups: Sequence[int],
+            share_idx: Sequence[int]) -> DutyAdd:
+        """One arriving set, in arrival order: partial i belongs to validator groups[i] (any number
+        >= n_groups: verify only) under share index share_idx[i]."""
+        n, t = len(pks), self.threshold
+        if not (n == len(msgs) == len(sigs) == len(groups) == len(share_idx)):
+            raise TblsError("duty add: length mismatch")
+        pk_blob = b"".join(_need(p, PUBKEY_LEN, "public key") for p in pks)
+        sig_blob = b"".join(_need(s, SIG_LEN, "signature") for s in sigs)
+        mb, mo, ml = _pack_msgs([bytes(m) for m in msgs])
+        rows = max(1, min(n, self.n_groups))
+        vst, stored = ctypes.create_string_buffer(max(n, 1)), ctypes.create_string_buffer(max(n, 1))
+        first, nf = ctypes.c_uint32(0), ctypes.c_size_t(0)
+        fired, chosen = (ctypes.c_uint32 * rows)(), (ctypes.c_uint32 * (rows * t))()
+        out, tst, ast = ctypes.create_string_buffer(96 * rows), ctypes.create_string_buffer(rows), ctypes.create_string_buffer(rows)
+        check(self._L.hbls_duty_add(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml,
+                                    _u32_array([min(int(g), 0xFFFFFFFF) if g >= 0 else 0xFFFFFFFF for g in groups]),
+                                    _i64_array([int(x) for x in share_idx]), n, vst, stored, ctypes.byref(first), fired,
+                                    ctypes.byref(nf), chosen, out, tst, ast))
+        f = nf.value
+        r = DutyAdd()
+        r.vstatus, r.stored, r.first_serial = list(vst.raw[:n]), list(stored.raw[:n]), first.value
+        r.fired = list(fired[:f])
+        r.chosen = [list(chosen[k * t:(k + 1) * t]) for k in range(f)]
+        r.aggregates = [out.raw[96 * k:96 * k + 96] for k in range(f)]
+        r.ta_status, r.agg_vstatus = list(tst.raw[:f]), list(ast.raw[:f])
+        return r
+
+    def state(self) -> Tuple[List[int], List[bool]]:
+        """Per validator: the number of stored partials, and whether it has fired."""
+        g = self.n_groups
+        cnt, fl = (ctypes.c_uint32 * max(g, 1))(), ctypes.create_string_buffer(max(g, 1))
+        check(self._L.hbls_duty_state(self._handle(), cnt, fl))
+        return list(cnt[:g]), [b != 0 for b in fl.raw[:g]]
+
+    def stats(self) -> Dict[str, int]:
+        out = (ctypes.c_uint64 * 6)()
+        check(self._L.hbls_duty_stats(self._handle(), out, 6))
+        return dict(zip(("seen", "stored", "hashed", "resident_lookups", "fired", "full"), (int(x) for x in out)))
+
+    def close(self) -> None:
+        if self._h is not None:
+            h, self._h = self._h, None
+            check(self._L.hbls_duty_close(h))
 
 
 # ---------------------------------------------------------------------- package level API

@@ -374,6 +374,62 @@ int hbls_slot_select_batch(const uint8_t* pks, const uint8_t* sigs, const uint8_
                            size_t n_groups, const uint8_t* dv_pks, uint32_t threshold,
                            uint8_t* vstatus, uint32_t* chosen, uint32_t* ta_count, uint8_t* ta_out,
                            uint8_t* ta_status, uint8_t* agg_vstatus);
+/* Duty sessions: hbls_slot_select_batch's pipeline under the reference node's arrival pattern.  A
+ * duty keeps its state in device memory between calls: the hashed messages, and per group
+ * (validator) the decompressed points, share indices and message ids of the partials stored so
+ * far.  Each arriving set is one hbls_duty_add: it verifies the set, stores what the ParSigDB would
+ * store, aggregates the groups that reach `threshold` through this set from the resident points,
+ * verifies their aggregates under the DV keys, and returns those groups only.  For any way of
+ * cutting one candidate stream into adds, the union of what the adds return equals what
+ * hbls_slot_select_batch returns for the concatenation (given max_stored no smaller than a group's
+ * candidates).  A handle is never 0.
+ * hbls_duty_open: group g is validator g and dv_pks[48 g] its DV key; threshold: 1 .. 16;
+ *   max_stored: 1 .. 64, the stored partials a group can hold.  Everything but the message table
+ *   is allocated here, on every device that owns groups (208 + 16 bytes per slot of n_groups *
+ *   max_stored); a failed allocation is a call error that leaves nothing behind.
+ * hbls_duty_add: the n partials in arrival order, bytes and messages exactly as hbls_verify_batch
+ *   takes them; partial i belongs to group group[i] under share index share_idx[i]; group[i] >=
+ *   n_groups (0xffffffff, say) means "verify only".  Partial i is serial *first_serial + i, where
+ *   *first_serial is the number of partials of all earlier adds.
+ *   vstatus[i]: what hbls_verify_batch writes for the partial, whatever its group.
+ *   Walking the partials in order, partial i is stored (stored[i] = 1) iff its vstatus is OK, its
+ *   group has not fired, no stored partial of the group has its share index (whatever that one's
+ *   message) and the group holds fewer than max_stored.  A store that gives some message `threshold`
+ *   stored partials in the group fires it: its members are those partials in stored order, and the
+ *   group is closed from then on (later partials, also of the same call, are verified, not stored).
+ *   fired[0 .. *n_fired): the groups that fired in this call, ascending; for row k, chosen[k t ..
+ *   k t + t) are the members' serials, ta_out[96 k] and ta_status[k] as
+ *   hbls_threshold_aggregate_batch over the members, agg_vstatus[k] the aggregate's verdict under the
+ *   group's DV key over the members' message (the aggregation status when there is no aggregate).
+ *   The caller sizes the fired-row arrays for min(n, n_groups) rows; rows past *n_fired are not
+ *   written.  n == 0 is valid and fires nothing.
+ * hbls_duty_state: per group, the number of stored partials and whether it has fired (n_groups each).
+ * hbls_duty_stats (cumulative for the duty, n <= 6): out[0] partials seen, out[1] partials stored,
+ *   out[2] messages hashed to G2, out[3] message lookups answered from the duty's resident table
+ *   (every partial is one lookup: out[2] + out[3] == out[0] on one device), out[4] groups fired,
+ *   out[5] partials not stored because their group was full.
+ * hbls_duty_close frees the duty.  Any call with a closed handle, or one never issued, is a call
+ *   error (-1 with hbls_last_error).  Other call errors: threshold or max_stored out of range, a
+ *   required pointer that is NULL while its count is not zero, a duty that would reach 2^32 - 1
+ *   partials.  A device error inside an add fails the duty: later adds are call errors.
+ * Threading: calls on one duty are serialised by the library; calls on different duties, and every
+ * other entry point, may run concurrently.  Every call is blocking.
+ * Devices: the groups are sharded over the devices of the mask in contiguous ranges, as
+ * hbls_slot_select_batch shards them; each shard owns its groups' state and its own message table.
+ * A partial goes to the shard of its group, a verify-only partial i of n to shard i nd / n.  One
+ * shard's add is not chunked: an add beyond the workspace's reach fails.
+ * Caches: the device entry's pipeline (learned key cache, ladder tables, batched subgroup test);
+ * the decompressed-signature cache is not written. */
+int hbls_duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored,
+                   uint64_t* duty);
+int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                  const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
+                  const int64_t* share_idx, size_t n, uint8_t* vstatus, uint8_t* stored,
+                  uint32_t* first_serial, uint32_t* fired, size_t* n_fired, uint32_t* chosen,
+                  uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus);
+int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag);
+int hbls_duty_stats(uint64_t duty, uint64_t* out, size_t n);
+int hbls_duty_close(uint64_t duty);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
