@@ -375,12 +375,18 @@ DEVBLOCKS_HASH_UNITS = [("devblocks_h2c.hip", [f"-DDB_H2C={k}"], f"h2c{k}") for 
 # pipeline.hip whole, so its compile time is that file's own.
 DEVBLOCKS_PAIR = "pair"
 DEVBLOCKS_PAIR_UNITS = [("devblocks_pair.hip", [], "pair"), ("devblocks_vgroup.hip", [], "vgroup")]
+# The combination and verdict kernels of the batched verification (tests/test_gpu_vbatch.py) are a
+# fifth harness, libhbls_devblocksvb.so: one unit, which compiles the product's vbatch.hip itself
+# (fp.h's default lanes; vbatch.hip sets its own HB_FAST_FPMUL).  Not split: it includes vbatch.hip
+# whole, so its compile time is that file's own.
+DEVBLOCKS_VB = "vb"
+DEVBLOCKS_VB_UNITS = [("devblocks_vbatch.hip", [], "vbatch")]
 # the product sources a harness's units compile themselves, hashed into that harness's id
 DEVBLOCKS_PRODUCT_SOURCES = {DEVBLOCKS_CURVE: ["msm.hip"], DEVBLOCKS_HASH: ["hashsplit.hip"],
-                             DEVBLOCKS_PAIR: ["pipeline.hip", "vgroup.hip"]}
+                             DEVBLOCKS_PAIR: ["pipeline.hip", "vgroup.hip"], DEVBLOCKS_VB: ["vbatch.hip"]}
 # the harnesses with a library and an id of their own, next to the block builds
 DEVBLOCKS_OWN = {DEVBLOCKS_CURVE: DEVBLOCKS_CURVE_UNITS, DEVBLOCKS_HASH: DEVBLOCKS_HASH_UNITS,
-                 DEVBLOCKS_PAIR: DEVBLOCKS_PAIR_UNITS}
+                 DEVBLOCKS_PAIR: DEVBLOCKS_PAIR_UNITS, DEVBLOCKS_VB: DEVBLOCKS_VB_UNITS}
 
 
 def devblocks_units(build: str) -> list:
@@ -397,10 +403,11 @@ def devblocks_path(build: str, root: str = "") -> str:
 
 def devblocks_build_id(build: str = "64", root: str = "") -> str:
     """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
-    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py, tests/test_gpu_pairing.py): sha256 (16 hex
+    harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py, tests/test_gpu_pairing.py,
+    tests/test_gpu_vbatch.py): sha256 (16 hex
     digits) over the harness sources, every header of charon_amd/csrc and the flags of that build --
     what its `db_build_id()` returns.  The block builds ("64", "128") hash every
-    tests/native/devblocks* file but the sources of the curve, hash and pair harnesses; each of those
+    tests/native/devblocks* file but the sources of the curve, hash, pair and vb harnesses; each of those
     hashes its own sources, the shared devblocks*.h and the product sources its units compile
     themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
     import hashlib
@@ -586,8 +593,13 @@ def build_devblocks_pair(force: bool = False, verbose: bool = True) -> str:
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_PAIR])[DEVBLOCKS_PAIR]
 
 
+def build_devblocks_vb(force: bool = False, verbose: bool = True) -> str:
+    """The vb harness (tests/test_gpu_vbatch.py), built and reused as build_devblocks' builds."""
+    return build_devblocks(force, verbose, builds=[DEVBLOCKS_VB])[DEVBLOCKS_VB]
+
+
 def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
-    """The block harnesses and the curve, hash and pair harnesses, their units compiled side by side"""
+    """The block harnesses and the curve, hash, pair and vb harnesses, their units compiled side by side"""
     return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + list(DEVBLOCKS_OWN))
 
 

@@ -3,7 +3,7 @@
 // History: built with r01's register-convention product subroutine (a hand-written routine
 // entered through inline asm the compiler could not see into), this kernel returned a wrong group
 // sum -- a point off the curve -- on the GPU, deterministically, while the same source built with
-// a compiler-visible product was exact (tests/native/devcheck_vb.hip).  That
+// a compiler-visible product was exact (a device harness of that time).  That
 // subroutine is gone; the kernel is compiled like the other fast units.
 #define HB_FAST_FPMUL 1
 #include "lines.h"

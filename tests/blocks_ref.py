@@ -733,3 +733,119 @@ def f12_of_words(w):
 
 def f12_words(c, upper=False):
     return [x for lane in poly_to_raw(c, upper) for v in lane for x in words(v)]
+
+
+# ---- the batched verification's combination (vbatch.hip; tests/native/devblocks_vbatch.hip,
+# tests/test_gpu_vbatch.py) ----
+# Coefficients: the digest is hashlib's SHA-256 over the 8 key words and the stream position, big-endian.
+# r = a + b lambda with lambda = -x^2 mod r (rlc.h), the eigenvalue of phi on G1 and of -psi^2 on G2.
+LAMBDA = (-B.X_PARAM ** 2) % B.R
+SPARSE_DIGITS = 22
+SPARSE_PAIRS = [(1, 0), (0, 1), (1, 1), (1, -1)]  # entry d & 3, negated when d & 4 (ec28.h RLC_DIGITS)
+
+
+def rlc_hash_words(key, item):
+    """the eight big-endian words of SHA-256(key words || item)"""
+    import hashlib
+    d = hashlib.sha256(b"".join(int(w).to_bytes(4, "big") for w in key) + int(item).to_bytes(4, "big")).digest()
+    return [int.from_bytes(d[4 * k:4 * k + 4], "big") for k in range(8)]
+
+
+def rlc_coeffs(key, item):
+    """the dense pair (a, b) of stream position `item`.  (A digest whose first 64 bits are zero
+    would give (1, 0) on the device; reaching that line takes a hash preimage, so it is not restated.)"""
+    h = rlc_hash_words(key, item)
+    assert h[0] | h[1]
+    return h[0], h[1]
+
+
+def rlc_record(key, item):
+    """the sparse record of stream position `item`: 10 + 10 + 2 three-bit digits, word 3 = usable"""
+    h = rlc_hash_words(key, item)
+    return h[0] & 0x3FFFFFFF, h[1] & 0x3FFFFFFF, h[2] & 0x3F, 1
+
+
+def sparse_ab(rec):
+    """(A, B) of a sparse record: A = sum u_j 4^j, B = sum v_j 4^j; digit j is bits 3 (j mod 10) .. + 2
+    of word j // 10"""
+    A = Bv = 0
+    for j in range(SPARSE_DIGITS):
+        d = (rec[j // 10] >> (3 * (j % 10))) & 7
+        u, v = SPARSE_PAIRS[d & 3]
+        if d & 4:
+            u, v = -u, -v
+        A += u * 4 ** j
+        Bv += v * 4 ** j
+    return A, Bv
+
+
+def rlc_scalar(a, b):
+    return (a + b * LAMBDA) % B.R
+
+
+class FixedBase:
+    """[k] base for many k: a table of d 16^w base (oracle additions), summed with mixed Jacobian
+    additions in Python integers and one inversion.  test_blocks_ref.py holds it against the oracle."""
+
+    def __init__(self, field, base):
+        self.field, self.F, self.base = field, FIELD_OPS[field], base
+        self.tab, self._memo = [], {}
+        w = base
+        for _ in range(64):
+            row, acc = [None], None
+            for _ in range(15):
+                acc = ec_add(field, acc, w)
+                row.append(acc)
+            self.tab.append(row)
+            w = ec_add(field, row[15], w)
+
+    def _madd(self, J, q):
+        F = self.F
+        if J is None:
+            return q[0], q[1], F.one
+        X, Y, Z = J
+        zz = F.mul(Z, Z)
+        h, r = F.sub(F.mul(q[0], zz), X), F.sub(F.mul(q[1], F.mul(zz, Z)), Y)
+        if h == F.zero:  # the same x: fall back to the oracle's law
+            zi = F.inv(Z)
+            zi2 = F.mul(zi, zi)
+            s = ec_add(self.field, (F.mul(X, zi2), F.mul(Y, F.mul(zi2, zi))), q)
+            return None if s is None else (s[0], s[1], F.one)
+        hh = F.mul(h, h)
+        hhh, v = F.mul(h, hh), F.mul(X, hh)
+        x3 = F.sub(F.sub(F.mul(r, r), hhh), F.add(v, v))
+        return x3, F.sub(F.mul(r, F.sub(v, x3)), F.mul(Y, hhh)), F.mul(Z, h)
+
+    def mul(self, k):
+        k %= B.R
+        if k not in self._memo:
+            J, F = None, self.F
+            for w in range(64):
+                d = (k >> (4 * w)) & 15
+                if d:
+                    J = self._madd(J, self.tab[w][d])
+            if J is not None:
+                zi = F.inv(J[2])
+                zi2 = F.mul(zi, zi)
+                J = (F.mul(J[0], zi2), F.mul(J[1], F.mul(zi2, zi)))
+            self._memo[k] = J
+        return self._memo[k]
+
+
+def plan_chunks(grp_off, cmax):
+    """The chunk plan of the comment above vbatch.hip k_plan_count: group g's items cut into
+    ceil(size / cmax) nearly equal chunks of consecutive items -> (cnt, coff, cfirst, ccount); chunk k
+    of nc covers [k size // nc, (k + 1) size // nc); bit 31 of ccount marks a group of ONE item"""
+    ng = len(grp_off) - 1
+    cnt = [(grp_off[g + 1] - grp_off[g] + cmax - 1) // cmax for g in range(ng)]
+    coff = [0]
+    for c in cnt:
+        coff.append(coff[-1] + c)
+    cfirst, ccount = [], []
+    for g in range(ng):
+        b, sz = grp_off[g], grp_off[g + 1] - grp_off[g]
+        for k in range(cnt[g]):
+            lo, hi = k * sz // cnt[g], (k + 1) * sz // cnt[g]
+            cfirst.append(b + lo)
+            ccount.append((hi - lo) | (0x80000000 if sz == 1 else 0))
+    return cnt, coff, cfirst, ccount

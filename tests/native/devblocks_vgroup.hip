@@ -1,6 +1,7 @@
 // TEST-ONLY device block harness, the group stage: this unit compiles the product's
 // charon_amd/csrc/vgroup.hip itself (fp.h's default HB_ARG_LANES, as in the library) and runs
-// launch_slines, launch_group_prep (its three kernels) and launch_batch_sum on explicit raw words.
+// launch_slines, launch_group_prep (its three kernels), launch_batch_sum and the verdict launchers
+// (launch_batch_verdict, launch_slot_verdict, launch_first_group, launch_first_item) on explicit raw words.
 // The second unit of the pair harness (devblocks_pair.hip: the terms are written there): in/out
 // arrays pre-filled by the caller and copied back in full, every index checked on the host first.
 #include "../../charon_amd/csrc/vgroup.hip"
@@ -136,3 +137,59 @@ extern "C" int db_batch_sum(uint32_t ng, uint32_t k, const uint32_t* gS, uint32_
   if (const int rc = db_finish()) return rc;
   return io.fetch();
 }
+
+// launch_batch_verdict (k_first_batch first when `first` is given, as the launcher issues them).
+// gst: ng bytes; bver: n_bver >= ceil(ng / fe_batch) bytes; gver: n_buf >= ng bytes, list: list_len >=
+// ng words, count: one word (0 on entry), first: one word or null -- all in/out
+extern "C" int db_batch_verdict(uint32_t ng, const uint8_t* gst, const uint8_t* bver, uint32_t n_bver, uint32_t fe_batch,
+                                uint8_t* gver, uint32_t n_buf, uint32_t* list, uint32_t list_len, uint32_t* count,
+                                int guard, uint32_t* first, uint32_t g0) {
+  if (ng < 1 || !gst || !bver || !gver || ng > n_buf || !list || ng > list_len || !count || *count != 0 || guard > 255)
+    return DB_E_ARG;
+  const uint32_t fb = fe_batch ? fe_batch : FE_BATCH;
+  if ((ng + fb - 1) / fb > n_bver || (uint64_t)g0 + ng > 0xffffffffull) return DB_E_ARG;
+  DbIo io;
+  const uint8_t *dgst, *dbver, *dg;
+  uint8_t* dgver;
+  uint32_t *dlist, *dcount, *dfirst;
+  DB_IN(io, dgst, gst, ng);
+  DB_IN(io, dbver, bver, n_bver);
+  DB_IO(io, dgver, gver, n_buf);
+  DB_IO(io, dlist, list, (size_t)list_len * 4);
+  DB_IO(io, dcount, count, 4);
+  DB_IO(io, dfirst, first, 4);
+  if (const int rc = io.guard(&dg, guard)) return rc;
+  launch_batch_verdict(dgst, dbver, ng, dgver, dlist, dcount, 0, dg, fe_batch, dfirst, g0);
+  if (const int rc = db_finish()) return rc;
+  return io.fetch();
+}
+
+// launch_slot_verdict.  gst: ng bytes; sfail: two bytes, gver: n_buf >= ng bytes, in/out
+extern "C" int db_slot_verdict(uint32_t ng, const uint8_t* gst, uint8_t* sfail, uint8_t* gver, uint32_t n_buf) {
+  if (ng < 1 || !gst || !sfail || !gver || ng > n_buf) return DB_E_ARG;
+  DbIo io;
+  const uint8_t* dgst;
+  uint8_t *dsfail, *dgver;
+  DB_IN(io, dgst, gst, ng);
+  DB_IO(io, dsfail, sfail, 2);
+  DB_IO(io, dgver, gver, n_buf);
+  launch_slot_verdict(dgst, dsfail, ng, dgver, 0);
+  if (const int rc = db_finish()) return rc;
+  return io.fetch();
+}
+
+// launch_first_group / launch_first_item.  bytes: n of them; first: one word, in/out
+static int db_first(bool item, const uint8_t* bytes, uint32_t n, uint32_t* first) {
+  if (!bytes || n < 1 || !first) return DB_E_ARG;
+  DbIo io;
+  const uint8_t* db;
+  uint32_t* dfirst;
+  DB_IN(io, db, bytes, n);
+  DB_IO(io, dfirst, first, 4);
+  if (item) launch_first_item(db, n, dfirst, 0);
+  else launch_first_group(db, n, dfirst, 0);
+  if (const int rc = db_finish()) return rc;
+  return io.fetch();
+}
+extern "C" int db_first_group(const uint8_t* gver, uint32_t n_groups, uint32_t* first) { return db_first(false, gver, n_groups, first); }
+extern "C" int db_first_item(const uint8_t* status, uint32_t n, uint32_t* first) { return db_first(true, status, n, first); }

@@ -219,3 +219,80 @@ def test_miller_reference_matches_host_lines(hc):
     assert len(w) == R.F12_WORDS and R.f12_of_words(w)[0] == f and min(R.f12_of_words(w)[1]) >= B.P
     lw = [x for c in lazy[3] for v in c for x in R.words(R.mont(v))]
     assert len(lw) == R.LINE_WORDS and R.line_of_words(lw)[0] == lazy[3]
+
+
+def test_fixed_base_matches_the_oracle():
+    """blocks_ref.FixedBase (the expectations of tests/test_gpu_vbatch.py) against the oracle's
+    scalar multiplication on both curves: edge scalars, random ones, and a base that is a multiple"""
+    rng = random.Random(3101)
+    for field, gen, mul in ((1, B.G1_GEN, B.g1_mul), (2, B.g2_mul(B.G2_GEN, 77), B.g2_mul)):
+        fb = R.FixedBase(field, gen)
+        for k in [0, 1, 2, 15, 16, 17, B.R - 1, B.R, B.R + 5, R.LAMBDA, (1 << 255) % B.R] + \
+                [rng.randrange(B.R) for _ in range(4)]:
+            assert fb.mul(k) == mul(gen, k % B.R), (field, k)
+
+
+def test_rlc_restatements_match_host_check(hc):
+    """The restated coefficients (hashlib), the eigenvalue and the sparse digit table against the host
+    check: hc_rlc_coeffs word for word; the dense and sparse chunk sums (hc_rlc_sum_g1, _g1_sparse,
+    _g2_sparse, _g2_lazy) equal ONE scalar multiplication [sum r_i k_i] of the base, with keys k_i G1
+    and signatures k_i Q -- how tests/test_gpu_vbatch.py computes every expectation."""
+    rng = random.Random(3102)
+    key = [rng.getrandbits(32) for _ in range(8)]
+    ab = (ctypes.c_uint32 * 2)()
+    for item in [0, 1, 2, 63, 64, 65, 0x7FFFFFFF, 0x80000000, 0xFFFFFFFF] + [rng.getrandbits(32) for _ in range(20)]:
+        hc.hc_rlc_coeffs((ctypes.c_uint32 * 8)(*key), item, ab)
+        assert (ab[0], ab[1]) == R.rlc_coeffs(key, item), item
+        rec = R.rlc_record(key, item)
+        assert rec[0] == ab[0] & 0x3FFFFFFF and rec[1] == ab[1] & 0x3FFFFFFF and rec[2] < 64 and rec[3] == 1
+    assert R.rlc_coeffs(key, 1) != R.rlc_coeffs(key, 2) and R.rlc_coeffs(key[::-1], 1) != R.rlc_coeffs(key, 1)
+    # the digit table: every three-bit digit at every position of a record
+    for j in range(R.SPARSE_DIGITS):
+        for d in range(8):
+            rec = [0, 0, 0, 1]
+            rec[j // 10] = d << (3 * (j % 10))
+            u, v = R.SPARSE_PAIRS[d & 3]
+            sgn = -1 if d & 4 else 1
+            # the other positions hold digit 0 = (1, 0)
+            rest = sum(4 ** i for i in range(R.SPARSE_DIGITS) if i != j)
+            assert R.sparse_ab(rec) == (sgn * u * 4 ** j + rest, sgn * v * 4 ** j)
+    Q = B.g2_mul(B.G2_GEN, 0x1234567)
+    f1, f2 = R.FixedBase(1, B.G1_GEN), R.FixedBase(2, Q)
+    for fn in ("hc_rlc_sum_g1", "hc_rlc_sum_g1_sparse", "hc_rlc_sum_g2_sparse", "hc_rlc_sum_g2_lazy"):
+        getattr(hc, fn).argtypes = [ctypes.c_int, ctypes.c_char_p, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p]
+    for k in (1, 5, 16):
+        ks = [rng.randrange(1, B.R) for _ in range(k)]
+        pks = b"".join(B.g1_compress(f1.mul(s)) for s in ks)
+        sigs = b"".join(B.g2_compress(f2.mul(s)) for s in ks)
+        dense = [R.rlc_coeffs(key, 100 + i) for i in range(k)]
+        recs = [R.rlc_record(key, 100 + i) for i in range(k)]
+        s_dense = sum(R.rlc_scalar(a, b) * s for (a, b), s in zip(dense, ks)) % B.R
+        s_sparse = sum(R.rlc_scalar(*R.sparse_ab(r)) * s for r, s in zip(recs, ks)) % B.R
+        flat2 = (ctypes.c_uint32 * (2 * k))(*[x for p in dense for x in p])
+        flat4 = (ctypes.c_uint32 * (4 * k))(*[x for r in recs for x in r])
+        o48, o96 = ctypes.create_string_buffer(48), ctypes.create_string_buffer(96)
+        assert hc.hc_rlc_sum_g1(k, pks, flat2, o48) == 0 and o48.raw == B.g1_compress(f1.mul(s_dense))
+        assert hc.hc_rlc_sum_g2_lazy(k, sigs, flat2, o96) == 0 and o96.raw == B.g2_compress(f2.mul(s_dense))
+        assert hc.hc_rlc_sum_g1_sparse(k, pks, flat4, o48) == 0 and o48.raw == B.g1_compress(f1.mul(s_sparse))
+        assert hc.hc_rlc_sum_g2_sparse(k, sigs, flat4, o96) == 0 and o96.raw == B.g2_compress(f2.mul(s_sparse))
+
+
+def test_plan_restatement_properties():
+    """blocks_ref.plan_chunks: the chunks of a group partition its items in order, sizes differ by at
+    most one and none exceeds cmax, bit 31 exactly for groups of one, the total within n // cmax + ng"""
+    rng = random.Random(3103)
+    for cmax in (1, 2, 3, 16):
+        sizes = [rng.choice([0, 1, 2, 15, 16, 17, 31, 32, 33, 100]) for _ in range(40)]
+        off = [0]
+        for s in sizes:
+            off.append(off[-1] + s)
+        cnt, coff, cfirst, ccount = R.plan_chunks(off, cmax)
+        assert coff[-1] == len(cfirst) <= off[-1] // cmax + len(sizes)
+        for g, s in enumerate(sizes):
+            cs = [(cfirst[c], ccount[c] & 0x7FFFFFFF, ccount[c] >> 31) for c in range(coff[g], coff[g + 1])]
+            assert sum(c[1] for c in cs) == s and all(c[2] == (s == 1) for c in cs)
+            assert not cs or (max(c[1] for c in cs) - min(c[1] for c in cs) <= 1 and max(c[1] for c in cs) <= cmax)
+            pos = off[g]
+            for f, n, _ in cs:
+                assert f == pos and n >= 1
+                pos += n

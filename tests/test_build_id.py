@@ -128,7 +128,7 @@ def test_curve_harness_id_is_its_own(tmp_path):
         shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
     curve = build.DEVBLOCKS_CURVE
     assert {u[0] for u in build.devblocks_units(curve)} == {"devblocks_curve.hip", "devblocks_msm.hip"}
-    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR]
+    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB]
             for u in build.devblocks_units(b)} == {f for f in mine if f.endswith(".hip")}  # every source is built
     cid = build.devblocks_build_id(curve, root=root)
     assert cid == build.devblocks_build_id(curve) and cid.startswith(build.DEVBLOCKS_PREFIX)
@@ -211,7 +211,7 @@ def test_hash_harness_id_is_its_own(tmp_path):
         build.build_devblocks_all()
     finally:
         build.build_devblocks = real
-    assert sorted(seen["builds"]) == sorted(others + [hsh, build.DEVBLOCKS_PAIR])
+    assert sorted(seen["builds"]) == sorted(others + [hsh, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB])
 
 
 def test_pair_harness_id_is_its_own(tmp_path):
@@ -220,7 +220,7 @@ def test_pair_harness_id_is_its_own(tmp_path):
     sources its units compile themselves (pipeline.hip, vgroup.hip) change its id; an unrelated file or
     another harness's source does not.  The other harnesses' ids do not move with a pair source,
     pipeline.hip or vgroup.hip; all the ids differ; every devblocks*.hip belongs to exactly one
-    harness; build_devblocks_all builds it."""
+    harness (the vb harness among them); build_devblocks_all builds it."""
     from charon_amd import build
     root = _copy_harness_tree(tmp_path)
     native = os.path.join(ROOT, "tests", "native")
@@ -235,7 +235,7 @@ def test_pair_harness_id_is_its_own(tmp_path):
     # pipeline.hip sets its own HB_FAST_FPMUL and HB_ARG_LANES; vgroup.hip takes the default lanes: no such flag
     assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(pair) for d in u[1])
     assert build.devblocks_flags(pair) == []
-    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH]
+    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_VB]
     every = others + [pair]
     owner = {}
     for b in every:  # every source in exactly one harness (the two block builds share theirs)
@@ -247,11 +247,12 @@ def test_pair_harness_id_is_its_own(tmp_path):
         return {b: build.devblocks_build_id(b, root=root) for b in which}
     pid = build.devblocks_build_id(pair, root=root)
     assert pid == build.devblocks_build_id(pair) and pid.startswith(build.DEVBLOCKS_PREFIX)
-    assert len(set(ids(every).values())) == 5
+    assert len(set(ids(every).values())) == 6
     for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
                 "charon_amd/csrc/vbatch.hip", "tests/native/hostcheck.cpp", "include/hipbls.h",
                 "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip",
-                "tests/native/devblocks_msm.hip", "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip"):
+                "tests/native/devblocks_msm.hip", "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip",
+                "tests/native/devblocks_vbatch.hip"):
         with open(tmp_path / rel, "a") as f:
             f.write("\n// touched\n")
     assert build.devblocks_build_id(pair, root=root) == pid
@@ -281,3 +282,78 @@ def test_pair_harness_id_is_its_own(tmp_path):
     finally:
         build.build_devblocks = real
     assert pair in seen["builds"] and sorted(seen["builds"]) == sorted(every)
+
+
+def test_vb_harness_id_is_its_own(tmp_path):
+    """The vb harness (tests/native/devblocks_vbatch.hip; tests/test_gpu_vbatch.py) on the same terms:
+    its one source, the shared devblocks.h, every csrc header and the product source its unit compiles
+    itself (vbatch.hip) change its id; an unrelated file or another harness's source does not.
+    Touching vbatch.hip moves this id (and the library's) and no other harness's; all the ids differ;
+    every devblocks*.hip belongs to exactly one harness; build_devblocks_all builds it next to the
+    others."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    vbh = build.DEVBLOCKS_VB
+    assert vbh == "vb" and vbh in build.DEVBLOCKS_OWN
+    assert [u[0] for u in build.devblocks_units(vbh)] == ["devblocks_vbatch.hip"]  # one unit
+    assert build.DEVBLOCKS_PRODUCT_SOURCES[vbh] == ["vbatch.hip"]
+    # vbatch.hip sets its own HB_FAST_FPMUL and takes fp.h's default lanes: the build passes neither
+    assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(vbh) for d in u[1])
+    assert build.devblocks_flags(vbh) == []
+    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR]
+    every = others + [vbh]
+    owner = {}
+    for b in every:  # every source in exactly one harness (the two block builds share theirs)
+        for src in {u[0] for u in build.devblocks_units(b)}:
+            owner.setdefault(src, set()).add("blocks" if b in build.DEVBLOCKS_BUILDS else b)
+    assert set(owner) == {f for f in mine if f.endswith(".hip")} and all(len(v) == 1 for v in owner.values())
+    assert owner["devblocks_vbatch.hip"] == {vbh}
+
+    def ids(which):
+        return {b: build.devblocks_build_id(b, root=root) for b in which}
+    vid = build.devblocks_build_id(vbh, root=root)
+    assert vid == build.devblocks_build_id(vbh) and vid.startswith(build.DEVBLOCKS_PREFIX)
+    assert len(set(ids(every).values())) == 6
+    for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
+                "charon_amd/csrc/pipeline.hip", "charon_amd/csrc/vgroup.hip", "charon_amd/csrc/threshold.hip",
+                "tests/native/hostcheck.cpp", "include/hipbls.h", "tests/native/devblocks_grp.hip",
+                "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip", "tests/native/devblocks_msm.hip",
+                "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip", "tests/native/devblocks_pair.hip",
+                "tests/native/devblocks_vgroup.hip"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    assert build.devblocks_build_id(vbh, root=root) == vid
+    before_others, lib_before = ids(others), _lib.source_build_id(root)
+    for rel in ("tests/native/devblocks_vbatch.hip", "charon_amd/csrc/vbatch.hip"):
+        before = build.devblocks_build_id(vbh, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(vbh, root=root) != before, rel
+        assert ids(others) == before_others, rel
+    assert _lib.source_build_id(root) != lib_before  # vbatch.hip is the library's too
+    for rel in ("tests/native/devblocks.h", "charon_amd/csrc/rlc.h", "charon_amd/csrc/ec28.h", "charon_amd/csrc/layout.h",
+                "charon_amd/csrc/sha256.h", "charon_amd/csrc/fp.h"):
+        before = build.devblocks_build_id(vbh, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(vbh, root=root) != before, rel
+    path = build.devblocks_path(vbh)
+    assert os.path.basename(path) == "libhbls_devblocksvb.so"
+    if os.path.exists(path):  # what build() left in the tree is this tree's
+        assert build.embedded_devblocks_id(path) == build.devblocks_build_id(vbh)
+    assert build.build_devblocks_vb.__doc__
+    seen = {}
+    real = build.build_devblocks
+    try:
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: seen.setdefault("builds", list(builds))
+        build.build_devblocks_all()
+        assert sorted(seen["builds"]) == sorted(every)
+        seen.clear()
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: {b: seen.setdefault("one", b) for b in builds}
+        assert build.build_devblocks_vb() == vbh and seen == {"one": vbh}
+    finally:
+        build.build_devblocks = real
