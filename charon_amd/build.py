@@ -381,12 +381,20 @@ DEVBLOCKS_PAIR_UNITS = [("devblocks_pair.hip", [], "pair"), ("devblocks_vgroup.h
 # whole, so its compile time is that file's own.
 DEVBLOCKS_VB = "vb"
 DEVBLOCKS_VB_UNITS = [("devblocks_vbatch.hip", [], "vbatch")]
+# The threshold-aggregation kernels (tests/test_gpu_threshold.py) are a sixth harness,
+# libhbls_devblocksta.so, on the vb harness's terms: one unit, which compiles the product's
+# threshold.hip itself (fp.h's default lanes; threshold.hip sets its own HB_FAST_FPMUL).  Not split:
+# it includes threshold.hip whole, so its compile time is that file's own.
+DEVBLOCKS_TA = "ta"
+DEVBLOCKS_TA_UNITS = [("devblocks_threshold.hip", [], "threshold")]
 # the product sources a harness's units compile themselves, hashed into that harness's id
 DEVBLOCKS_PRODUCT_SOURCES = {DEVBLOCKS_CURVE: ["msm.hip"], DEVBLOCKS_HASH: ["hashsplit.hip"],
-                             DEVBLOCKS_PAIR: ["pipeline.hip", "vgroup.hip"], DEVBLOCKS_VB: ["vbatch.hip"]}
+                             DEVBLOCKS_PAIR: ["pipeline.hip", "vgroup.hip"], DEVBLOCKS_VB: ["vbatch.hip"],
+                             DEVBLOCKS_TA: ["threshold.hip"]}
 # the harnesses with a library and an id of their own, next to the block builds
 DEVBLOCKS_OWN = {DEVBLOCKS_CURVE: DEVBLOCKS_CURVE_UNITS, DEVBLOCKS_HASH: DEVBLOCKS_HASH_UNITS,
-                 DEVBLOCKS_PAIR: DEVBLOCKS_PAIR_UNITS, DEVBLOCKS_VB: DEVBLOCKS_VB_UNITS}
+                 DEVBLOCKS_PAIR: DEVBLOCKS_PAIR_UNITS, DEVBLOCKS_VB: DEVBLOCKS_VB_UNITS,
+                 DEVBLOCKS_TA: DEVBLOCKS_TA_UNITS}
 
 
 def devblocks_units(build: str) -> list:
@@ -404,10 +412,10 @@ def devblocks_path(build: str, root: str = "") -> str:
 def devblocks_build_id(build: str = "64", root: str = "") -> str:
     """The id embedded in a device block harness (tests/native/devblocks*: the GPU twin of the CPU
     harness, tests/test_gpu_blocks.py, tests/test_gpu_curve.py, tests/test_gpu_hash.py, tests/test_gpu_pairing.py,
-    tests/test_gpu_vbatch.py): sha256 (16 hex
+    tests/test_gpu_vbatch.py, tests/test_gpu_threshold.py): sha256 (16 hex
     digits) over the harness sources, every header of charon_amd/csrc and the flags of that build --
     what its `db_build_id()` returns.  The block builds ("64", "128") hash every
-    tests/native/devblocks* file but the sources of the curve, hash, pair and vb harnesses; each of those
+    tests/native/devblocks* file but the sources of the curve, hash, pair, vb and ta harnesses; each of those
     hashes its own sources, the shared devblocks*.h and the product sources its units compile
     themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
     import hashlib
@@ -598,8 +606,13 @@ def build_devblocks_vb(force: bool = False, verbose: bool = True) -> str:
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_VB])[DEVBLOCKS_VB]
 
 
+def build_devblocks_ta(force: bool = False, verbose: bool = True) -> str:
+    """The ta harness (tests/test_gpu_threshold.py), built and reused as build_devblocks' builds."""
+    return build_devblocks(force, verbose, builds=[DEVBLOCKS_TA])[DEVBLOCKS_TA]
+
+
 def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
-    """The block harnesses and the curve, hash, pair and vb harnesses, their units compiled side by side"""
+    """The block harnesses and the curve, hash, pair, vb and ta harnesses, their units compiled side by side"""
     return build_devblocks(force, verbose, builds=list(DEVBLOCKS_BUILDS) + list(DEVBLOCKS_OWN))
 
 

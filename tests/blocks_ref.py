@@ -849,3 +849,71 @@ def plan_chunks(grp_off, cmax):
             cfirst.append(b + lo)
             ccount.append((hi - lo) | (0x80000000 if sz == 1 else 0))
     return cnt, coff, cfirst, ccount
+
+
+# ---- the threshold aggregation (threshold.hip; tests/native/devblocks_threshold.hip,
+# tests/test_gpu_threshold.py) ----
+# z = |x|: psi acts on G2 as multiplication by x = -z, so sum_i a_i (-1)^i psi^i(sigma) = [sum_i a_i z^i] sigma.
+TA_Z = X_ABS
+TA_SMALL_T = range(2, 17)  # ta_small.h: the member counts the small-scalar split takes
+
+
+def ta_lambda(ids):
+    """lambda_j(0) = prod_{m != j} x_m / (x_m - x_j) per member, the numerator and the denominator as
+    exact Python integers (any signed 64-bit indices) and only their quotient reduced mod r.  A group of
+    one has lambda = 1.  An entry is None where member j itself shows the combine failure: ANOTHER
+    member's index is 0 mod r (the numerator vanishes) or equals x_j mod r (the denominator does)."""
+    if len(ids) == 1:
+        return [1]
+    out = []
+    for j, xj in enumerate(ids):
+        num = den = 1
+        for m, xm in enumerate(ids):
+            if m != j:
+                num *= xm
+                den *= xm - xj
+        out.append(None if num % B.R == 0 or den % B.R == 0 else num * pow(den, -1, B.R) % B.R)
+    return out
+
+
+def ta_digits(v):
+    """the four base-z digits of 0 <= v < z^4, least significant first"""
+    assert 0 <= v < TA_Z ** 4
+    a = [v // TA_Z ** i % TA_Z for i in range(4)]
+    assert sum(d * TA_Z ** i for i, d in enumerate(a)) == v and all(d < TA_Z for d in a)
+    return a
+
+
+def ta_digit_scalar(a):
+    """the scalar of arbitrary digits: sum_i a_i (-1)^i psi^i(sigma) = [sum_i a_i z^i mod r] sigma"""
+    return sum(d * TA_Z ** i for i, d in enumerate(a)) % B.R
+
+
+def ta_small_split(ids):
+    """ta_small.h's form of the coefficients from Python integers: with P = prod x_m, E_j = x_j prod_{m
+    != j} (x_m - x_j) and L = lcm |E_j|: c_j = L / E_j and s = P / L mod r, so lambda_j = s c_j.
+    -> (c, s), or None where the header refuses: t outside 2..16, an index 0, duplicates, |x| >= 2^31, any
+    intermediate beyond 63 bits (the products to E_j and the running lcm only grow in magnitude, so it is
+    the final E_j and L that decide), E_j = -2^63."""
+    import math
+    t = len(ids)
+    if t not in TA_SMALL_T or any(x == 0 or abs(x) >= 1 << 31 for x in ids) or len(set(ids)) != t:
+        return None
+    E = []
+    for j, xj in enumerate(ids):
+        e = xj
+        for m, xm in enumerate(ids):
+            if m != j:
+                e *= xm - xj
+        if not -(1 << 63) < e < (1 << 63):
+            return None
+        E.append(e)
+    L = 1
+    for e in E:
+        L = L * abs(e) // math.gcd(L, abs(e))
+        if L >= 1 << 63:
+            return None
+    Pm = 1
+    for x in ids:
+        Pm *= x
+    return [L // e for e in E], Pm * pow(L, -1, B.R) % B.R

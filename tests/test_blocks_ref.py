@@ -296,3 +296,84 @@ def test_plan_restatement_properties():
             for f, n, _ in cs:
                 assert f == pos and n >= 1
                 pos += n
+
+
+# ---- the threshold aggregation's references (tests/test_gpu_threshold.py) ----
+def test_ta_lambda_matches_the_oracle():
+    """blocks_ref.ta_lambda against oracle.bls12381.lagrange_coeffs_at_zero wherever that is defined,
+    and None entries exactly where a member sees the combine failure; ta_digits recomposes"""
+    import itertools
+    rng = random.Random(3104)
+    sets = [list(c) for t in range(1, 6) for c in itertools.combinations(range(1, 8), t)]
+    sets += [[3, 1, 2], [-1, 5, 2], [1, 64, 65, 130], [2 ** 62 - 1, 1, 2], [-(2 ** 62 - 1), 2 ** 62, 7],
+             [2 ** 63 - 1, -2 ** 63, 1], [2 ** 63 - 1, -2 ** 63, 2 ** 62, -3]]
+    sets += [[rng.randrange(-2 ** 63, 2 ** 63) for _ in range(rng.randrange(1, 18))] for _ in range(40)]
+    for ids in sets:
+        want = B.lagrange_coeffs_at_zero(ids)
+        assert want is not None and R.ta_lambda(ids) == want, ids
+        for lam in want:
+            a = R.ta_digits(lam)
+            assert len(a) == 4 and R.ta_digit_scalar(a) == lam
+    assert R.TA_Z == -B.X_PARAM == 0xd201000000010000 and B.R < R.TA_Z ** 4
+    for ids, none_at in (([0, 1, 2], [1, 2]), ([1, 1, 2], [0, 1]), ([0, 0, 3], [0, 1, 2]), ([4, 5, 4, 0], [0, 1, 2]),
+                         ([5, 7, 5 + B.R], None)):
+        assert B.lagrange_coeffs_at_zero(ids) is None
+        if none_at is not None:  # the last set is no set of 64-bit indices: the oracle's rule is mod r
+            assert [j for j, lam in enumerate(R.ta_lambda(ids)) if lam is None] == none_at, ids
+    assert R.ta_lambda([0]) == [1] == B.lagrange_coeffs_at_zero([0])
+
+
+def test_ta_small_split_matches_the_host_check(hc):
+    """blocks_ref.ta_small_split against hc_ta_small (ta_small.h compiled for the CPU) over every 2- to
+    7-subset of 1..10 -- c_j and s equal, and lambda_j = s c_j -- and over the refusal list of
+    tests/test_hostcheck.py::test_ta_small_split, with the other refusals the header names"""
+    import itertools
+    c, s = (ctypes.c_int64 * 16)(), ctypes.create_string_buffer(32)
+
+    def host(ids):
+        if not hc.hc_ta_small((ctypes.c_int64 * len(ids))(*ids), len(ids), c, s):
+            return None
+        return [int(c[j]) for j in range(len(ids))], int.from_bytes(s.raw, "big")
+    n = 0
+    for t in range(2, 8):
+        for ids in itertools.combinations(range(1, 11), t):
+            got = R.ta_small_split(list(ids))
+            assert got is not None and got == host(ids), ids
+            assert [got[1] * cj % B.R for cj in got[0]] == R.ta_lambda(list(ids)), ids
+            n += 1
+    assert n == sum(len(list(itertools.combinations(range(10), t))) for t in range(2, 8))
+    edge = [-2 ** 30, 2 ** 30, -2 ** 30 + 1, -2 ** 30 + 4]  # E_0 = -2^63 exactly
+    for bad in ([0, 1, 2], [1, 1, 2], [5], list(range(1, 18)), edge, [1, 2 ** 31], [1, -2 ** 31], [2 ** 31 - 1, -2 ** 31 + 1, 5, 9],
+                list(range(1, 65, 4))):
+        assert R.ta_small_split(bad) is None and host(bad) is None, bad
+    rng = random.Random(3105)
+    seen = set()
+    for _ in range(300):  # shuffled, signed and wide sets: the two agree on taking or refusing, and on the values
+        ids = rng.sample(range(-40, 41), rng.randrange(2, 17)) if rng.random() < 0.7 else \
+            [rng.randrange(-2 ** 31 + 1, 2 ** 31) for _ in range(rng.randrange(2, 5))]
+        got = R.ta_small_split(ids)
+        assert got == host(ids), ids
+        seen.add(got is None)
+        if got:
+            assert [got[1] * cj % B.R for cj in got[0]] == R.ta_lambda(ids), ids
+    assert seen == {True, False}
+    assert R.ta_small_split([1, 2 ** 31 - 1]) == host([1, 2 ** 31 - 1]) is not None
+
+
+def test_ta_digit_sum_is_one_fixed_base_multiplication():
+    """sum_i a_i (-1)^i psi^i(sigma) = [(sum_i a_i z^i) k mod r] Q for sigma = [k] Q, against the oracle's
+    g2_psi, for digit vectors that are no digits of a reduced scalar too (z - 1 in every position)"""
+    rng = random.Random(3106)
+    Q = B.g2_mul(B.G2_GEN, rng.randrange(1, B.R))
+    fb = R.FixedBase(2, Q)
+    z = R.TA_Z
+    for a in ([1, 0, 0, 0], [0, 1, 0, 0], [0, 0, 1, 0], [0, 0, 0, 1], [z - 1] * 4, [0, 0, 0, 0],
+              [rng.randrange(z) for _ in range(4)], R.ta_digits(rng.randrange(B.R))):
+        k = rng.randrange(1, B.R)
+        sigma, acc = fb.mul(k), None
+        w = sigma
+        for i in range(4):
+            term = B.g2_mul(w, a[i])
+            acc = B.g2_add(acc, B.g2_neg(term) if i & 1 else term)
+            w = B.g2_psi(w)
+        assert acc == fb.mul(R.ta_digit_scalar(a) * k), a

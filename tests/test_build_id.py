@@ -128,7 +128,8 @@ def test_curve_harness_id_is_its_own(tmp_path):
         shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
     curve = build.DEVBLOCKS_CURVE
     assert {u[0] for u in build.devblocks_units(curve)} == {"devblocks_curve.hip", "devblocks_msm.hip"}
-    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB]
+    assert {u[0] for b in list(build.DEVBLOCKS_BUILDS) + [curve, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB,
+                                                        build.DEVBLOCKS_TA]
             for u in build.devblocks_units(b)} == {f for f in mine if f.endswith(".hip")}  # every source is built
     cid = build.devblocks_build_id(curve, root=root)
     assert cid == build.devblocks_build_id(curve) and cid.startswith(build.DEVBLOCKS_PREFIX)
@@ -211,7 +212,7 @@ def test_hash_harness_id_is_its_own(tmp_path):
         build.build_devblocks_all()
     finally:
         build.build_devblocks = real
-    assert sorted(seen["builds"]) == sorted(others + [hsh, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB])
+    assert sorted(seen["builds"]) == sorted(others + [hsh, build.DEVBLOCKS_PAIR, build.DEVBLOCKS_VB, build.DEVBLOCKS_TA])
 
 
 def test_pair_harness_id_is_its_own(tmp_path):
@@ -235,7 +236,8 @@ def test_pair_harness_id_is_its_own(tmp_path):
     # pipeline.hip sets its own HB_FAST_FPMUL and HB_ARG_LANES; vgroup.hip takes the default lanes: no such flag
     assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(pair) for d in u[1])
     assert build.devblocks_flags(pair) == []
-    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_VB]
+    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_VB,
+                                             build.DEVBLOCKS_TA]
     every = others + [pair]
     owner = {}
     for b in every:  # every source in exactly one harness (the two block builds share theirs)
@@ -247,9 +249,10 @@ def test_pair_harness_id_is_its_own(tmp_path):
         return {b: build.devblocks_build_id(b, root=root) for b in which}
     pid = build.devblocks_build_id(pair, root=root)
     assert pid == build.devblocks_build_id(pair) and pid.startswith(build.DEVBLOCKS_PREFIX)
-    assert len(set(ids(every).values())) == 6
+    assert len(set(ids(every).values())) == 7
     for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
-                "charon_amd/csrc/vbatch.hip", "tests/native/hostcheck.cpp", "include/hipbls.h",
+                "charon_amd/csrc/vbatch.hip", "charon_amd/csrc/threshold.hip", "tests/native/devblocks_threshold.hip",
+                "tests/native/hostcheck.cpp", "include/hipbls.h",
                 "tests/native/devblocks_grp.hip", "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip",
                 "tests/native/devblocks_msm.hip", "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip",
                 "tests/native/devblocks_vbatch.hip"):
@@ -305,7 +308,7 @@ def test_vb_harness_id_is_its_own(tmp_path):
     assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(vbh) for d in u[1])
     assert build.devblocks_flags(vbh) == []
     others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR]
-    every = others + [vbh]
+    every = others + [vbh, build.DEVBLOCKS_TA]
     owner = {}
     for b in every:  # every source in exactly one harness (the two block builds share theirs)
         for src in {u[0] for u in build.devblocks_units(b)}:
@@ -317,10 +320,10 @@ def test_vb_harness_id_is_its_own(tmp_path):
         return {b: build.devblocks_build_id(b, root=root) for b in which}
     vid = build.devblocks_build_id(vbh, root=root)
     assert vid == build.devblocks_build_id(vbh) and vid.startswith(build.DEVBLOCKS_PREFIX)
-    assert len(set(ids(every).values())) == 6
+    assert len(set(ids(every).values())) == 7
     for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
                 "charon_amd/csrc/pipeline.hip", "charon_amd/csrc/vgroup.hip", "charon_amd/csrc/threshold.hip",
-                "tests/native/hostcheck.cpp", "include/hipbls.h", "tests/native/devblocks_grp.hip",
+                "tests/native/devblocks_threshold.hip", "tests/native/hostcheck.cpp", "include/hipbls.h", "tests/native/devblocks_grp.hip",
                 "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip", "tests/native/devblocks_msm.hip",
                 "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip", "tests/native/devblocks_pair.hip",
                 "tests/native/devblocks_vgroup.hip"):
@@ -355,5 +358,83 @@ def test_vb_harness_id_is_its_own(tmp_path):
         seen.clear()
         build.build_devblocks = lambda force=False, verbose=True, builds=None: {b: seen.setdefault("one", b) for b in builds}
         assert build.build_devblocks_vb() == vbh and seen == {"one": vbh}
+    finally:
+        build.build_devblocks = real
+
+
+def test_ta_harness_id_is_its_own(tmp_path):
+    """The ta harness (tests/native/devblocks_threshold.hip; tests/test_gpu_threshold.py) on the same
+    terms: its one source, the shared devblocks.h, every csrc header and the product source its unit
+    compiles itself (threshold.hip) change its id; an unrelated file or another harness's source does
+    not.  Touching threshold.hip moves this id (and the library's) and no other harness's; touching
+    devblocks_threshold.hip moves this id alone; all the ids differ; every devblocks*.hip belongs to
+    exactly one harness; build_devblocks_all builds it next to the others."""
+    from charon_amd import build
+    root = _copy_harness_tree(tmp_path)
+    native = os.path.join(ROOT, "tests", "native")
+    mine = sorted(f for f in os.listdir(native) if f.startswith("devblocks") and f.endswith((".hip", ".h")))
+    for f in mine:
+        shutil.copy(os.path.join(native, f), tmp_path / "tests" / "native")
+    ta = build.DEVBLOCKS_TA
+    assert ta == "ta" and ta in build.DEVBLOCKS_OWN
+    assert [u[0] for u in build.devblocks_units(ta)] == ["devblocks_threshold.hip"]  # one unit
+    assert build.DEVBLOCKS_PRODUCT_SOURCES[ta] == ["threshold.hip"]
+    # threshold.hip sets its own HB_FAST_FPMUL and takes fp.h's default lanes: the build passes neither
+    assert not any("HB_ARG_LANES" in d or "HB_FAST_FPMUL" in d for u in build.devblocks_units(ta) for d in u[1])
+    assert build.devblocks_flags(ta) == []
+    others = list(build.DEVBLOCKS_BUILDS) + [build.DEVBLOCKS_CURVE, build.DEVBLOCKS_HASH, build.DEVBLOCKS_PAIR,
+                                             build.DEVBLOCKS_VB]
+    every = others + [ta]
+    owner = {}
+    for b in every:  # every source in exactly one harness (the two block builds share theirs)
+        for src in {u[0] for u in build.devblocks_units(b)}:
+            owner.setdefault(src, set()).add("blocks" if b in build.DEVBLOCKS_BUILDS else b)
+    assert set(owner) == {f for f in mine if f.endswith(".hip")} and all(len(v) == 1 for v in owner.values())
+    assert owner["devblocks_threshold.hip"] == {ta}
+
+    def ids(which):
+        return {b: build.devblocks_build_id(b, root=root) for b in which}
+    tid = build.devblocks_build_id(ta, root=root)
+    assert tid == build.devblocks_build_id(ta) and tid.startswith(build.DEVBLOCKS_PREFIX)
+    assert len(set(ids(every).values())) == 7
+    for rel in ("charon_amd/csrc/hash.hip", "charon_amd/csrc/msm.hip", "charon_amd/csrc/hashsplit.hip",
+                "charon_amd/csrc/pipeline.hip", "charon_amd/csrc/vgroup.hip", "charon_amd/csrc/vbatch.hip",
+                "charon_amd/csrc/hipbls.hip", "tests/native/hostcheck.cpp", "include/hipbls.h", "tests/native/devblocks_grp.hip",
+                "tests/native/devblocks_leaf.hip", "tests/native/devblocks_curve.hip", "tests/native/devblocks_msm.hip",
+                "tests/native/devblocks_h2c.hip", "tests/native/devblocks_h2c_std.hip", "tests/native/devblocks_pair.hip",
+                "tests/native/devblocks_vgroup.hip", "tests/native/devblocks_vbatch.hip"):
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+    assert build.devblocks_build_id(ta, root=root) == tid
+    before_others, lib_before = ids(others), _lib.source_build_id(root)
+    for rel in ("tests/native/devblocks_threshold.hip", "charon_amd/csrc/threshold.hip"):
+        before = build.devblocks_build_id(ta, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(ta, root=root) != before, rel
+        assert ids(others) == before_others, rel
+        if rel.startswith("tests/"):
+            assert _lib.source_build_id(root) == lib_before  # the harness source is not the library's
+    assert _lib.source_build_id(root) != lib_before  # threshold.hip is the library's too
+    for rel in ("tests/native/devblocks.h", "charon_amd/csrc/ta_small.h", "charon_amd/csrc/tasel.h", "charon_amd/csrc/layout.h",
+                "charon_amd/csrc/ec28.h", "charon_amd/csrc/fr.h", "charon_amd/csrc/fp.h"):
+        before = build.devblocks_build_id(ta, root=root)
+        with open(tmp_path / rel, "a") as f:
+            f.write("\n// touched\n")
+        assert build.devblocks_build_id(ta, root=root) != before, rel
+    path = build.devblocks_path(ta)
+    assert os.path.basename(path) == "libhbls_devblocksta.so"
+    if os.path.exists(path):  # what build() left in the tree is this tree's
+        assert build.embedded_devblocks_id(path) == build.devblocks_build_id(ta)
+    assert build.build_devblocks_ta.__doc__
+    seen = {}
+    real = build.build_devblocks
+    try:
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: seen.setdefault("builds", list(builds))
+        build.build_devblocks_all()
+        assert sorted(seen["builds"]) == sorted(every)
+        seen.clear()
+        build.build_devblocks = lambda force=False, verbose=True, builds=None: {b: seen.setdefault("one", b) for b in builds}
+        assert build.build_devblocks_ta() == ta and seen == {"one": ta}
     finally:
         build.build_devblocks = real
