@@ -285,6 +285,48 @@ def build_dutycheck(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+DUTYSETCHECK_PREFIX = "hbls-dutysetcheck:"
+DUTYSETCHECK_HEADERS = ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h")
+
+
+def dutysetcheck_build_id(root: str = "") -> str:
+    """The id embedded in the set-atomic adds' harness (tests/native/dutysetcheck.cpp,
+    `ds_build_id()`): sha256 over its source, the headers it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "dutysetcheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYSETCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return DUTYSETCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_dutysetcheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_dutysetcheck.so (tests/test_duty_sets_host.py): the host side of
+    hbls_duty_add_sets on the CPU -- set_off's validation, the plan's set ids, the shards' merge, the
+    admission predicate and the storing rule behind it; test-only.  Reused when its embedded id
+    equals the tree's, as build_dutycheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "dutysetcheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_dutysetcheck.so")
+    bid = dutysetcheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-dutysetcheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
 SUBGCHECK_PREFIX = "hbls-subgcheck:"
 SUBGCHECK_HEADERS = ("subgbatch.h", "sha256.h", "hd.h", "vplan.h")
 
@@ -586,6 +628,50 @@ def build_subgdev(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+DUTYSETDEV_PREFIX = "hbls-dutysetdev:"
+
+
+def dutysetdev_build_id(root: str = "") -> str:
+    """The id embedded in the set-atomic adds' device harness (tests/native/dutysetdev.hip,
+    tests/test_gpu_duty_sets_kernels.py; `dsd_build_id()`): sha256 over its source, the device
+    harnesses' shared devblocks.h, the product source it compiles (duty.hip), every header of
+    charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "dutysetdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "duty.hip")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return DUTYSETDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_dutysetdev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_dutysetdev.so: k_duty_set_first, k_duty_gate and k_duty_store behind the
+    gate on the device over explicit words, a harness of its own like build_subgdev; test-only.
+    Reused when its embedded id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "dutysetdev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_dutysetdev.so")
+    bid = dutysetdev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-dutysetdev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DDSD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -649,7 +735,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
     for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
-               build_subgdev):
+               build_subgdev, build_dutysetcheck, build_dutysetdev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

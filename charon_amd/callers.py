@@ -333,10 +333,17 @@ class ParSigDuty:
     entry of the set (in set order) that fails its pre-checks or its verification aborts with
     "invalid partial signature: ..." (parsigex.go:96), a fired validator whose aggregation or
     aggregate verification fails with "threshold aggregate: ..." (sigagg.go:105-119).  A context
-    manager: close() frees the device state, where MemDB.Trim deletes the duty."""
+    manager: close() frees the device state, where MemDB.Trim deletes the duty.
+
+    reject_sets: False admits a set's partials one by one (hbls_duty_add; see store_external on what
+    a set with a failing entry then leaves behind).  True gives the reference's rule exactly
+    (hbls_duty_add_sets): a set with an entry that fails verification stores nothing, fires nothing
+    and leaves the duty as it was.  store_external_many(sets) takes several peers' sets in one call,
+    each with that all-or-nothing boundary of its own, whatever reject_sets is."""
 
     def __init__(self, impl, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
-                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16):
+                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16, reject_sets: bool = False):
+        self._reject_sets = reject_sets
         self._keys = list(dv_pubkeys)
         self._group = {pk: g for g, pk in enumerate(self._keys)}
         self._shares = pubshares_by_key
@@ -355,7 +362,88 @@ class ParSigDuty:
         cnt, fired = self._duty.state()
         return {pk: (cnt[g], fired[g]) for g, pk in enumerate(self._keys)}
 
+    def store_external_many(self, sets: Sequence[Mapping[bytes, ParSig]]) -> List[object]:
+        """Several peers' sets, in arrival order, as ONE hbls_duty_add_sets call.  Per set, what
+        ParSigEx.handle + StoreExternal would have given for it: {pubkey: aggregate} of the validators
+        that fired through it (a fired validator belongs to the set that holds its last member), or the
+        CallerError the reference would have returned -- not raised: a rejected set does not stop the
+        sets behind it, which are stored and fire.  An error of the aggregation stage carries the set's
+        other aggregates as `fired`; a rejected set's error carries an empty one."""
+        pks, msgs, sigs, groups, idx, set_off, pres = [], [], [], [], [], [0], []
+        for signed_set in sets:
+            p, m, s, g, x, pre = self._checked(signed_set)
+            if pre is not None:  # the entries before the failing one are verified only
+                g = [0xFFFFFFFF] * len(p)
+            pks += p
+            msgs += m
+            sigs += s
+            groups += g
+            idx += x
+            set_off.append(len(pks))
+            pres.append(pre)
+        r = self._duty.add_sets(pks, msgs, sigs, groups, idx, set_off)
+        res: List[object] = []
+        for j, pre in enumerate(pres):
+            b, e = set_off[j], set_off[j + 1]
+            if r.set_first[j] is not None:  # the verification loop runs first in the reference: its error wins
+                err = _wrap("invalid partial signature", "invalid signature: " + _verr(r.vstatus[r.set_first[j]]))
+                err.fired = {}
+                res.append(err)
+                continue
+            if pre is not None:
+                err = _wrap("invalid partial signature", pre)
+                err.fired = {}
+                res.append(err)
+                continue
+            out: Dict[bytes, bytes] = {}
+            err = None
+            for k, g in enumerate(r.fired):
+                if not b <= r.chosen[k][-1] - r.first_serial < e:
+                    continue
+                if r.ta_status[k] != OK:
+                    err = err or _wrap("threshold aggregate", status_error("threshold_aggregate", int(r.ta_status[k])))
+                elif r.agg_vstatus[k] != OK:
+                    err = err or _wrap("threshold aggregate",
+                                       "aggregate signature verification failed: " + _verr(int(r.agg_vstatus[k])))
+                else:
+                    out[self._keys[g]] = r.aggregates[k]
+            if err is not None:
+                err.fired = out
+                res.append(err)
+            else:
+                res.append(out)
+        return res
+
+    def _checked(self, signed_set: Mapping[bytes, ParSig]):
+        """The pre-checks of a set in set order, up to the first failing one: the entries that passed
+        (public shares, roots, signatures, groups, share indices) and that failure's text, or None."""
+        pks, msgs, sigs, groups, idx = [], [], [], [], []
+        pre: Optional[str] = None
+        for pk, ps in signed_set.items():
+            shares = self._shares.get(pk)
+            if shares is None or pk not in self._group:
+                pre = "unknown pubkey, not part of cluster lock"
+            elif ps.share_idx not in shares:
+                pre = "invalid shareIdx"
+            elif len(ps.signature) != 96:
+                pre = "signature from core: " + _LEN_ERR
+            elif ps.signature == ZERO_SIG:
+                pre = "invalid signature: no signature found"  # signing.go:107-110
+            if pre is not None:
+                break
+            pks.append(shares[ps.share_idx])
+            msgs.append(ps.signing_root)
+            sigs.append(ps.signature)
+            groups.append(self._group[pk])
+            idx.append(ps.share_idx)
+        return pks, msgs, sigs, groups, idx, pre
+
     def store_external(self, signed_set: Mapping[bytes, ParSig]) -> Dict[bytes, bytes]:
+        if self._reject_sets:
+            res = self.store_external_many([signed_set])[0]
+            if isinstance(res, CallerError):
+                raise res
+            return res
         pks, msgs, sigs, groups, idx = [], [], [], [], []
         pre: Optional[str] = None
         for pk, ps in signed_set.items():  # the pre-checks in set order, up to the first failing one
@@ -390,7 +478,8 @@ class ParSigDuty:
         # set (handle returns before StoreExternal); the session has by then stored the set's verified
         # entries, each of which is a partial the ParSigDB would accept from that peer on its own.
         # The error then carries, as `fired`, the aggregates of the validators those entries brought to the
-        # threshold: they fire once, so the caller must not lose them.
+        # threshold: they fire once, so the caller must not lose them.  (reject_sets=True closes this
+        # divergence: there the set is one set of hbls_duty_add_sets and is stored whole or not at all.)
         r = self._duty.add(pks, msgs, sigs, groups, idx)
         out: Dict[bytes, bytes] = {}
         err: Optional[CallerError] = None

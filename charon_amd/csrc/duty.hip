@@ -9,6 +9,12 @@
 //   k_duty_gather 1 lane / fired group, in ascending group order (the host sorted the list): its
 //                 members, share indices, class key and message into the tables threshold.hip's
 //                 k_ta_sel_fill reads, its members' serials and its DV key
+// hbls_duty_add_sets puts two kernels between the verification and k_duty_store:
+//   k_duty_set_first 1 lane / item: a lane whose verification failed folds its arrival index into its
+//                 set's entry of set_first with atomicMin; the failing lanes of a wave that share a
+//                 set combine first (one atomic per distinct failing set of the wave, none on a clean add)
+//   k_duty_gate   1 lane / item: the status byte k_duty_store reads (dutysel.h duty_admit), so that no
+//                 partial of a rejected set is admitted
 // The aggregation itself is threshold.hip's, over the duty's store.
 #include <hip/hip_runtime.h>
 
@@ -74,6 +80,35 @@ __global__ __launch_bounds__(64) void k_duty_store(DutyStoreArgs a) {
   }
 }
 
+__global__ __launch_bounds__(64) void k_duty_set_first(const uint8_t* __restrict__ vstatus, const uint32_t* __restrict__ set_id,
+                                                       const uint32_t* __restrict__ arrival, uint32_t n,
+                                                       uint32_t* __restrict__ set_first, uint32_t n_sets) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  const uint32_t lane = threadIdx.x & 63u;
+  // a set id outside the call's sets is never an address (the host plan gives none)
+  const uint32_t sid = q < n ? set_id[q] : DUTY_NONE;
+  const bool fail = q < n && sid < n_sets && vstatus[q] != 0;
+  const uint32_t arr = fail ? arrival[q] : DUTY_NONE;
+  uint64_t todo = __ballot(fail);  // wave-uniform: every lane walks the same leaders
+  while (todo) {
+    const int leader = __ffsll((unsigned long long)todo) - 1;
+    const uint32_t s0 = __shfl(sid, leader);
+    const bool mine = fail && sid == s0;
+    uint32_t v = mine ? arr : DUTY_NONE;
+    for (uint32_t d = 32; d; d >>= 1) v = min(v, (uint32_t)__shfl_xor(v, d));
+    if (lane == (uint32_t)leader) atomicMin(set_first + s0, v);
+    todo &= ~__ballot(mine);
+  }
+}
+
+__global__ __launch_bounds__(64) void k_duty_gate(const uint8_t* __restrict__ vstatus, const uint32_t* __restrict__ set_id,
+                                                  uint32_t n, const uint32_t* __restrict__ set_first, uint32_t n_sets,
+                                                  uint8_t* __restrict__ admit) {
+  const uint32_t q = blockIdx.x * blockDim.x + threadIdx.x;
+  if (q >= n) return;
+  admit[q] = duty_admit(vstatus[q], set_id[q], set_first, n_sets);
+}
+
 __global__ __launch_bounds__(256) void k_duty_copy(const HmEntry* __restrict__ src, uint32_t n_src,
                                                    const uint2* __restrict__ copies, const uint32_t* __restrict__ count,
                                                    uint32_t max_copies, HmEntry* __restrict__ store, uint32_t n_slots) {
@@ -111,6 +146,17 @@ __global__ __launch_bounds__(64) void k_duty_gather(DutyGatherArgs a) {
 void launch_duty_store(const DutyStoreArgs& a, hipStream_t s) {
   if (!a.n_touched) return;
   hipLaunchKernelGGL(k_duty_store, dim3(duty_blocks(a.n_touched, 64)), dim3(64), 0, s, a);
+}
+void launch_duty_set_first(const uint8_t* vstatus, const uint32_t* set_id, const uint32_t* arrival, uint32_t n,
+                           uint32_t* set_first, uint32_t n_sets, hipStream_t s) {
+  if (!n || !n_sets) return;
+  hipLaunchKernelGGL(k_duty_set_first, dim3(duty_blocks(n, 64)), dim3(64), 0, s, vstatus, set_id, arrival, n, set_first,
+                     n_sets);
+}
+void launch_duty_gate(const uint8_t* vstatus, const uint32_t* set_id, uint32_t n, const uint32_t* set_first,
+                      uint32_t n_sets, uint8_t* admit, hipStream_t s) {
+  if (!n) return;
+  hipLaunchKernelGGL(k_duty_gate, dim3(duty_blocks(n, 64)), dim3(64), 0, s, vstatus, set_id, n, set_first, n_sets, admit);
 }
 void launch_duty_copy(const HmEntry* src, uint32_t n_src, const uint2* copies, const uint32_t* count, uint32_t max_copies,
                       HmEntry* store, uint32_t n_slots, hipStream_t s) {

@@ -23,6 +23,21 @@ constexpr uint32_t DUTY_MAX_T = 16;            // members per group (tasel.h TAS
 constexpr uint32_t DUTY_MAX_STORED = 64;       // stored partials per group, at most
 constexpr uint32_t DUTY_NONE = 0xffffffffu;    // no destination slot / no group
 
+// hbls_duty_add_sets: a peer's set is stored whole or not at all (parsigex.go:93-98 returns at the
+// first partial of a set that fails, before any subscriber sees the set).  set_first[k] is the
+// smallest arrival index of set k whose verification failed, DUTY_NONE when every partial of the
+// set verified.  The admission predicate: the status byte the storing rule sees for a partial of
+// set `set_id` -- its own verdict when that is a failure, DUTY_SET_REJECTED when it verified but its
+// set did not, 0 (admitted) otherwise.  A set id outside the call's sets admits nothing and is never
+// an address.  duty.hip's k_duty_gate and the CPU harness tests/native/dutysetcheck.cpp both
+// compile this one function.
+constexpr uint8_t DUTY_SET_REJECTED = 0xff;
+DUTYSEL_HD uint8_t duty_admit(uint8_t vstatus, uint32_t set_id, const uint32_t* set_first, uint32_t n_sets) {
+  if (vstatus != 0) return vstatus;
+  if (set_id >= n_sets) return DUTY_SET_REJECTED;
+  return set_first[set_id] != DUTY_NONE ? DUTY_SET_REJECTED : (uint8_t)0;
+}
+
 // One group's resident records: slot k < *count holds the k-th stored partial's share index,
 // message id and serial; *fired != 0 closes the group.
 struct DutyRecords {

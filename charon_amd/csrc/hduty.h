@@ -152,4 +152,35 @@ inline void duty_plan_shard(const uint8_t* msgs, const uint64_t* msg_off, const 
   p.toff.push_back((uint32_t)mine.size());
 }
 
+// hbls_duty_add_sets: set k of the call is partials [set_off[k], set_off[k + 1]) in arrival order.
+// What is wrong with set_off (n_sets + 1 entries: 0 first, n last, non-decreasing), nullptr when
+// nothing is.  Checked before anything is enqueued, so that a set id is never past n_sets.
+inline const char* duty_check_sets(const uint32_t* set_off, size_t n_sets, size_t n) {
+  if (!n_sets) return n ? "n_sets is 0 with partials in the call" : nullptr;
+  if (!set_off) return "set_off is required";
+  if (set_off[0] != 0) return "set_off[0] must be 0";
+  for (size_t k = 0; k < n_sets; k++)
+    if (set_off[k + 1] < set_off[k]) return "set_off must not decrease";
+  if (set_off[n_sets] != n) return "set_off[n_sets] must be n";
+  return nullptr;
+}
+
+// each arrival index's set id (set_off as duty_check_sets accepts it)
+inline void duty_set_ids(const uint32_t* set_off, size_t n_sets, size_t n, std::vector<uint32_t>& set_of) {
+  set_of.resize(n);
+  for (size_t k = 0; k < n_sets; k++)
+    for (size_t i = set_off[k]; i < set_off[k + 1]; i++) set_of[i] = (uint32_t)k;
+}
+
+// A shard's items in its verification order: their set ids.  (Their arrival indices are p.order.)
+inline void duty_plan_sets(const std::vector<uint32_t>& set_of, const DutyShardPlan& p, std::vector<uint32_t>& set_id) {
+  set_id.resize(p.m());
+  for (size_t q = 0; q < p.m(); q++) set_id[q] = set_of[p.order[q]];
+}
+
+// Several shards: a set's first failure is the smallest any shard saw (0xffffffff: none)
+inline void duty_merge_set_first(uint32_t* merged, const uint32_t* shard, size_t n_sets) {
+  for (size_t k = 0; k < n_sets; k++) merged[k] = std::min(merged[k], shard[k]);
+}
+
 }  // namespace hb

@@ -368,6 +368,9 @@ enum IoId {
   // k_duty_store, its two lists and counters, the sorted fired rows and their group ids
   I_DSERIAL, I_DTGRP, I_DTOFF, I_DTPOS, I_DTIDX, I_DSTORED, I_DSLOT, I_DMSLOT, I_DMSER, I_DMIDX, I_DFMSG, I_DFKEY,
   I_DCOPY, I_DFIRED, I_DCTR, I_DFROW, I_DFGRP,
+  // hbls_duty_add_sets: the items' set ids and arrival indices, the sets' first failures, the status bytes
+  // k_duty_store reads, and (several shards) the decompressed signatures kept from phase one for phase two
+  I_DSETID, I_DARR, I_DSETFIRST, I_DADMIT, I_DVSIG,
   I_COUNT
 };
 
@@ -3058,6 +3061,10 @@ struct DutyShard {
 // from before its first enqueue until its stream (a host-call context's, with the workspace side
 // streams joined into it) has drained; the next call, on whatever stream, is ordered behind it by
 // that host-side wait alone.  Nothing else in the library knows these buffers.
+// INVARIANT (hbls_duty_add_sets): what the host plan hands a kernel is never trusted as an address.
+// set_off is validated on the host before anything is enqueued, and k_duty_set_first and the gate
+// (dutysel.h duty_admit) still check an item's set id against n_sets before it indexes set_first,
+// as k_duty_store checks a touched group against the shard's groups.
 struct Duty {
   std::mutex mu;
   bool closed = false, broken = false;
@@ -3065,6 +3072,7 @@ struct Duty {
   uint32_t t = 0, max_stored = 0, next_serial = 0;
   std::vector<DutyShard> sh;
   uint64_t stats[6] = {};
+  uint64_t set_stats[3] = {};  // hbls_duty_set_stats: sets seen, sets rejected, verified partials of rejected sets
 };
 std::mutex g_duty_mu;
 std::unordered_map<uint64_t, std::shared_ptr<Duty>> g_duties;
@@ -3140,21 +3148,112 @@ struct DutyShardOut {
   uint64_t n_stored = 0, n_full = 0, n_new_msgs = 0, resident = 0;
 };
 
+// hbls_duty_add_sets: the call's sets (hduty.h), every caller index's set id
+struct DutySetCall {
+  const uint32_t* set_off = nullptr;
+  size_t n_sets = 0;
+  std::vector<uint32_t> set_of;
+};
+
 // One shard's part of an add: its items (caller indices, increasing).  As with
 // hbls_slot_select_batch, the shard's add is one verification: it is not chunked.
-int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
-                   const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx,
-                   const std::vector<uint32_t>& items, uint32_t first_serial, size_t gmax, uint8_t* vstatus,
-                   uint8_t* stored, DutyShardOut& out) {
-  const size_t m = items.size(), t = du.t, ng = sh.ge - sh.gb;
-  if (!m) return 0;
-  const double t_start = now_ms();
-  Dev& d = *sh.d;
-  HcLease hcs(d);
-  Hc& h = *hcs.h[0];
+//
+// verify() enqueues the upload, the hashing and the verification, store() the storing rule, the
+// copies, and, behind the one host wait, the aggregation of what fired.  hbls_duty_add runs the two
+// back to back as one stream segment under one hold of the device lock.  hbls_duty_add_sets does
+// the same on one shard, with k_duty_set_first and k_duty_gate between the verification and the
+// store.  On several shards a set's verdict needs every shard's verification, so verify(split)
+// ends phase one: it hands its workspace set back, waits for the shard's set_first and returns
+// with no device lock held, the caller joins the shards and merges, and store(merged) is phase two.
+// INVARIANT (host-call contexts): a context is one of a bounded pool per device that other calls
+// block on (hc_acquire), so no call may wait for a second context while it holds one unless every
+// such call takes them in one global order.  On the one-segment path a shard takes its context in
+// verify() and gives it back at the end of store(), with no other shard waited for in between --
+// the lifetime the shard routine always had.  On the two-phase path the contexts are held across
+// the join (phase two needs the staging buffers phase one filled), so duty_add takes all of them
+// itself before any shard starts, in ascending order of their devices' addresses (lease()), and each
+// goes back at the end of its shard's store(): calls that hold a device's context wait only for
+// devices later in that order, and one-context holders wait for nothing.
+// INVARIANT (workspace sets): none is kept between the phases.  A set cannot be kept without the
+// device lock (ws_acquire hands the sets out round-robin and orders their users by free_ev alone),
+// so what phase two reads of the verification -- the decompressed signatures k_duty_copy moves -- is
+// copied into the context's staging before the set is handed back.
+// Members: "the call" is set by duty_add before verify(); the rest is written by verify_() and read
+// by store_().  `lk` is held from the first upload of a phase to its last enqueue only, and never
+// when verify() / store() return; `w` is non-null from the verification's ws_acquire until the
+// ws_release at the end of phase one (two phases) or of the store's enqueues (one segment), and
+// stays unreleased, as it always did, when an enqueue fails in between; `hcs` is held from lease()
+// or verify() until store() returns (or verify() fails); the device pointers are valid while it is.
+struct DutyShardAdd {
+  // the call
+  Duty* du_ = nullptr;
+  DutyShard* sh_ = nullptr;
+  const uint8_t *pks = nullptr, *sigs = nullptr, *msgs = nullptr;
+  const uint64_t* msg_off = nullptr;
+  const uint32_t *msg_len = nullptr, *group = nullptr;
+  const int64_t* share_idx = nullptr;
+  const std::vector<uint32_t>* items_ = nullptr;
+  uint32_t first_serial = 0;
+  size_t gmax = 0;
+  uint8_t *vstatus = nullptr, *stored = nullptr;
+  DutyShardOut* out_ = nullptr;
+  const DutySetCall* sets = nullptr;  // null: hbls_duty_add
+  const char* who = "hbls_duty_add";
+  // from verify() to store()
+  std::unique_ptr<HcLease> hcs;
   DutyShardPlan p;
+  std::unique_lock<std::mutex> lk;
+  bool split = false;
+  size_t m = 0, nm = 0, nnew = 0, nt = 0, np = 0;
+  double t_start = 0, t_prep = 0;
+  uint32_t *dmidx = nullptr, *dserial = nullptr, *dtgrp = nullptr, *dtoff = nullptr, *dtpos = nullptr, *dsid = nullptr;
+  int64_t* dtidx = nullptr;
+  void *pst = nullptr, *pstored = nullptr, *pslot = nullptr, *pmslot = nullptr, *pmser = nullptr, *pmidx = nullptr,
+       *pfmsg = nullptr, *pfkey = nullptr, *pcopy = nullptr, *pfired = nullptr, *pctr = nullptr, *psetfirst = nullptr,
+       *padmit = nullptr;
+  const HmEntry* vsig = nullptr;
+  Ws* w = nullptr;  // the verification's workspace set, until it is handed back
+  std::vector<uint32_t> set_first;  // the sets' first failures as this shard saw them (one shard: the call's)
+
+  int verify_(bool split);
+  int store_(const uint32_t* merged);
+  // the device lock never outlives the phase (nor, in a shard thread, the thread) that took it
+  int verify(bool two_phases) {
+    const int rc = verify_(two_phases);
+    if ((rc || two_phases) && lk.owns_lock()) lk.unlock();
+    if (rc) hcs.reset();
+    return rc;
+  }
+  int store(const uint32_t* merged) {
+    const int rc = store_(merged);
+    if (lk.owns_lock()) lk.unlock();
+    hcs.reset();  // the last download is synchronised (or the shard failed): the context goes back now
+    return rc;
+  }
+  // two phases: the shard's context, taken by duty_add in the global order before any shard starts
+  void lease() {
+    if (!items_->empty()) hcs.reset(new HcLease(*sh_->d));
+  }
+};
+
+int DutyShardAdd::verify_(bool two_phases) {
+  Duty& du = *du_;
+  DutyShard& sh = *sh_;
+  const std::vector<uint32_t>& items = *items_;
+  DutyShardOut& out = *out_;
+  split = two_phases;
+  m = items.size();
+  if (sets) set_first.assign(sets->n_sets, DUTY_NONE);
+  if (!m) return 0;
+  t_start = now_ms();
+  Dev& d = *sh.d;
+  if (!hcs) hcs.reset(new HcLease(d));
+  Hc& h = *hcs->h[0];
   duty_plan_shard(msgs, msg_off, msg_len, group, share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p);
-  const size_t nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
+  std::vector<uint32_t> hsid;
+  if (sets) duty_plan_sets(sets->set_of, p, hsid);
+  nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
+  const size_t t = du.t, n_sets = sets ? sets->n_sets : 0;
   out.n_new_msgs = nnew;
   out.resident = p.resident;
   std::vector<uint8_t> hpk(48 * m), hsig(96 * m);
@@ -3165,8 +3264,8 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   std::vector<uint64_t> noff(nnew);  // the new messages' offsets, from the first new byte
   const uint64_t nb0 = nnew ? sh.tab.t.off[sh.hashed] : 0;
   for (size_t j = 0; j < nnew; j++) noff[j] = sh.tab.t.off[sh.hashed + j] - nb0;
-  const double t_prep = now_ms();
-  std::unique_lock<std::mutex> lk(d.mu);
+  t_prep = now_ms();
+  lk = std::unique_lock<std::mutex>(d.mu);
   if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
   hipStream_t s = h.s;
   if (nm > sh.hm_cap) {  // grow geometrically, keeping the resident entries (hash and lines)
@@ -3181,8 +3280,7 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   }
   uint8_t *dpk, *dsig, *dmsg;
   uint64_t* doff;
-  uint32_t *dlen, *dmidx, *dvgoff, *dserial, *dtgrp, *dtoff, *dtpos;
-  int64_t* dtidx;
+  uint32_t *dlen, *dvgoff, *darr = nullptr;
   if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
   PinnedUploads up;
   up.add(I_MSG, sh.tab.t.bytes.data() + nb0, sh.tab.t.bytes.size() - (nnew ? nb0 : sh.tab.t.bytes.size()), &dmsg);
@@ -3195,7 +3293,12 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   up.add(I_DTOFF, p.toff.data(), p.toff.size(), &dtoff);
   up.add(I_DTPOS, p.tpos.data(), np, &dtpos);
   up.add(I_DTIDX, p.tidx.data(), np, &dtidx);
-  void *pst, *pstored, *pslot, *pmslot, *pmser, *pmidx, *pfmsg, *pfkey, *pcopy, *pfired, *pctr;
+  if (sets) {
+    up.add(I_DSETID, hsid.data(), m, &dsid);
+    up.add(I_DARR, p.order.data(), m, &darr);
+  }
+  if (sets && (ensure_buf(h.io[I_DSETFIRST], n_sets * sizeof(uint32_t), &psetfirst) || ensure_buf(h.io[I_DADMIT], m, &padmit)))
+    return -1;
   if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_DSTORED], m, &pstored) ||
       ensure_buf(h.io[I_DSLOT], m * sizeof(uint32_t), &pslot) || ensure_buf(h.io[I_DMSLOT], nt * t * sizeof(uint32_t), &pmslot) ||
       ensure_buf(h.io[I_DMSER], nt * t * sizeof(uint32_t), &pmser) || ensure_buf(h.io[I_DMIDX], nt * t * sizeof(int64_t), &pmidx) ||
@@ -3205,6 +3308,7 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
     return -1;
   // phase 1: hash the messages new to the shard (with their lines: the entries stay), verify the set
   Ws& w = ws_acquire(d, s);
+  this->w = &w;
   HCHK(hipEventRecord(w.ev_fork, s));
   hipStream_t shs = w.side[2];
   HCHK(hipStreamWaitEvent(shs, w.ev_fork, 0));
@@ -3224,6 +3328,54 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   vc.hm_ready = w.ev_side[2];
   if (verify_pipeline(d, w, vc)) return -1;
   HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  vsig = vc.vsig;
+  if (sets) {
+    HCHK(hipMemsetAsync(psetfirst, 0xff, std::max<size_t>(n_sets, 1) * sizeof(uint32_t), s));
+    TIMED(d, "k_duty_set_first", s,
+          launch_duty_set_first((const uint8_t*)pst, dsid, darr, (uint32_t)m, (uint32_t*)psetfirst, (uint32_t)n_sets, s));
+    HCHK(hipGetLastError());
+  }
+  if (!split) return 0;
+  // end of phase one: the decompressed signatures leave the workspace set, the set goes back, and the
+  // shard's verdicts per set come to the host
+  void* pv;
+  if (ensure_buf(h.io[I_DVSIG], m * sizeof(HmEntry), &pv)) return -1;
+  HCHK(hipMemcpyAsync(pv, vsig, m * sizeof(HmEntry), hipMemcpyDeviceToDevice, s));
+  vsig = (const HmEntry*)pv;
+  if (ws_release(w, s)) return -1;
+  this->w = nullptr;
+  lk.unlock();
+  if (n_sets) HCHK(hipMemcpyAsync(set_first.data(), psetfirst, n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  sh.hashed = nm;
+  return 0;
+}
+
+int DutyShardAdd::store_(const uint32_t* merged) {
+  if (!m) return 0;
+  Duty& du = *du_;
+  DutyShard& sh = *sh_;
+  DutyShardOut& out = *out_;
+  Dev& d = *sh.d;
+  Hc& h = *hcs->h[0];
+  hipStream_t s = h.s;
+  const size_t t = du.t, ng = sh.ge - sh.gb, n_sets = sets ? sets->n_sets : 0;
+  if (split) {  // phase two: every shard's store sees the call's verdicts per set
+    lk.lock();
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    PinnedUploads upm;
+    uint32_t* dm;
+    upm.add(I_DSETFIRST, merged, n_sets, &dm);
+    if (upload_pinned(d, h, upm)) return -1;
+    psetfirst = dm;
+  }
+  const uint8_t* seen = (const uint8_t*)pst;  // what the storing rule reads as the items' statuses
+  if (sets) {
+    TIMED(d, "k_duty_gate", s,
+          launch_duty_gate((const uint8_t*)pst, dsid, (uint32_t)m, (const uint32_t*)psetfirst, (uint32_t)n_sets,
+                           (uint8_t*)padmit, s));
+    seen = (const uint8_t*)padmit;
+  }
   // store: the rule per touched group, then the stored partials' points out of the workspace
   HCHK(hipMemsetAsync(pstored, 0, m, s));
   HCHK(hipMemsetAsync(pctr, 0, DUTY_CTRS * sizeof(uint32_t), s));
@@ -3236,7 +3388,7 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   st.n_groups = (uint32_t)ng;
   st.max_stored = du.max_stored;
   st.t = du.t;
-  st.vstatus = (const uint8_t*)pst;
+  st.vstatus = seen;
   st.msg_idx = dmidx;
   st.serial = dserial;
   st.n = (uint32_t)m;
@@ -3258,15 +3410,20 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   st.ctr = (uint32_t*)pctr;
   TIMED(d, "k_duty_store", s, launch_duty_store(st, s));
   TIMED(d, "k_duty_copy", s,
-        launch_duty_copy(vc.vsig, (uint32_t)m, st.copies, st.ctr + DUTY_CTR_COPIES, (uint32_t)m, sh.store,
+        launch_duty_copy(vsig, (uint32_t)m, st.copies, st.ctr + DUTY_CTR_COPIES, (uint32_t)m, sh.store,
                          (uint32_t)(ng * du.max_stored), s));
   HCHK(hipGetLastError());
-  if (ws_release(w, s)) return -1;
+  if (w) {
+    if (ws_release(*w, s)) return -1;
+    w = nullptr;
+  }
   lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
   const double t_enq1 = now_ms();
   std::vector<uint8_t> hst(m), hstored(m);
   std::vector<uint32_t> hfired(nt);
   uint32_t hctr[DUTY_CTRS] = {};
+  if (sets && !split && n_sets)  // one shard: the sets' verdicts come back with the items'
+    HCHK(hipMemcpyAsync(set_first.data(), psetfirst, n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HCHK(hipMemcpyAsync(hst.data(), pst, m, hipMemcpyDeviceToHost, s));
   HCHK(hipMemcpyAsync(hstored.data(), pstored, m, hipMemcpyDeviceToHost, s));
   HCHK(hipMemcpyAsync(hctr, pctr, sizeof(hctr), hipMemcpyDeviceToHost, s));
@@ -3281,13 +3438,13 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   }
   out.n_full = hctr[DUTY_CTR_FULL];
   const size_t nf = hctr[DUTY_CTR_FIRED];
-  if (nf > nt) return set_err("hbls_duty_add: the fired list is longer than the touched groups");
+  if (nf > nt) return set_err(std::string(who) + ": the fired list is longer than the touched groups");
   double t_enq2 = t_dev1;
   if (nf) {
     // phases 3 and 4 of slot_select_core over the fired groups, ascending: their members are in the store
     std::sort(hfired.begin(), hfired.begin() + nf);
     for (size_t k = 0; k < nf; k++)
-      if (hfired[k] >= nt) return set_err("hbls_duty_add: a fired row names no touched group");
+      if (hfired[k] >= nt) return set_err(std::string(who) + ": a fired row names no touched group");
     lk.lock();
     if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
     uint32_t* dfrow;
@@ -3395,34 +3552,94 @@ int duty_add_shard(Duty& du, DutyShard& sh, const uint8_t* pks, const uint8_t* s
   return 0;
 }
 
+// sets: null for hbls_duty_add; else the call's sets, with set_first (n_sets entries) to fill
 int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
              const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
              uint8_t* stored, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status,
-             uint8_t* agg_vstatus) {
-  const size_t nd = du.sh.size(), t = du.t;
+             uint8_t* agg_vstatus, const DutySetCall* sets = nullptr, uint32_t* set_first = nullptr) {
+  const size_t nd = du.sh.size(), t = du.t, n_sets = sets ? sets->n_sets : 0;
+  const std::string who = sets ? "hbls_duty_add_sets" : "hbls_duty_add";
   const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
   std::vector<std::vector<uint32_t>> items;
   duty_route(group, n, du.n_groups, nd, items);
   std::vector<DutyShardOut> outs(nd);
+  std::vector<DutyShardAdd> adds(nd);
+  for (size_t k = 0; k < nd; k++) {
+    DutyShardAdd& a = adds[k];
+    a.du_ = &du;
+    a.sh_ = &du.sh[k];
+    a.pks = pks;
+    a.sigs = sigs;
+    a.msgs = msgs;
+    a.msg_off = msg_off;
+    a.msg_len = msg_len;
+    a.group = group;
+    a.share_idx = share_idx;
+    a.items_ = &items[k];
+    a.first_serial = du.next_serial;
+    a.gmax = gmax;
+    a.vstatus = vstatus;
+    a.stored = stored;
+    a.out_ = &outs[k];
+    a.sets = sets;
+    a.who = sets ? "hbls_duty_add_sets" : "hbls_duty_add";
+  }
   std::vector<int> rc(nd, 0);
   std::vector<std::string> errs(nd);
-  auto run = [&](size_t k) {
-    rc[k] = duty_add_shard(du, du.sh[k], pks, sigs, msgs, msg_off, msg_len, group, share_idx, items[k], du.next_serial, gmax,
-                           vstatus, stored, outs[k]);
-    if (rc[k]) errs[k] = g_err;
-  };
-  if (nd == 1) {
-    run(0);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
-    for (auto& x : th) x.join();
-  }
-  for (size_t k = 0; k < nd; k++)
-    if (rc[k]) {
-      du.broken = true;  // a shard may have stored what another did not verify: the duty's state is no longer one stream's
-      return set_err("hbls_duty_add: device " + std::to_string(du.sh[k].d->ord) + ": " + errs[k]);
+  // every shard runs fn concurrently (one host thread per shard beyond one), all joined before this returns
+  auto each = [&](const std::function<int(size_t)>& fn) {
+    auto run = [&](size_t k) {
+      rc[k] = fn(k);
+      if (rc[k]) errs[k] = g_err;
+    };
+    if (nd == 1) {
+      run(0);
+    } else {
+      std::vector<std::thread> th;
+      for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
+      for (auto& x : th) x.join();
     }
+    for (size_t k = 0; k < nd; k++)
+      if (rc[k]) {
+        du.broken = true;  // a shard may have stored what another did not verify: the duty's state is no longer one stream's
+        return set_err(who + ": device " + std::to_string(du.sh[k].d->ord) + ": " + errs[k]);
+      }
+    return 0;
+  };
+  std::vector<uint32_t> merged(n_sets, DUTY_NONE);
+  if (!sets || nd == 1) {  // one stream segment per shard
+    if (each([&](size_t k) { return adds[k].verify(false) ? -1 : adds[k].store(nullptr); })) return -1;
+    if (sets) merged = adds[0].set_first;
+  } else {
+    // a set's verdict needs every shard's verification: phase one everywhere, the shards joined (none
+    // parked, no device lock and no workspace set held), the element-wise min, then phase two everywhere.  A failure in
+    // phase one leaves nothing stored anywhere.
+    // the shards' contexts first, in the one global order (DutyShardAdd's invariant)
+    std::vector<size_t> ord(nd);
+    std::iota(ord.begin(), ord.end(), size_t(0));
+    std::sort(ord.begin(), ord.end(), [&](size_t x, size_t y) { return std::less<Dev*>()(du.sh[x].d, du.sh[y].d); });
+    for (size_t k : ord) adds[k].lease();
+    if (each([&](size_t k) { return adds[k].verify(true); })) return -1;
+    for (size_t k = 0; k < nd; k++) duty_merge_set_first(merged.data(), adds[k].set_first.data(), n_sets);
+    if (each([&](size_t k) { return adds[k].store(merged.data()); })) return -1;
+  }
+  if (sets) {
+    uint64_t rejected = 0, lost = 0;
+    for (size_t k = 0; k < n_sets; k++) {
+      const uint32_t f = merged[k], b = sets->set_off[k], e = sets->set_off[k + 1];
+      if (f == DUTY_NONE) continue;
+      if (f < b || f >= e) {
+        du.broken = true;
+        return set_err(who + ": a set's first failure lies outside the set");
+      }
+      rejected++;
+      for (uint32_t i = b; i < e; i++) lost += vstatus[i] == HBLS_OK ? 1 : 0;
+    }
+    if (n_sets) memcpy(set_first, merged.data(), n_sets * sizeof(uint32_t));
+    du.set_stats[0] += n_sets;
+    du.set_stats[1] += rejected;
+    du.set_stats[2] += lost;
+  }
   size_t nf = 0;  // the shards own ascending ranges of the groups: their lists concatenate in order
   for (size_t k = 0; k < nd; k++) {
     const DutyShardOut& o = outs[k];
@@ -4195,6 +4412,55 @@ int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const 
   if (!n) return 0;
   return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
                   ta_out, ta_status, agg_vstatus);
+}
+
+int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                       const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n,
+                       const uint32_t* set_off, size_t n_sets, uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial,
+                       uint32_t* set_first, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
+                       uint8_t* ta_status, uint8_t* agg_vstatus) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_add_sets: no such duty (never opened, or closed)");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_add_sets: the duty is closed");
+  if (du->broken) return set_err("hbls_duty_add_sets: an earlier add failed on a device; close the duty");
+  if (!first_serial || !n_fired) return set_err("hbls_duty_add_sets: first_serial and n_fired are required");
+  if (n >= 0xffffffffull - du->next_serial) return set_err("hbls_duty_add_sets: the duty would reach 2^32 - 1 partials");
+  if (n_sets >= 0xffffffffull) return set_err("hbls_duty_add_sets: too many sets");
+  if (n_sets && !set_first) return set_err("hbls_duty_add_sets: set_first is required");
+  if (const char* bad = duty_check_sets(set_off, n_sets, n)) return set_err(std::string("hbls_duty_add_sets: ") + bad);
+  if (n && (!pks || !sigs || !msg_off || !msg_len || !group || !share_idx || !vstatus || !stored))
+    return set_err("hbls_duty_add_sets: pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
+  if (!msgs)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i]) return set_err("hbls_duty_add_sets: msgs is required");
+  if (std::min(n, du->n_groups) && (!fired || !chosen || !ta_out || !ta_status || !agg_vstatus))
+    return set_err("hbls_duty_add_sets: fired, chosen, ta_out, ta_status and agg_vstatus are required");
+  *first_serial = du->next_serial;
+  *n_fired = 0;
+  if (!n) {  // empty sets only: seen, none rejected
+    for (size_t k = 0; k < n_sets; k++) set_first[k] = DUTY_NONE;
+    du->set_stats[0] += n_sets;
+    return 0;
+  }
+  DutySetCall sc;
+  sc.set_off = set_off;
+  sc.n_sets = n_sets;
+  duty_set_ids(set_off, n_sets, n, sc.set_of);
+  return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
+                  ta_out, ta_status, agg_vstatus, &sc, set_first);
+}
+
+int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_set_stats: no such duty (never opened, or closed)");
+  if (!out || n > 3) return set_err("hbls_duty_set_stats: out is null or n above 3");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_set_stats: the duty is closed");
+  for (size_t k = 0; k < n; k++) out[k] = du->set_stats[k];
+  return 0;
 }
 
 int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag) {

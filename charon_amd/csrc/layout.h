@@ -212,6 +212,14 @@ void launch_duty_store(const DutyStoreArgs& a, hipStream_t s);
 void launch_duty_copy(const HmEntry* src, uint32_t n_src, const uint2* copies, const uint32_t* count, uint32_t max_copies,
                       HmEntry* store, uint32_t n_slots, hipStream_t s);
 void launch_duty_gather(const DutyGatherArgs& a, hipStream_t s);
+// hbls_duty_add_sets (k_duty_set_first / k_duty_gate), over the add's n items in verification order with their set ids
+// and arrival indices (hduty.h duty_plan_sets): set_first (n_sets entries, preset to 0xff bytes by the caller) gets
+// each set's smallest failing arrival index; admit[q] is what k_duty_store then reads as item q's status (dutysel.h
+// duty_admit).
+void launch_duty_set_first(const uint8_t* vstatus, const uint32_t* set_id, const uint32_t* arrival, uint32_t n,
+                           uint32_t* set_first, uint32_t n_sets, hipStream_t s);
+void launch_duty_gate(const uint8_t* vstatus, const uint32_t* set_id, uint32_t n, const uint32_t* set_first,
+                      uint32_t n_sets, uint8_t* admit, hipStream_t s);
 
 // Hashing and the pairing kernel (pipeline.hip).
 constexpr int GROUPS_PER_WAVE = 21;  // k_pair3: 3 lanes per pairing, 21 pairings per wave

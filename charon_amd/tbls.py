@@ -329,6 +329,14 @@ class DutyAdd:
     __slots__ = ("vstatus", "stored", "first_serial", "fired", "chosen", "aggregates", "ta_status", "agg_vstatus")
 
 
+class DutySetsAdd(DutyAdd):
+    """What one Duty.add_sets returns: DutyAdd's fields over the whole call, and per set `set_first`,
+    the index (among the call's partials) of its first partial that failed to verify, None when the
+    set was admitted."""
+
+    __slots__ = ("set_first",)
+
+
 class Duty:
     """One duty's state in device memory between calls (include/hipbls.h hbls_duty_*).  A context
     manager; calls on one Duty are serialised by the library."""
@@ -354,7 +362,17 @@ class Duty:
     def add(self, pks: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], groups: Sequence[int],
             share_idx: Sequence[int]) -> DutyAdd:
         """One arriving set, in arrival order: partial i belongs to validator groups[i] (any number
-        >= n_groups: verify only) under share index share_idx[i]."""
+        >= n_groups: verify only) under share index share_idx[i].  Partials are admitted one by one."""
+        return self._add(pks, msgs, sigs, groups, share_idx, None)
+
+    def add_sets(self, pks: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], groups: Sequence[int],
+                 share_idx: Sequence[int], set_off: Sequence[int]) -> DutySetsAdd:
+        """Several peers' sets in one call (hbls_duty_add_sets): set k is partials set_off[k] ..
+        set_off[k + 1] - 1 in arrival order, and is stored whole or, when one of its partials fails to
+        verify, not at all -- ParSigEx.handle followed by StoreExternal, per set."""
+        return self._add(pks, msgs, sigs, groups, share_idx, [int(x) for x in set_off])
+
+    def _add(self, pks, msgs, sigs, groups, share_idx, set_off):
         n, t = len(pks), self.threshold
         if not (n == len(msgs) == len(sigs) == len(groups) == len(share_idx)):
             raise TblsError("duty add: length mismatch")
@@ -366,12 +384,23 @@ class Duty:
         first, nf = ctypes.c_uint32(0), ctypes.c_size_t(0)
         fired, chosen = (ctypes.c_uint32 * rows)(), (ctypes.c_uint32 * (rows * t))()
         out, tst, ast = ctypes.create_string_buffer(96 * rows), ctypes.create_string_buffer(rows), ctypes.create_string_buffer(rows)
-        check(self._L.hbls_duty_add(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml,
-                                    _u32_array([min(int(g), 0xFFFFFFFF) if g >= 0 else 0xFFFFFFFF for g in groups]),
-                                    _i64_array([int(x) for x in share_idx]), n, vst, stored, ctypes.byref(first), fired,
-                                    ctypes.byref(nf), chosen, out, tst, ast))
+        grp = _u32_array([min(int(g), 0xFFFFFFFF) if g >= 0 else 0xFFFFFFFF for g in groups])
+        idx = _i64_array([int(x) for x in share_idx])
+        if set_off is None:
+            check(self._L.hbls_duty_add(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n, vst, stored,
+                                        ctypes.byref(first), fired, ctypes.byref(nf), chosen, out, tst, ast))
+            r = DutyAdd()
+        else:
+            if any(not 0 <= x <= 0xFFFFFFFF for x in set_off):
+                raise TblsError("duty add_sets: set_off out of range")
+            n_sets = max(len(set_off) - 1, 0)
+            sf = (ctypes.c_uint32 * max(n_sets, 1))()
+            check(self._L.hbls_duty_add_sets(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n,
+                                             _u32_array(set_off) if set_off else None, n_sets, vst, stored, ctypes.byref(first),
+                                             sf, fired, ctypes.byref(nf), chosen, out, tst, ast))
+            r = DutySetsAdd()
+            r.set_first = [None if x == 0xFFFFFFFF else int(x) for x in sf[:n_sets]]
         f = nf.value
-        r = DutyAdd()
         r.vstatus, r.stored, r.first_serial = list(vst.raw[:n]), list(stored.raw[:n]), first.value
         r.fired = list(fired[:f])
         r.chosen = [list(chosen[k * t:(k + 1) * t]) for k in range(f)]
@@ -390,6 +419,13 @@ class Duty:
         out = (ctypes.c_uint64 * 6)()
         check(self._L.hbls_duty_stats(self._handle(), out, 6))
         return dict(zip(("seen", "stored", "hashed", "resident_lookups", "fired", "full"), (int(x) for x in out)))
+
+    def set_stats(self) -> Dict[str, int]:
+        """hbls_duty_set_stats: sets seen and rejected by add_sets, and the verified partials its
+        rejected sets held."""
+        out = (ctypes.c_uint64 * 3)()
+        check(self._L.hbls_duty_set_stats(self._handle(), out, 3))
+        return dict(zip(("sets", "rejected", "verified_not_stored"), (int(x) for x in out)))
 
     def close(self) -> None:
         if self._h is not None:

@@ -430,6 +430,38 @@ int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const 
 int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag);
 int hbls_duty_stats(uint64_t duty, uint64_t* out, size_t n);
 int hbls_duty_close(uint64_t duty);
+/* Set-atomic adds: a peer's set is stored whole or not at all, as the reference node does it
+ * (ParSigEx.handle verifies every partial of a set and returns at the first failure, before
+ * ParSigDB.StoreExternal sees the set).  Everything not named here means what it means for
+ * hbls_duty_add; the two calls may be mixed on one duty.
+ * hbls_duty_add_sets: set k of the call is partials [set_off[k], set_off[k + 1]) in arrival order.
+ *   set_off has n_sets + 1 entries, set_off[0] == 0, set_off[n_sets] == n, non-decreasing; empty
+ *   sets are allowed anywhere.  Anything else, a NULL set_off or set_first with n_sets > 0, and
+ *   n_sets == 0 with n != 0 are call errors, on which nothing is verified, stored or numbered.
+ *   vstatus[i]: exactly what hbls_verify_batch writes, for every partial -- those of rejected sets
+ *   and verify-only ones (which belong to their set like any other) included.
+ *   set_first[k]: the smallest i of set k with vstatus[i] != HBLS_OK, as an index among the call's n
+ *   partials; 0xffffffff when there is none (an empty set has none).  Set k is rejected iff
+ *   set_first[k] != 0xffffffff.
+ *   No partial of a rejected set is stored: stored[i] = 0, no record slot is taken, nothing counts
+ *   towards max_stored or "group full" (hbls_duty_stats out[5]); it still has serial *first_serial + i.
+ *   To the partials of the admitted sets, in arrival order across the call, hbls_duty_add's rule
+ *   applies unchanged: a later set of the call sees what an earlier admitted set of it stored and fired.
+ *   So the call equals hbls_duty_add given the same partials with group[i] = 0xffffffff for every i of
+ *   a rejected set, in vstatus, stored, first_serial, the fired rows and the duty's state; with every
+ *   set a singleton it equals hbls_duty_add on the call as it is.
+ * hbls_duty_set_stats (cumulative, n <= 3): out[0] sets seen, empty ones included; out[1] sets
+ *   rejected; out[2] partials with vstatus OK that were not stored because their set was rejected.
+ * Devices: a set spans shards (its partials go to their groups' shards, verify-only ones by position);
+ *   rejection is decided over the whole call, whichever shard saw the failure, at the cost of one
+ *   more host round trip when the duty has more than one shard. */
+int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                       const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
+                       const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets,
+                       uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial, uint32_t* set_first,
+                       uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
+                       uint8_t* ta_status, uint8_t* agg_vstatus);
+int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
