@@ -41,7 +41,7 @@ EXPORTS = (
     "hbls_slot_select_device", "hbls_slot_select_stats", "hbls_subgroup_batch", "hbls_subgroup_batch_stats",
     "hbls_slot_select_batch",
     "hbls_duty_open", "hbls_duty_add", "hbls_duty_state", "hbls_duty_stats", "hbls_duty_close",
-    "hbls_duty_add_sets", "hbls_duty_set_stats",
+    "hbls_duty_add_sets", "hbls_duty_set_stats", "hbls_duty_add_sets_first", "hbls_duty_first_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -153,6 +153,9 @@ def _declare(lib):
         "hbls_duty_close": ([ctypes.c_uint64], ctypes.c_int),
         "hbls_duty_add_sets": ([ctypes.c_uint64, P, P, P, P, P, P, P, SZ, P, SZ, P, P, P, P, P, P, P, P, P, P], ctypes.c_int),
         "hbls_duty_set_stats": ([ctypes.c_uint64, P, SZ], ctypes.c_int),
+        "hbls_duty_add_sets_first": ([ctypes.c_uint64, P, P, P, P, P, P, P, SZ, P, SZ, P, P, P, P, P, P, P, P, P, P],
+                                     ctypes.c_int),
+        "hbls_duty_first_stats": ([ctypes.c_uint64, P, SZ], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
         "hbls_sync": ([P], ctypes.c_int),
         "hbls_status_bitmap": ([P, SZ, P, P], ctypes.c_int),

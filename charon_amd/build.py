@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "lib", "libhipbls.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["hipbls.hip", "pipeline.hip", "threshold.hip", "vbatch.hip", "vgroup.hip", "roots.hip", "hash.hip", "msm.hip",
-           "hashsplit.hip", "duty.hip"]
+           "hashsplit.hip", "duty.hip", "dutyfirst.hip"]
 
 
 def build_id(defines=()) -> str:
@@ -672,6 +672,93 @@ def build_dutysetdev(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+DUTYFIRSTCHECK_PREFIX = "hbls-dutyfirstcheck:"
+DUTYFIRSTCHECK_HEADERS = ("dutyfirst.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h")
+
+
+def dutyfirstcheck_build_id(root: str = "") -> str:
+    """The id embedded in the first-error set adds' harness (tests/native/dutyfirstcheck.cpp,
+    `df_build_id()`): sha256 over its source, the headers it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "dutyfirstcheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYFIRSTCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return DUTYFIRSTCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_dutyfirstcheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_dutyfirstcheck.so (tests/test_duty_first_host.py): the host side of
+    hbls_duty_add_sets_first on the CPU -- the set-major plan and the descent rule of the segmented
+    first-error verification; test-only.  Reused when its embedded id equals the tree's, as
+    build_dutycheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "dutyfirstcheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_dutyfirstcheck.so")
+    bid = dutyfirstcheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-dutyfirstcheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDF_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
+DUTYFIRSTDEV_PREFIX = "hbls-dutyfirstdev:"
+
+
+def dutyfirstdev_build_id(root: str = "") -> str:
+    """The id embedded in the first-error set adds' device harness (tests/native/dutyfirstdev.hip,
+    tests/test_gpu_duty_first_kernels.py; `dfd_build_id()`): sha256 over its source, the device
+    harnesses' shared devblocks.h, the product source it compiles (dutyfirst.hip), every header of
+    charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "dutyfirstdev.hip"), os.path.join(native, "devblocks.h"),
+              os.path.join(csrc, "dutyfirst.hip")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return DUTYFIRSTDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_dutyfirstdev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_dutyfirstdev.so: the kernels of the segmented first-error verification on
+    the device over explicit bytes, a harness of its own like build_dutysetdev; test-only.  Reused
+    when its embedded id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "dutyfirstdev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_dutyfirstdev.so")
+    bid = dutyfirstdev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-dutyfirstdev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DDFD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -735,7 +822,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
     for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
-               build_subgdev, build_dutysetcheck, build_dutysetdev):
+               build_subgdev, build_dutysetcheck, build_dutysetdev, build_dutyfirstcheck, build_dutyfirstdev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -339,11 +339,17 @@ class ParSigDuty:
     a set with a failing entry then leaves behind).  True gives the reference's rule exactly
     (hbls_duty_add_sets): a set with an entry that fails verification stores nothing, fires nothing
     and leaves the duty as it was.  store_external_many(sets) takes several peers' sets in one call,
-    each with that all-or-nothing boundary of its own, whatever reject_sets is."""
+    each with that all-or-nothing boundary of its own, whatever reject_sets is.
+    first_error: the calls that go through sets (reject_sets=True, store_external_many) stop a rejected
+    set's verification at its first failing entry, as parsigex.go:93-98 does (hbls_duty_add_sets_first):
+    the same results and errors -- the error of a rejected set is that of its first failing entry,
+    whose status is exact -- at a cost that does not grow with the number of bad entries."""
 
     def __init__(self, impl, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
-                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16, reject_sets: bool = False):
+                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16, reject_sets: bool = False,
+                 first_error: bool = False):
         self._reject_sets = reject_sets
+        self._first_error = first_error
         self._keys = list(dv_pubkeys)
         self._group = {pk: g for g, pk in enumerate(self._keys)}
         self._shares = pubshares_by_key
@@ -363,7 +369,8 @@ class ParSigDuty:
         return {pk: (cnt[g], fired[g]) for g, pk in enumerate(self._keys)}
 
     def store_external_many(self, sets: Sequence[Mapping[bytes, ParSig]]) -> List[object]:
-        """Several peers' sets, in arrival order, as ONE hbls_duty_add_sets call.  Per set, what
+        """Several peers' sets, in arrival order, as ONE hbls_duty_add_sets call (first_error:
+        hbls_duty_add_sets_first).  Per set, what
         ParSigEx.handle + StoreExternal would have given for it: {pubkey: aggregate} of the validators
         that fired through it (a fired validator belongs to the set that holds its last member), or the
         CallerError the reference would have returned -- not raised: a rejected set does not stop the
@@ -381,7 +388,8 @@ class ParSigDuty:
             idx += x
             set_off.append(len(pks))
             pres.append(pre)
-        r = self._duty.add_sets(pks, msgs, sigs, groups, idx, set_off)
+        add = self._duty.add_sets_first if self._first_error else self._duty.add_sets
+        r = add(pks, msgs, sigs, groups, idx, set_off)
         res: List[object] = []
         for j, pre in enumerate(pres):
             b, e = set_off[j], set_off[j + 1]

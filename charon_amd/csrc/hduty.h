@@ -8,7 +8,8 @@
 // partial goes to the shard that owns its group; a partial of no group (group[i] >= n_groups:
 // verify only) goes to shard i nd / n.  Within a shard the items are put in verification order --
 // by message, in groups of at most gmax (hgroup.h), as every host Verify path does -- and the
-// groups the add touches are listed in CSR form over positions in that order.
+// groups the add touches are listed in CSR form over positions in that order.  hbls_duty_add_sets_first
+// verifies in set-major order instead (group_by_set): the sets as they came, each group inside one set.
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -86,6 +87,7 @@ struct DutyShardPlan {
   std::vector<uint32_t> order;   // verification order: the caller index of each of the m items
   std::vector<uint32_t> midx;    // each item's duty-wide message id, in that order
   std::vector<uint32_t> vgoff;   // the verification groups' offsets in that order (n_vgroups + 1)
+  std::vector<uint32_t> vgset;   // set-major plans (hbls_duty_add_sets_first) only: each verification group's set
   std::vector<uint32_t> serial;  // each item's serial, in that order
   size_t msgs_before = 0;        // the table's size before this add: ids from there on are new to the shard
   size_t resident = 0;           // message lookups answered from the table
@@ -99,12 +101,38 @@ struct DutyShardPlan {
   size_t n_touched() const { return tgroup.size(); }
 };
 
+// hbls_duty_add_sets_first: the verification order is set-major and, within a set, arrival order -- the
+// order of `items` itself, which are increasing caller indices and whose sets are ranges of those.  The
+// groups are hgroup.h split_runs' runs (consecutive items over one message, at most gmax), taken set by
+// set, so that a group belongs to exactly one set; gset gets each group's set.  sid: the set of each of
+// the m items, non-decreasing.
+inline MsgGroups group_by_set(const uint32_t* mid, const uint32_t* sid, size_t m, size_t gmax, std::vector<uint32_t>& gset) {
+  MsgGroups g{std::vector<uint32_t>(m), std::vector<uint32_t>(mid, mid + m), {}};
+  for (size_t q = 0; q < m; q++) g.order[q] = (uint32_t)q;
+  gset.clear();
+  std::vector<size_t> runs;
+  for (size_t a = 0; a < m;) {
+    size_t b = a + 1;
+    while (b < m && sid[b] == sid[a]) b++;
+    split_runs(mid + a, b - a, gmax, runs);
+    for (size_t j = 0; j + 1 < runs.size(); j++) {
+      g.gstart.push_back(a + runs[j]);
+      gset.push_back(sid[a]);
+    }
+    a = b;
+  }
+  g.gstart.push_back(m);
+  return g;
+}
+
 // The plan of one shard (groups gb .. ge) for its items (caller indices, increasing) of an add
-// whose first partial has serial first_serial.  New messages are appended to tab.
+// whose first partial has serial first_serial.  New messages are appended to tab.  set_of (nullable;
+// hbls_duty_add_sets_first): every caller index's set id -- the plan is then set-major (group_by_set)
+// and fills p.vgset; the message ids, the touched groups and the serials are what they are without it.
 inline void duty_plan_shard(const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len,
                             const uint32_t* group, const int64_t* share_idx, const std::vector<uint32_t>& items,
                             size_t gb, size_t ge, uint32_t first_serial, size_t gmax, DutyMsgTable& tab,
-                            DutyShardPlan& p) {
+                            DutyShardPlan& p, const uint32_t* set_of = nullptr) {
   const size_t m = items.size();
   p.msgs_before = tab.size();
   p.resident = 0;
@@ -119,7 +147,11 @@ inline void duty_plan_shard(const uint8_t* msgs, const uint64_t* msg_off, const 
       mid[k] = tab.lookup(msg_len[i] ? msgs + msg_off[i] : (const uint8_t*)"", msg_len[i], &is_new);
     if (!is_new) p.resident++;
   }
-  const MsgGroups vg = group_by_message(mid.data(), m, tab.size(), gmax);
+  p.vgset.clear();
+  std::vector<uint32_t> sid(set_of ? m : 0);
+  for (size_t k = 0; k < sid.size(); k++) sid[k] = set_of[items[k]];
+  const MsgGroups vg = set_of ? group_by_set(mid.data(), sid.data(), m, gmax, p.vgset)
+                              : group_by_message(mid.data(), m, tab.size(), gmax);
   p.order.resize(m);
   p.serial.resize(m);
   std::vector<uint32_t> inv(m);  // position in `items` -> position in verification order

@@ -335,6 +335,7 @@ enum WsId {
   // sort, the tables and the aggregation's outputs in class order, the aggregates to verify
   W_SELCIDX, W_SELKEY, W_SELSTATE, W_SELGMSG, W_SELHIST, W_SELOFF, W_SELPERM, W_SELPMEM, W_SELPIDX, W_SELPGOFF,
   W_SELPOUT, W_SELPST, W_SELPPT, W_SELAPT, W_SELAST,
+  W_SEGFIRST,  // segmented first-error mode (VerifyCall::gseg): two words per segment
   W_COUNT_
 };
 
@@ -371,6 +372,7 @@ enum IoId {
   // hbls_duty_add_sets: the items' set ids and arrival indices, the sets' first failures, the status bytes
   // k_duty_store reads, and (several shards) the decompressed signatures kept from phase one for phase two
   I_DSETID, I_DARR, I_DSETFIRST, I_DADMIT, I_DVSIG,
+  I_DGSEG,  // hbls_duty_add_sets_first: the verification groups' set ids
   I_COUNT
 };
 
@@ -1074,6 +1076,16 @@ struct VerifyCall {
   size_t defer_msgs = 0;
   // first-error mode (vplan.h): the first item whose status is decided and not OK (0xffffffff: none)
   uint32_t* first_out = nullptr;
+  // segmented first-error mode (dutyfirst.h; hbls_duty_add_sets_first): the call's groups are cut into
+  // n_seg ordered segments, gseg[g] the segment of group g, and each segment gets its own first failure
+  // where the plan's first_only applies (exact statuses where it does not).  Per segment the pipeline
+  // keeps two words (batch and group, VerifyBufs::wseg) and writes seg_first_out[k]: the smallest
+  // item_arrival[i] over the items i of segment item_seg[i] == k whose status is decided and not OK
+  // (0xffffffff: none).  Takes no folded aggregates, and not first_out beside it.
+  const uint32_t* gseg = nullptr;
+  uint32_t n_seg = 0;
+  const uint32_t *item_seg = nullptr, *item_arrival = nullptr;
+  uint32_t* seg_first_out = nullptr;
   // the items' signatures already decompressed and in G2, with their statuses (sigs is then unused):
   // hbls_slot_select_device's aggregates, sums of partials it decompressed and subgroup-checked
   const HmEntry* pre_sig = nullptr;
@@ -1104,6 +1116,7 @@ struct VerifyBufs {
   G1JEntry* apr;
   G2JEntry* asr;
   uint32_t* wfirst;  // first_only
+  uint32_t* wseg;    // first_only with VerifyCall::gseg: two words per segment (taken by verify_pipeline)
   // batched final exponentiation (bfe)
   Fp4Entry* fbuf;
   G2JEntry *gS, *bS;
@@ -1618,9 +1631,14 @@ int check_slot_wide(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, Ver
   pb.guard = sfail;
   TIMED(d, "k_pair3_fin", s, launch_pair3_fin(pb, s));
   HCHK(hipMemsetAsync(b.gcount, 0, sizeof(uint32_t), s));
-  TIMED(d, "k_batch_verdict", s,
-        launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, sfail, (uint32_t)mmlk, b.wfirst,
-                             (uint32_t)g0));
+  if (b.wseg)
+    TIMED(d, "k_seg_batch_verdict", s,
+          launch_seg_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, sfail, (uint32_t)mmlk,
+                                   (uint32_t)g0, c.gseg, c.n_seg, b.wseg));
+  else
+    TIMED(d, "k_batch_verdict", s,
+          launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, sfail, (uint32_t)mmlk, b.wfirst,
+                               (uint32_t)g0));
   // groups of a failing batch: their own (P_g, H(m_g)) loops, then each group alone below
   pm.list = b.glist;
   pm.count = b.gcount;
@@ -1698,8 +1716,13 @@ int check_per_batch(Dev& d, const VerifyCall& c, const VerifyPlan& p, VerifyBufs
   TIMED(d, "k_pair3_fin", s, launch_pair6_fin(pf, s));
   // groups of a failing batch: checked one by one (their stored loop, their own S lines)
   HCHK(hipMemsetAsync(b.gcount, 0, sizeof(uint32_t), s));
-  TIMED(d, "k_batch_verdict", s,
-        launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, guard, fb, b.wfirst, (uint32_t)g0));
+  if (b.wseg)
+    TIMED(d, "k_seg_batch_verdict", s,
+          launch_seg_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, guard, fb, (uint32_t)g0, c.gseg,
+                                   c.n_seg, b.wseg));
+  else
+    TIMED(d, "k_batch_verdict", s,
+          launch_batch_verdict(b.gst, b.bver, ng, b.gver + g0, b.glist, b.gcount, s, guard, fb, b.wfirst, (uint32_t)g0));
   return group_recheck(d, c, b, g0, ng);
 }
 
@@ -1776,11 +1799,16 @@ int verify_resolve(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, Veri
   sa.status = c.status;
   sa.list = b.list;
   sa.count = b.count;
-  if (p.first_only) {
-    TIMED(d, "k_first_group", s, launch_first_group(b.gver, (uint32_t)p.n_groups, b.wfirst + 1, s));
-    sa.first_group = b.wfirst + 1;
+  if (b.wseg) {  // first_only per segment: each segment's first failing group, and only its items re-checked
+    TIMED(d, "k_seg_first_group", s, launch_seg_first_group(b.gver, (uint32_t)p.n_groups, c.gseg, c.n_seg, b.wseg, s));
+    TIMED(d, "k_seg_scatter", s, launch_seg_scatter(sa, c.gseg, c.n_seg, b.wseg, s));
+  } else {
+    if (p.first_only) {
+      TIMED(d, "k_first_group", s, launch_first_group(b.gver, (uint32_t)p.n_groups, b.wfirst + 1, s));
+      sa.first_group = b.wfirst + 1;
+    }
+    TIMED(d, "k_scatter", s, launch_scatter(sa, s));
   }
-  TIMED(d, "k_scatter", s, launch_scatter(sa, s));
   // fallback: every item of a failing group on its own; passes beyond the list end exit at once
   for (size_t base = 0; base < n + n_agg; base += p.fbcap) {
     TIMED(d, "k_fb_lines", s,
@@ -1805,6 +1833,11 @@ int verify_resolve(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, Veri
   if (c.first_out) {
     HCHK(hipMemsetAsync(c.first_out, 0xff, sizeof(uint32_t), s));
     TIMED(d, "k_first_item", s, launch_first_item(c.status, (uint32_t)n, c.first_out, s));
+  }
+  if (c.seg_first_out) {
+    HCHK(hipMemsetAsync(c.seg_first_out, 0xff, std::max<size_t>(c.n_seg, 1) * sizeof(uint32_t), s));
+    TIMED(d, "k_seg_first_item", s,
+          launch_seg_first_item(c.status, c.item_seg, c.item_arrival, (uint32_t)n, c.seg_first_out, c.n_seg, s));
   }
   if (fold && fold->n_groups && !n_agg) {  // the aggregation ran beside the verification: join it
     HCHK(hipStreamWaitEvent(s, w.ev_ta, 0));
@@ -1847,7 +1880,9 @@ int verify_pipeline(Dev& d, Ws& w, VerifyCall& c) {
   sh.n_groups = c.n_groups;
   sh.n_agg = (c.fold && c.fold->dv_pks) ? c.fold->n_groups : 0;
   sh.grouped = c.grp_off != nullptr;
-  sh.first_error = c.first_out != nullptr;
+  sh.first_error = c.first_out != nullptr || c.gseg != nullptr;
+  if (c.gseg && (c.first_out || !c.grp_off || !c.item_seg || !c.item_arrival || !c.seg_first_out))
+    return set_err("verify: a segmented call takes group offsets, the items' segments and arrival indices, no first_out");
   sh.defer_msgs = c.defer_msgs;
   sh.n_cu = d.n_cu;
   // the adaptive history, read by the calls that could take the slot-wide check: the outcomes of
@@ -1876,6 +1911,11 @@ int verify_pipeline(Dev& d, Ws& w, VerifyCall& c) {
   c.vsig = b.vsig;
   c.vsigst = b.vsigst;
   if (p.first_only) HCHK(hipMemsetAsync(b.wfirst, 0xff, 2 * sizeof(uint32_t), c.s));
+  if (p.first_only && c.gseg) {
+    const size_t words = 2 * std::max<size_t>(c.n_seg, 1);
+    if (wsbuf(w, W_SEGFIRST, words, &b.wseg)) return -1;
+    HCHK(hipMemsetAsync(b.wseg, 0xff, words * sizeof(uint32_t), c.s));
+  }
   if (verify_decompress(d, w, c, p, b) || verify_fold(d, w, c, b) || verify_combine(d, w, c, p, b)) return -1;
   for (size_t g0 = 0; g0 < p.n_groups; g0 += p.gcap) {
     const uint32_t ng = (uint32_t)std::min(p.gcap, p.n_groups - g0);
@@ -3064,7 +3104,9 @@ struct DutyShard {
 // INVARIANT (hbls_duty_add_sets): what the host plan hands a kernel is never trusted as an address.
 // set_off is validated on the host before anything is enqueued, and k_duty_set_first and the gate
 // (dutysel.h duty_admit) still check an item's set id against n_sets before it indexes set_first,
-// as k_duty_store checks a touched group against the shard's groups.
+// as k_duty_store checks a touched group against the shard's groups.  hbls_duty_add_sets_first hands the
+// verification the groups' and items' set ids as well (VerifyCall::gseg / item_seg): dutyfirst.hip's kernels
+// check each against n_seg in the same way.
 struct Duty {
   std::mutex mu;
   bool closed = false, broken = false;
@@ -3073,6 +3115,7 @@ struct Duty {
   std::vector<DutyShard> sh;
   uint64_t stats[6] = {};
   uint64_t set_stats[3] = {};  // hbls_duty_set_stats: sets seen, sets rejected, verified partials of rejected sets
+  uint64_t first_stats[2] = {};  // hbls_duty_first_stats: partials through hbls_duty_add_sets_first, those reported UNCHECKED
 };
 std::mutex g_duty_mu;
 std::unordered_map<uint64_t, std::shared_ptr<Duty>> g_duties;
@@ -3153,6 +3196,9 @@ struct DutySetCall {
   const uint32_t* set_off = nullptr;
   size_t n_sets = 0;
   std::vector<uint32_t> set_of;
+  // hbls_duty_add_sets_first: the shards plan set-major (hduty.h group_by_set) and verify segmented
+  // (VerifyCall::gseg), which leaves set_first where k_duty_set_first would; the gate and the store are the same
+  bool first = false;
 };
 
 // One shard's part of an add: its items (caller indices, increasing).  As with
@@ -3162,7 +3208,9 @@ struct DutySetCall {
 // copies, and, behind the one host wait, the aggregation of what fired.  hbls_duty_add runs the two
 // back to back as one stream segment under one hold of the device lock.  hbls_duty_add_sets does
 // the same on one shard, with k_duty_set_first and k_duty_gate between the verification and the
-// store.  On several shards a set's verdict needs every shard's verification, so verify(split)
+// store; hbls_duty_add_sets_first likewise, except that the verification itself, run segmented over a
+// set-major plan, leaves each set's first failure where k_duty_set_first would (DutySetCall::first).
+// On several shards a set's verdict needs every shard's verification, so verify(split)
 // ends phase one: it hands its workspace set back, waits for the shard's set_first and returns
 // with no device lock held, the caller joins the shards and merges, and store(merged) is phase two.
 // INVARIANT (host-call contexts): a context is one of a bounded pool per device that other calls
@@ -3249,7 +3297,9 @@ int DutyShardAdd::verify_(bool two_phases) {
   Dev& d = *sh.d;
   if (!hcs) hcs.reset(new HcLease(d));
   Hc& h = *hcs->h[0];
-  duty_plan_shard(msgs, msg_off, msg_len, group, share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p);
+  const bool seg = sets && sets->first;
+  duty_plan_shard(msgs, msg_off, msg_len, group, share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p,
+                  seg ? sets->set_of.data() : nullptr);
   std::vector<uint32_t> hsid;
   if (sets) duty_plan_sets(sets->set_of, p, hsid);
   nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
@@ -3280,7 +3330,7 @@ int DutyShardAdd::verify_(bool two_phases) {
   }
   uint8_t *dpk, *dsig, *dmsg;
   uint64_t* doff;
-  uint32_t *dlen, *dvgoff, *darr = nullptr;
+  uint32_t *dlen, *dvgoff, *darr = nullptr, *dgseg = nullptr;
   if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
   PinnedUploads up;
   up.add(I_MSG, sh.tab.t.bytes.data() + nb0, sh.tab.t.bytes.size() - (nnew ? nb0 : sh.tab.t.bytes.size()), &dmsg);
@@ -3297,6 +3347,7 @@ int DutyShardAdd::verify_(bool two_phases) {
     up.add(I_DSETID, hsid.data(), m, &dsid);
     up.add(I_DARR, p.order.data(), m, &darr);
   }
+  if (seg) up.add(I_DGSEG, p.vgset.data(), p.vgset.size(), &dgseg);
   if (sets && (ensure_buf(h.io[I_DSETFIRST], n_sets * sizeof(uint32_t), &psetfirst) || ensure_buf(h.io[I_DADMIT], m, &padmit)))
     return -1;
   if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_DSTORED], m, &pstored) ||
@@ -3326,10 +3377,17 @@ int DutyShardAdd::verify_(bool two_phases) {
   vc.s = s;
   vc.device_entry = true;
   vc.hm_ready = w.ev_side[2];
+  if (seg) {  // one first failure per set: the verification itself leaves set_first (preset by it)
+    vc.gseg = dgseg;
+    vc.n_seg = (uint32_t)n_sets;
+    vc.item_seg = dsid;
+    vc.item_arrival = darr;
+    vc.seg_first_out = (uint32_t*)psetfirst;
+  }
   if (verify_pipeline(d, w, vc)) return -1;
   HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
   vsig = vc.vsig;
-  if (sets) {
+  if (sets && !seg) {
     HCHK(hipMemsetAsync(psetfirst, 0xff, std::max<size_t>(n_sets, 1) * sizeof(uint32_t), s));
     TIMED(d, "k_duty_set_first", s,
           launch_duty_set_first((const uint8_t*)pst, dsid, darr, (uint32_t)m, (uint32_t*)psetfirst, (uint32_t)n_sets, s));
@@ -3558,7 +3616,8 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
              uint8_t* stored, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status,
              uint8_t* agg_vstatus, const DutySetCall* sets = nullptr, uint32_t* set_first = nullptr) {
   const size_t nd = du.sh.size(), t = du.t, n_sets = sets ? sets->n_sets : 0;
-  const std::string who = sets ? "hbls_duty_add_sets" : "hbls_duty_add";
+  const char* const who_c = !sets ? "hbls_duty_add" : sets->first ? "hbls_duty_add_sets_first" : "hbls_duty_add_sets";
+  const std::string who = who_c;
   const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
   std::vector<std::vector<uint32_t>> items;
   duty_route(group, n, du.n_groups, nd, items);
@@ -3582,7 +3641,7 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
     a.stored = stored;
     a.out_ = &outs[k];
     a.sets = sets;
-    a.who = sets ? "hbls_duty_add_sets" : "hbls_duty_add";
+    a.who = who_c;
   }
   std::vector<int> rc(nd, 0);
   std::vector<std::string> errs(nd);
@@ -3639,6 +3698,10 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
     du.set_stats[0] += n_sets;
     du.set_stats[1] += rejected;
     du.set_stats[2] += lost;
+    if (sets->first) {
+      du.first_stats[0] += n;
+      for (size_t i = 0; i < n; i++) du.first_stats[1] += vstatus[i] == HBLS_UNCHECKED ? 1 : 0;
+    }
   }
   size_t nf = 0;  // the shards own ascending ranges of the groups: their lists concatenate in order
   for (size_t k = 0; k < nd; k++) {
@@ -4414,29 +4477,31 @@ int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const 
                   ta_out, ta_status, agg_vstatus);
 }
 
-int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
-                       const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n,
-                       const uint32_t* set_off, size_t n_sets, uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial,
-                       uint32_t* set_first, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
-                       uint8_t* ta_status, uint8_t* agg_vstatus) {
+// hbls_duty_add_sets and hbls_duty_add_sets_first: one argument check, one call
+static int duty_add_sets_entry(bool first, uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                               const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
+                               const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets, uint8_t* vstatus,
+                               uint8_t* stored, uint32_t* first_serial, uint32_t* set_first, uint32_t* fired, size_t* n_fired,
+                               uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
+  const std::string who = first ? "hbls_duty_add_sets_first" : "hbls_duty_add_sets";
   if (ensure_init()) return -1;
   std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_add_sets: no such duty (never opened, or closed)");
+  if (!du) return set_err(who + ": no such duty (never opened, or closed)");
   std::lock_guard<std::mutex> l(du->mu);
-  if (du->closed) return set_err("hbls_duty_add_sets: the duty is closed");
-  if (du->broken) return set_err("hbls_duty_add_sets: an earlier add failed on a device; close the duty");
-  if (!first_serial || !n_fired) return set_err("hbls_duty_add_sets: first_serial and n_fired are required");
-  if (n >= 0xffffffffull - du->next_serial) return set_err("hbls_duty_add_sets: the duty would reach 2^32 - 1 partials");
-  if (n_sets >= 0xffffffffull) return set_err("hbls_duty_add_sets: too many sets");
-  if (n_sets && !set_first) return set_err("hbls_duty_add_sets: set_first is required");
-  if (const char* bad = duty_check_sets(set_off, n_sets, n)) return set_err(std::string("hbls_duty_add_sets: ") + bad);
+  if (du->closed) return set_err(who + ": the duty is closed");
+  if (du->broken) return set_err(who + ": an earlier add failed on a device; close the duty");
+  if (!first_serial || !n_fired) return set_err(who + ": first_serial and n_fired are required");
+  if (n >= 0xffffffffull - du->next_serial) return set_err(who + ": the duty would reach 2^32 - 1 partials");
+  if (n_sets >= 0xffffffffull) return set_err(who + ": too many sets");
+  if (n_sets && !set_first) return set_err(who + ": set_first is required");
+  if (const char* bad = duty_check_sets(set_off, n_sets, n)) return set_err(who + ": " + bad);
   if (n && (!pks || !sigs || !msg_off || !msg_len || !group || !share_idx || !vstatus || !stored))
-    return set_err("hbls_duty_add_sets: pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
+    return set_err(who + ": pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
   if (!msgs)
     for (size_t i = 0; i < n; i++)
-      if (msg_len[i]) return set_err("hbls_duty_add_sets: msgs is required");
+      if (msg_len[i]) return set_err(who + ": msgs is required");
   if (std::min(n, du->n_groups) && (!fired || !chosen || !ta_out || !ta_status || !agg_vstatus))
-    return set_err("hbls_duty_add_sets: fired, chosen, ta_out, ta_status and agg_vstatus are required");
+    return set_err(who + ": fired, chosen, ta_out, ta_status and agg_vstatus are required");
   *first_serial = du->next_serial;
   *n_fired = 0;
   if (!n) {  // empty sets only: seen, none rejected
@@ -4447,9 +4512,39 @@ int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, c
   DutySetCall sc;
   sc.set_off = set_off;
   sc.n_sets = n_sets;
+  sc.first = first;
   duty_set_ids(set_off, n_sets, n, sc.set_of);
   return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
                   ta_out, ta_status, agg_vstatus, &sc, set_first);
+}
+
+int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                       const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n,
+                       const uint32_t* set_off, size_t n_sets, uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial,
+                       uint32_t* set_first, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
+                       uint8_t* ta_status, uint8_t* agg_vstatus) {
+  return duty_add_sets_entry(false, duty, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, set_off, n_sets, vstatus,
+                             stored, first_serial, set_first, fired, n_fired, chosen, ta_out, ta_status, agg_vstatus);
+}
+
+int hbls_duty_add_sets_first(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                             const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
+                             const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets, uint8_t* vstatus,
+                             uint8_t* stored, uint32_t* first_serial, uint32_t* set_first, uint32_t* fired, size_t* n_fired,
+                             uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
+  return duty_add_sets_entry(true, duty, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, set_off, n_sets, vstatus,
+                             stored, first_serial, set_first, fired, n_fired, chosen, ta_out, ta_status, agg_vstatus);
+}
+
+int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err("hbls_duty_first_stats: no such duty (never opened, or closed)");
+  if (!out || n > 2) return set_err("hbls_duty_first_stats: out is null or n above 2");
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err("hbls_duty_first_stats: the duty is closed");
+  for (size_t k = 0; k < n; k++) out[k] = du->first_stats[k];
+  return 0;
 }
 
 int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n) {

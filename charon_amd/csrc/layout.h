@@ -576,6 +576,23 @@ struct ScatterArgs {
   const uint32_t* first_group;
 };
 void launch_scatter(const ScatterArgs& a, hipStream_t s);
+// Segmented first-error mode (dutyfirst.hip; the rule is dutyfirst.h's): the call's groups are cut into
+// n_seg ordered segments, gseg[g] the segment of group g (every group of the call), and each segment
+// gets its own first failure.  sfirst: two words per segment, preset to 0xff bytes before the first
+// chunk -- [2k] the key of the failing batch that descends for segment k besides its head batch, [2k + 1]
+// its first group whose own check failed.  launch_seg_batch_verdict stands where launch_batch_verdict
+// does with `first`, launch_seg_first_group and launch_seg_scatter (items only: no folded aggregates)
+// where launch_first_group and launch_scatter do.  launch_seg_first_item: set_first[k] (preset likewise)
+// = the smallest arrival[q] over the items q of segment item_seg[q] == k whose status is decided and
+// not OK.
+void launch_seg_batch_verdict(const uint8_t* gst, const uint8_t* bver, uint32_t ng, uint8_t* gver, uint32_t* list,
+                              uint32_t* count, hipStream_t s, const uint8_t* guard, uint32_t fe_batch, uint32_t g0,
+                              const uint32_t* gseg, uint32_t n_seg, uint32_t* sfirst);
+void launch_seg_first_group(const uint8_t* gver, uint32_t n_groups, const uint32_t* gseg, uint32_t n_seg, uint32_t* sfirst,
+                            hipStream_t s);
+void launch_seg_scatter(const ScatterArgs& a, const uint32_t* gseg, uint32_t n_seg, const uint32_t* sfirst, hipStream_t s);
+void launch_seg_first_item(const uint8_t* status, const uint32_t* item_seg, const uint32_t* arrival, uint32_t n,
+                           uint32_t* set_first, uint32_t n_seg, hipStream_t s);
 // fallback: lines at -g1 of the listed signatures (entries >= n_items: folded aggregates)
 void launch_fb_lines(const uint32_t* list, const uint32_t* count, uint32_t base, uint32_t cap, const HmEntry* sig,
                      const HmEntry* agg_sig, uint32_t n_items, LineEntry* lines, hipStream_t s);

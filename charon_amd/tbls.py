@@ -372,7 +372,15 @@ class Duty:
         verify, not at all -- ParSigEx.handle followed by StoreExternal, per set."""
         return self._add(pks, msgs, sigs, groups, share_idx, [int(x) for x in set_off])
 
-    def _add(self, pks, msgs, sigs, groups, share_idx, set_off):
+    def add_sets_first(self, pks: Sequence[bytes], msgs: Sequence[bytes], sigs: Sequence[bytes], groups: Sequence[int],
+                       share_idx: Sequence[int], set_off: Sequence[int]) -> DutySetsAdd:
+        """add_sets that stops a rejected set at its first failure (hbls_duty_add_sets_first): `set_first`,
+        `stored` and the fired rows are add_sets', and so is `vstatus` of every admitted set; in a rejected
+        set the partial at set_first carries its exact status, those before it are OK and the others
+        carry their exact status or UNCHECKED."""
+        return self._add(pks, msgs, sigs, groups, share_idx, [int(x) for x in set_off], first_error=True)
+
+    def _add(self, pks, msgs, sigs, groups, share_idx, set_off, first_error=False):
         n, t = len(pks), self.threshold
         if not (n == len(msgs) == len(sigs) == len(groups) == len(share_idx)):
             raise TblsError("duty add: length mismatch")
@@ -395,9 +403,10 @@ class Duty:
                 raise TblsError("duty add_sets: set_off out of range")
             n_sets = max(len(set_off) - 1, 0)
             sf = (ctypes.c_uint32 * max(n_sets, 1))()
-            check(self._L.hbls_duty_add_sets(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n,
-                                             _u32_array(set_off) if set_off else None, n_sets, vst, stored, ctypes.byref(first),
-                                             sf, fired, ctypes.byref(nf), chosen, out, tst, ast))
+            call = self._L.hbls_duty_add_sets_first if first_error else self._L.hbls_duty_add_sets
+            check(call(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n,
+                       _u32_array(set_off) if set_off else None, n_sets, vst, stored, ctypes.byref(first),
+                       sf, fired, ctypes.byref(nf), chosen, out, tst, ast))
             r = DutySetsAdd()
             r.set_first = [None if x == 0xFFFFFFFF else int(x) for x in sf[:n_sets]]
         f = nf.value
@@ -426,6 +435,13 @@ class Duty:
         out = (ctypes.c_uint64 * 3)()
         check(self._L.hbls_duty_set_stats(self._handle(), out, 3))
         return dict(zip(("sets", "rejected", "verified_not_stored"), (int(x) for x in out)))
+
+    def first_stats(self) -> Dict[str, int]:
+        """hbls_duty_first_stats: the partials that went through add_sets_first, and those it reported
+        UNCHECKED."""
+        out = (ctypes.c_uint64 * 2)()
+        check(self._L.hbls_duty_first_stats(self._handle(), out, 2))
+        return dict(zip(("partials", "unchecked"), (int(x) for x in out)))
 
     def close(self) -> None:
         if self._h is not None:

@@ -462,6 +462,34 @@ int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, c
                        uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
                        uint8_t* ta_status, uint8_t* agg_vstatus);
 int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n);
+/* hbls_duty_add_sets that stops a rejected set at its first failure (parsigex.go:93-98 returns at the
+ * first failing partial of a set): the same arguments and outputs, freely mixed with hbls_duty_add and
+ * hbls_duty_add_sets on one duty, and everything not named here means what it means there.  A set
+ * that is thrown away no longer costs the exact status of each of its partials, however many are bad.
+ *   set_first[k]: exact -- the smallest i of set k, in arrival order, whose status from
+ *   hbls_verify_batch would not be HBLS_OK; 0xffffffff when there is none.
+ *   vstatus of an admitted set: every partial HBLS_OK (exact: nothing failed).
+ *   vstatus of a rejected set k, f = set_first[k]: vstatus[f] is the exact status (not OK); every i < f
+ *   of the set is HBLS_OK; every other partial of the set carries its exact status or HBLS_UNCHECKED,
+ *   nothing else.  Decoding failures are exact everywhere; verify-only partials belong to their set.
+ *   Below the batched final exponentiation's size (hbls_fe_batch) every status is exact.
+ *   On a twin duty given the same calls through hbls_duty_add_sets, set_first, stored, first_serial,
+ *   the fired rows (fired, n_fired, chosen, ta_out, ta_status, agg_vstatus), hbls_duty_state,
+ *   hbls_duty_stats and hbls_duty_set_stats out[0] and out[1] are equal; out[2] counts the partials of
+ *   rejected sets reported HBLS_OK and is at most the twin's.
+ *   The partials are verified in arrival order (set by set), in runs of consecutive partials over one
+ *   message: a call of many sets over the same messages forms smaller groups than hbls_duty_add_sets,
+ *   which sorts the call by message.  Take this call for a peer's set as it arrives, or whenever sets
+ *   may be bad; take hbls_duty_add_sets for a large window of sets known to be clean.
+ * hbls_duty_first_stats (cumulative, n <= 2): out[0] partials that went through this call, out[1]
+ *   those reported HBLS_UNCHECKED. */
+int hbls_duty_add_sets_first(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
+                             const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
+                             const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets,
+                             uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial, uint32_t* set_first,
+                             uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
+                             uint8_t* ta_status, uint8_t* agg_vstatus);
+int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the

@@ -1,20 +1,23 @@
-"""Set-atomic duty adds (hbls_duty_add_sets) against hbls_duty_add on the same arrival, on one GPU.
+"""Set-atomic duty adds (hbls_duty_add_sets, hbls_duty_add_sets_first) against hbls_duty_add on the same
+arrival, on one GPU.
 
-    python tools/duty_sets_bench.py --tag new    [--rounds 3] [--legs add,sets,window] --out new_1.json
+    python tools/duty_sets_bench.py --tag new    [--rounds 3] [--legs add,sets,window,first,first_window] --out new_1.json
     python tools/duty_sets_bench.py --tag parent  --legs add                            --out parent_1.json
     python tools/duty_sets_bench.py --merge parent_1.json new_1.json ... --out profiles/duty_sets_bench.json
 
 Inputs as tools/duty_bench.py's (whose output this tool leaves alone): C3, 100 k validators 7 of 10,
-clean; the C5 shard, 125 k validators 5 of 7, clean and at 1 % corrupted partials, arriving as n
+clean; the C5 shard, 125 k validators 5 of 7, clean and at 1 % and 10 % corrupted partials, arriving as n
 peer-major sets of V partials.  One duty per leg and round, one call at a time, legs alternating:
   add     n hbls_duty_add, one per peer's set (runs on a library without the set-atomic call: --tag
           parent under HBLS_LIBRARY is the parent commit's figure)
   sets    n hbls_duty_add_sets, one set per call
   window  every peer's set of the duty as ONE hbls_duty_add_sets call of n sets
+  first, first_window  as sets and window, through hbls_duty_add_sets_first: a rejected set stops at its first
+          failure (reported with them: the partials it left HBLS_UNCHECKED, hbls_duty_first_stats)
 Per leg: the time per duty (open and close included), the time of every call, the validators that
 fired and the sets rejected.  On the clean streams every leg must end with every validator's
-aggregate; at 1 % corrupted every set of 125 k partials holds a bad one, so `sets` and `window`
-reject every set and fire nothing -- what is measured there is the cost of a rejected set.
+aggregate; at 1 % and 10 % corrupted every set of 125 k partials holds a bad one, so every leg but `add`
+rejects every set and fires nothing -- what is measured there is the cost of a rejected set.
 --split N runs the legs over N contexts of the one GPU (hbls_debug_split): a duty of N shards, where
 hbls_duty_add_sets takes its two-phase path; give such a run a tag of its own (--tag new_split2).
 --merge puts the runs of several processes (alternating libraries) side by side: medians and spreads
@@ -33,7 +36,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-CONFIGS = [("c3_clean", "c3", 0.0), ("c5_clean", "c5", 0.0), ("c5_1pct", "c5", 0.01)]
+CONFIGS = [("c3_clean", "c3", 0.0), ("c5_clean", "c5", 0.0), ("c5_1pct", "c5", 0.01), ("c5_10pct", "c5", 0.1)]
+LEGS = ("add", "sets", "window", "first", "first_window")
 
 
 def summary(xs):
@@ -52,6 +56,8 @@ def merge(paths, out):
             for leg, v in c["legs"].items():
                 e = m.setdefault("legs", {}).setdefault(d["tag"] + ":" + leg, {"total": [], "calls": [], "fired": v["fired"],
                                                                               "sets_rejected": v["sets_rejected"]})
+                if "unchecked" in v:
+                    e["unchecked"] = v["unchecked"]
                 e["total"] += v["total_ms"]["runs"]
                 e["calls"] += v["calls_ms_runs"]
     for c in res["configs"].values():
@@ -72,7 +78,7 @@ def main(argv=None):
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--validators", type=int, default=0, help="override the shard size (smoke runs)")
     ap.add_argument("--configs", default=",".join(c[0] for c in CONFIGS))
-    ap.add_argument("--legs", default="add,sets,window")
+    ap.add_argument("--legs", default=",".join(LEGS))
     ap.add_argument("--tag", default="new")
     ap.add_argument("--split", type=int, default=1, help="hbls_debug_split(N): N contexts (shards) on the one GPU")
     ap.add_argument("--merge", nargs="+")
@@ -113,8 +119,8 @@ def main(argv=None):
         bad_sets = int((d["exp_v"].reshape(V, n) != 0).any(axis=0).sum())  # peer k's set holds a bad partial
 
         def duty(mode):
-            """mode: add / sets (one call per peer's set) or window (one call)"""
-            per = NP if mode == "window" else V
+            """mode: add / sets / first (one call per peer's set) or window / first_window (one call)"""
+            per = NP if mode.endswith("window") else V
             n_calls = NP // per
             vst, stored = np.full(per, 255, np.uint8), np.zeros(per, np.uint8)
             rows = min(per, V)
@@ -124,6 +130,7 @@ def main(argv=None):
             set_off, set_first = np.arange(n_sets + 1, dtype=np.uint32) * V, np.zeros(n_sets, np.uint32)
             first, nf, h = ctypes.c_uint32(0), ctypes.c_size_t(0), ctypes.c_uint64(0)
             calls, good, rejected = [], 0, 0
+            add_sets = L.hbls_duty_add_sets_first if mode.startswith("first") else L.hbls_duty_add_sets
             t0 = time.perf_counter()
             _chk(L, L.hbls_duty_open(_p(d["dv_pks"]), V, t, n, ctypes.byref(h)))
             t_open = (time.perf_counter() - t0) * 1e3
@@ -135,7 +142,7 @@ def main(argv=None):
                 if mode == "add":
                     _chk(L, L.hbls_duty_add(*a, _p(vst), _p(stored), ctypes.byref(first), *b))
                 else:
-                    _chk(L, L.hbls_duty_add_sets(*a, _p(set_off), n_sets, _p(vst), _p(stored), ctypes.byref(first), _p(set_first), *b))
+                    _chk(L, add_sets(*a, _p(set_off), n_sets, _p(vst), _p(stored), ctypes.byref(first), _p(set_first), *b))
                 calls.append((time.perf_counter() - t1) * 1e3)
                 f = nf.value
                 ok = (tst[:f] == 0) & (ast[:f] == 0)
@@ -143,12 +150,17 @@ def main(argv=None):
                 good += int(ok.sum())
                 if mode != "add":
                     rejected += int((set_first != 0xFFFFFFFF).sum())
+            if mode.startswith("first"):
+                fs = np.zeros(2, np.uint64)
+                _chk(L, L.hbls_duty_first_stats(h.value, _p(fs), 2))
+                unchecked[mode] = int(fs[1])
             t2 = time.perf_counter()
             _chk(L, L.hbls_duty_close(h.value))
             t_close = (time.perf_counter() - t2) * 1e3
             return dict(total=sum(calls) + t_open + t_close, calls=calls), good, rejected
 
-        legs = [k for k in ("add", "sets", "window") if k in want_legs]
+        unchecked = {}
+        legs = [k for k in LEGS if k in want_legs]
         for k in legs:  # warm-up: workspaces, staging buffers, learned keys
             duty(k)
         runs, got, rej = {k: [] for k in legs}, {}, {}
@@ -167,7 +179,8 @@ def main(argv=None):
         result["configs"][name] = {
             "workload": wl_name, "validators": V, "n": n, "t": t, "corrupted_fraction": frac,
             "legs": {k: {"total_ms": summary([r["total"] for r in runs[k]]), "calls_ms_runs": [r["calls"] for r in runs[k]],
-                         "fired": got[k], "sets_rejected": rej[k]} for k in legs},
+                         "fired": got[k], "sets_rejected": rej[k], **({"unchecked": unchecked[k]} if k in unchecked else {})}
+                     for k in legs},
         }
         print(name, json.dumps({k: result["configs"][name]["legs"][k]["total_ms"] for k in legs}), flush=True)
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
