@@ -2782,6 +2782,80 @@ int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* go
   return 0;
 }
 
+// The selection-and-aggregation tail shared by slot_select_core (phases 2-4) and a duty shard's
+// aggregation of its fired groups (DutyShardAdd::aggregate_fired_): sel_ws, the caller's own kernel that
+// fills the groups' candidates (k_ta_select / k_duty_gather), sel_aggregate, sel_verify.  SelWs: sa's buffers
+// (the rest of sa is the caller's), the aggregation's rows in class order, the aggregates for sel_verify
+struct SelWs {
+  TaSelectArgs sa{};
+  uint8_t *pout = nullptr, *pst = nullptr, *ast = nullptr;
+  HmEntry *ppt = nullptr, *apt = nullptr;
+};
+
+// ng groups of t members in workspace set w; enqueues the histogram's reset, the tail's first operation on s
+int sel_ws(Ws& w, size_t ng, size_t t, hipStream_t s, SelWs& x) {
+  TaSelectArgs& sa = x.sa;
+  if (wsbuf(w, W_SELCIDX, ng * t, &sa.cidx) || wsbuf(w, W_SELKEY, ng, &sa.key) || wsbuf(w, W_SELSTATE, ng, &sa.state) ||
+      wsbuf(w, W_SELGMSG, ng, &sa.gmsg) || wsbuf(w, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
+      wsbuf(w, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w, W_SELPERM, ng, &sa.perm) ||
+      wsbuf(w, W_SELPMEM, ng * t, &sa.pmem) || wsbuf(w, W_SELPIDX, ng * t, &sa.pidx) ||
+      wsbuf(w, W_SELPGOFF, ng + 1, &sa.pgoff) || wsbuf(w, W_SELPOUT, 96 * ng, &x.pout) || wsbuf(w, W_SELPST, ng, &x.pst) ||
+      wsbuf(w, W_SELPPT, ng, &x.ppt) || wsbuf(w, W_SELAPT, ng, &x.apt) || wsbuf(w, W_SELAST, ng, &x.ast))
+    return -1;
+  sa.cur = sa.hist + TASEL_KEYS;
+  sa.n_groups = (uint32_t)ng;
+  sa.t = (uint32_t)t;
+  HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
+  return 0;
+}
+
+// The groups in class order, ThresholdAggregate over the chosen members of pts / pts_st (ta_tail on
+// w, x's workspace set), the rows back in group order into ta_out / ta_status, counted into ctr
+int sel_aggregate(Dev& d, Ws& w, SelWs& x, const HmEntry* pts, const uint8_t* pts_st, uint8_t* ta_out, uint8_t* ta_status,
+                  uint64_t* ctr, hipStream_t s) {
+  TaSelectArgs& sa = x.sa;
+  const size_t ng = sa.n_groups, t = sa.t;
+  TIMED(d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
+  TIMED(d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
+  const uint8_t* sdone = nullptr;
+  if (ta_tail(d, w, pts, sa.pmem, pts_st, sa.pidx, sa.pgoff, ng, ng * t, 0, x.pout, x.pst, x.ppt, s, nullptr, nullptr, &sdone))
+    return -1;
+  TaScatterArgs sc{};
+  sc.n_groups = (uint32_t)ng;
+  sc.perm = sa.perm;
+  sc.state = sa.state;
+  sc.pout = x.pout;
+  sc.pstatus = x.pst;
+  sc.ppt = x.ppt;
+  sc.sdone = sdone;
+  sc.ta_out = ta_out;
+  sc.ta_status = ta_status;
+  sc.rows16 = (((uintptr_t)ta_out | (uintptr_t)x.pout) & 15) == 0 ? 1 : 0;
+  sc.agg_pt = x.apt;
+  sc.agg_st = x.ast;
+  sc.ctr = ctr;
+  TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+  return 0;
+}
+
+// The aggregates verified, one item per group: a second verify_pipeline on workspace set w, handed
+// the affine aggregates in place of signature bytes (pre_sig); a group without an aggregate is an
+// item with a bad signature status, which costs no pairing.  v2 comes with the caller's own fields (pks,
+// hm, fold, defer_hm, defer_msgs).  Then the groups' verdicts
+int sel_verify(Dev& d, Ws& w, const SelWs& x, VerifyCall& v2, const uint8_t* ta_status, uint8_t* agg_vstatus, hipStream_t s) {
+  const size_t ng = x.sa.n_groups;
+  v2.pre_sig = x.apt;
+  v2.pre_sigst = x.ast;
+  v2.msg_idx = x.sa.gmsg;
+  v2.n = ng;
+  v2.n_groups = ng;
+  v2.status = agg_vstatus;
+  v2.s = s;
+  if (verify_pipeline(d, w, v2)) return -1;
+  TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(ta_status, (uint32_t)ng, agg_vstatus, s));
+  return 0;
+}
+
 // The core of hbls_slot_select_device and hbls_slot_select_batch: hbls_slot_device with
 // verified-member selection, over device buffers (a: as the device entry takes it, checked by the
 // caller, who holds d.mu) on stream s.  mode: how members are picked (tasel.h TASEL_MODE_*).
@@ -2793,11 +2867,10 @@ int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* go
 // Four phases on the stream, each behind the one before (the aggregation needs the verdicts, the
 // second verification the aggregates):
 //   1. hash, and verify the partials without a fold (workspace set w: the decompressed partials stay)
-//   2. select each group's members and put the groups in class order (threshold.hip k_ta_select ...)
-//   3. ThresholdAggregate over the chosen members through src into the retained points (ta_tail)
-//   4. verify the aggregates under the DV keys: a second verify_pipeline on the next workspace set,
-//      one item per group, handed the affine aggregates in place of signature bytes (pre_sig); a
-//      group without an aggregate is an item with a bad signature status, which costs no pairing
+//   2. select each group's members (threshold.hip k_ta_select) and put the groups in class order
+//   3. ThresholdAggregate over the chosen members through src into the retained points
+//      (sel_aggregate: the shared tail, with the class order of phase 2)
+//   4. verify the aggregates under the DV keys on the next workspace set (sel_verify: the shared tail)
 thread_local double g_core_marks[3];  // HBLS_HOST_TIMING: phase 1, phases 2-3 and phase 4 enqueued
 int slot_select_core(Dev& d, hipStream_t s, const hbls_slot& a, uint32_t threshold, uint32_t* chosen,
                      uint32_t* ta_count, uint32_t mode, bool behind_default) {
@@ -2850,59 +2923,34 @@ int slot_select_core(Dev& d, hipStream_t s, const hbls_slot& a, uint32_t thresho
     HCHK(hipMemset(ctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
     HCHK(hipStreamSynchronize(nullptr));
   }
-  TaSelectArgs sa{};
-  uint8_t *pout, *pst, *ast;
-  HmEntry *ppt, *apt;
-  if (wsbuf(w, W_SELCIDX, ng * t, &sa.cidx) || wsbuf(w, W_SELKEY, ng, &sa.key) || wsbuf(w, W_SELSTATE, ng, &sa.state) ||
-      wsbuf(w, W_SELGMSG, ng, &sa.gmsg) || wsbuf(w, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
-      wsbuf(w, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w, W_SELPERM, ng, &sa.perm) ||
-      wsbuf(w, W_SELPMEM, ng * t, &sa.pmem) || wsbuf(w, W_SELPIDX, ng * t, &sa.pidx) ||
-      wsbuf(w, W_SELPGOFF, ng + 1, &sa.pgoff) || wsbuf(w, W_SELPOUT, 96 * ng, &pout) || wsbuf(w, W_SELPST, ng, &pst) ||
-      wsbuf(w, W_SELPPT, ng, &ppt) || wsbuf(w, W_SELAPT, ng, &apt) || wsbuf(w, W_SELAST, ng, &ast))
-    return -1;
-  sa.cur = sa.hist + TASEL_KEYS;
+  SelWs x;
+  if (sel_ws(w, ng, t, s, x)) return -1;
+  TaSelectArgs& sa = x.sa;
   sa.vstatus = a.vstatus;
   sa.msg_idx = a.msg_idx;
   sa.n = (uint32_t)a.n;
   sa.src = a.ta_src;
   sa.idx = a.ta_idx;
   sa.grp_off = a.grp_off;
-  sa.n_groups = (uint32_t)ng;
   sa.n_cand = (uint32_t)a.n_ta_partials;
-  sa.t = threshold;
   sa.mode = mode;
   sa.chosen = chosen;
   sa.ta_count = ta_count;
   sa.ctr = ctr;
-  HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
   TIMED(d, "k_ta_select", s, launch_ta_select(sa, s));
-  TaScatterArgs sc{};
-  sc.n_groups = (uint32_t)ng;
-  sc.state = sa.state;
-  sc.ta_out = a.ta_out;
-  sc.ta_status = a.ta_status;
-  sc.ctr = ctr;
   if (!a.n) {  // no partial: no group has a member
+    TaScatterArgs sc{};
+    sc.n_groups = (uint32_t)ng;
+    sc.state = sa.state;
+    sc.ta_out = a.ta_out;
+    sc.ta_status = a.ta_status;
+    sc.ctr = ctr;
     TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
     TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a.ta_status, (uint32_t)ng, a.agg_vstatus, s));
     return ws_release(w, s);
   }
-  TIMED(d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
-  TIMED(d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
-  // phase 3
-  const uint8_t* sdone = nullptr;
-  if (ta_tail(d, w, vc.vsig, sa.pmem, vc.vsigst, sa.pidx, sa.pgoff, ng, ng * t, 0, pout, pst, ppt, s, nullptr, nullptr,
-              &sdone))
-    return -1;
-  sc.perm = sa.perm;
-  sc.pout = pout;
-  sc.pstatus = pst;
-  sc.ppt = ppt;
-  sc.sdone = sdone;
-  sc.rows16 = (((uintptr_t)a.ta_out | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
-  sc.agg_pt = apt;
-  sc.agg_st = ast;
-  TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
+  // phase 3, with the rest of phase 2
+  if (sel_aggregate(d, w, x, vc.vsig, vc.vsigst, a.ta_out, a.ta_status, ctr, s)) return -1;
   if (host_timing()) g_core_marks[1] = now_ms();
   // phase 4.  The messages' lines: computed by phase 1 unless it deferred them; then this pass
   // defers them too where its plan can (the batched sizes), else they are computed first
@@ -2921,20 +2969,12 @@ int slot_select_core(Dev& d, hipStream_t s, const hbls_slot& a, uint32_t thresho
   tables2.pk_table_st = a.dv_pk_table_st;
   VerifyCall v2;
   v2.pks = a.dv_pks;
-  v2.pre_sig = apt;
-  v2.pre_sigst = ast;
-  v2.msg_idx = sa.gmsg;
   v2.hm = (const MsgEntry*)a.hm;
-  v2.n = ng;
-  v2.n_groups = ng;
-  v2.status = a.agg_vstatus;
-  v2.s = s;
   v2.fold = a.dv_pk_table ? &tables2 : nullptr;
   v2.defer_hm = (MsgEntry*)a.hm;
   v2.defer_msgs = defer2;
-  if (verify_pipeline(d, w2, v2)) return -1;
+  if (sel_verify(d, w2, x, v2, a.ta_status, a.agg_vstatus, s)) return -1;
   if (host_timing()) g_core_marks[2] = now_ms();
-  TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts(a.ta_status, (uint32_t)ng, a.agg_vstatus, s));
   if (ws_release(w, s)) return -1;
   return &w2 == &w ? 0 : ws_release(w2, s);
 }
@@ -3201,14 +3241,32 @@ struct DutySetCall {
   bool first = false;
 };
 
+// What a duty add was called with (include/hipbls.h), checked by duty_add_entry
+struct DutyAddArgs {
+  const uint8_t *pks, *sigs, *msgs;
+  const uint64_t* msg_off;
+  const uint32_t *msg_len, *group;
+  const int64_t* share_idx;
+  size_t n;
+  uint8_t *vstatus, *stored;
+  uint32_t *first_serial, *fired;
+  size_t* n_fired;
+  uint32_t* chosen;
+  uint8_t *ta_out, *ta_status, *agg_vstatus;
+  const char* who;
+  const DutySetCall* sets;  // the set entry points (null: hbls_duty_add): the call's sets,
+  uint32_t* set_first;      // and their first failures (n_sets entries) to fill
+};
+
 // One shard's part of an add: its items (caller indices, increasing).  As with
 // hbls_slot_select_batch, the shard's add is one verification: it is not chunked.
 //
-// verify() enqueues the upload, the hashing and the verification, store() the storing rule, the
-// copies, and, behind the one host wait, the aggregation of what fired.  hbls_duty_add runs the two
-// back to back as one stream segment under one hold of the device lock.  hbls_duty_add_sets does
-// the same on one shard, with k_duty_set_first and k_duty_gate between the verification and the
-// store; hbls_duty_add_sets_first likewise, except that the verification itself, run segmented over a
+// verify() enqueues the upload, the hashing and the verification; store() runs gate_(), store_rule_()
+// (with the copies), download_() (the one host wait) and, where a group fired, aggregate_fired_() (the
+// tail shared with slot_select_core) and download_fired_().  hbls_duty_add runs the two back to back
+// as one stream segment under one hold of the device lock.  hbls_duty_add_sets does the same on one
+// shard, with k_duty_set_first and k_duty_gate between the verification and the store;
+// hbls_duty_add_sets_first likewise, except that the verification itself, run segmented over a
 // set-major plan, leaves each set's first failure where k_duty_set_first would (DutySetCall::first).
 // On several shards a set's verdict needs every shard's verification, so verify(split)
 // ends phase one: it hands its workspace set back, waits for the shard's set_first and returns
@@ -3226,45 +3284,50 @@ struct DutySetCall {
 // device lock (ws_acquire hands the sets out round-robin and orders their users by free_ev alone),
 // so what phase two reads of the verification -- the decompressed signatures k_duty_copy moves -- is
 // copied into the context's staging before the set is handed back.
-// Members: "the call" is set by duty_add before verify(); the rest is written by verify_() and read
-// by store_().  `lk` is held from the first upload of a phase to its last enqueue only, and never
-// when verify() / store() return; `w` is non-null from the verification's ws_acquire until the
-// ws_release at the end of phase one (two phases) or of the store's enqueues (one segment), and
-// stays unreleased, as it always did, when an enqueue fails in between; `hcs` is held from lease()
-// or verify() until store() returns (or verify() fails); the device pointers are valid while it is.
+// Members: "the call" is set by duty_add (the constructor); the rest is written by verify_() and the
+// steps of store_() and read by the steps behind them.  `lk` is held from the first upload of a phase
+// to its last enqueue only -- taken by verify_(), gate_() (phase two) and aggregate_fired_(), dropped by
+// verify_() (phase one), store_rule_() and aggregate_fired_() -- and never when verify() / store()
+// return; `w` is non-null from the verification's ws_acquire until the ws_release at the end of phase
+// one (two phases: verify_()) or of the store's enqueues (one segment: store_rule_()), and stays
+// unreleased, as it always did, when an enqueue fails in between; `hcs` is held from lease() or
+// verify() until store() returns (or verify() fails); the device pointers are valid while it is.
 struct DutyShardAdd {
   // the call
-  Duty* du_ = nullptr;
-  DutyShard* sh_ = nullptr;
-  const uint8_t *pks = nullptr, *sigs = nullptr, *msgs = nullptr;
-  const uint64_t* msg_off = nullptr;
-  const uint32_t *msg_len = nullptr, *group = nullptr;
-  const int64_t* share_idx = nullptr;
-  const std::vector<uint32_t>* items_ = nullptr;
-  uint32_t first_serial = 0;
-  size_t gmax = 0;
-  uint8_t *vstatus = nullptr, *stored = nullptr;
-  DutyShardOut* out_ = nullptr;
-  const DutySetCall* sets = nullptr;  // null: hbls_duty_add
-  const char* who = "hbls_duty_add";
-  // from verify() to store()
+  Duty& du;
+  DutyShard& sh;
+  Dev& d;
+  const DutyAddArgs& a;
+  const DutySetCall* const sets;  // null: hbls_duty_add
+  const size_t n_sets, t, ng, gmax;
+  const std::vector<uint32_t>& items;
+  const uint32_t first_serial;
+  DutyShardOut& out;
+  DutyShardAdd(Duty& du, DutyShard& sh, const DutyAddArgs& a, const std::vector<uint32_t>& items, size_t gmax, DutyShardOut& out)
+      : du(du), sh(sh), d(*sh.d), a(a), sets(a.sets), n_sets(sets ? sets->n_sets : 0), t(du.t), ng(sh.ge - sh.gb),
+        gmax(gmax), items(items), first_serial(du.next_serial), out(out) {}
+  // from verify() to store(), and from step to step of it
   std::unique_ptr<HcLease> hcs;
   DutyShardPlan p;
   std::unique_lock<std::mutex> lk;
   bool split = false;
-  size_t m = 0, nm = 0, nnew = 0, nt = 0, np = 0;
-  double t_start = 0, t_prep = 0;
+  size_t m = 0, nm = 0, nnew = 0, nt = 0, np = 0, nf = 0;
+  double t_start = 0, t_prep = 0, t_enq1 = 0, t_dev1 = 0, t_enq2 = 0;
   uint32_t *dmidx = nullptr, *dserial = nullptr, *dtgrp = nullptr, *dtoff = nullptr, *dtpos = nullptr, *dsid = nullptr;
   int64_t* dtidx = nullptr;
   void *pst = nullptr, *pstored = nullptr, *pslot = nullptr, *pmslot = nullptr, *pmser = nullptr, *pmidx = nullptr,
        *pfmsg = nullptr, *pfkey = nullptr, *pcopy = nullptr, *pfired = nullptr, *pctr = nullptr, *psetfirst = nullptr,
        *padmit = nullptr;
+  void *pser = nullptr, *pfg = nullptr, *ptout = nullptr, *ptst = nullptr, *past = nullptr;  // the fired groups' rows
   const HmEntry* vsig = nullptr;
+  DutyStoreArgs st{};             // the storing rule's arguments: the gather reads its per-group outputs
+  std::vector<uint32_t> hfired;   // the touched groups that fired (rows of the plan), downloaded
   Ws* w = nullptr;  // the verification's workspace set, until it is handed back
   std::vector<uint32_t> set_first;  // the sets' first failures as this shard saw them (one shard: the call's)
 
   int verify_(bool split);
   int store_(const uint32_t* merged);
+  int gate_(const uint32_t* merged), store_rule_(), download_(), aggregate_fired_(), download_fired_();  // its steps
   // the device lock never outlives the phase (nor, in a shard thread, the thread) that took it
   int verify(bool two_phases) {
     const int rc = verify_(two_phases);
@@ -3280,36 +3343,30 @@ struct DutyShardAdd {
   }
   // two phases: the shard's context, taken by duty_add in the global order before any shard starts
   void lease() {
-    if (!items_->empty()) hcs.reset(new HcLease(*sh_->d));
+    if (!items.empty()) hcs.reset(new HcLease(d));
   }
 };
 
 int DutyShardAdd::verify_(bool two_phases) {
-  Duty& du = *du_;
-  DutyShard& sh = *sh_;
-  const std::vector<uint32_t>& items = *items_;
-  DutyShardOut& out = *out_;
   split = two_phases;
   m = items.size();
   if (sets) set_first.assign(sets->n_sets, DUTY_NONE);
   if (!m) return 0;
   t_start = now_ms();
-  Dev& d = *sh.d;
   if (!hcs) hcs.reset(new HcLease(d));
   Hc& h = *hcs->h[0];
   const bool seg = sets && sets->first;
-  duty_plan_shard(msgs, msg_off, msg_len, group, share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p,
+  duty_plan_shard(a.msgs, a.msg_off, a.msg_len, a.group, a.share_idx, items, sh.gb, sh.ge, first_serial, gmax, sh.tab, p,
                   seg ? sets->set_of.data() : nullptr);
   std::vector<uint32_t> hsid;
   if (sets) duty_plan_sets(sets->set_of, p, hsid);
   nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
-  const size_t t = du.t, n_sets = sets ? sets->n_sets : 0;
   out.n_new_msgs = nnew;
   out.resident = p.resident;
   std::vector<uint8_t> hpk(48 * m), hsig(96 * m);
   for (size_t q = 0; q < m; q++) {
-    memcpy(&hpk[48 * q], pks + 48ull * p.order[q], 48);
-    memcpy(&hsig[96 * q], sigs + 96ull * p.order[q], 96);
+    memcpy(&hpk[48 * q], a.pks + 48ull * p.order[q], 48);
+    memcpy(&hsig[96 * q], a.sigs + 96ull * p.order[q], 96);
   }
   std::vector<uint64_t> noff(nnew);  // the new messages' offsets, from the first new byte
   const uint64_t nb0 = nnew ? sh.tab.t.off[sh.hashed] : 0;
@@ -3409,15 +3466,24 @@ int DutyShardAdd::verify_(bool two_phases) {
   return 0;
 }
 
+// The steps of store(), in order; hcs is held throughout; a failing step leaves lk as it is (store() drops it)
 int DutyShardAdd::store_(const uint32_t* merged) {
   if (!m) return 0;
-  Duty& du = *du_;
-  DutyShard& sh = *sh_;
-  DutyShardOut& out = *out_;
-  Dev& d = *sh.d;
+  if (gate_(merged) || store_rule_() || download_()) return -1;
+  t_enq2 = t_dev1;
+  if (nf && (aggregate_fired_() || download_fired_())) return -1;
+  if (host_timing())
+    fprintf(stderr, "hbls duty_add shard groups %zu..%zu n=%zu touched=%zu new msgs=%zu fired=%zu: plan %.2f ms, "
+            "enqueue verify+store %.2f, device %.2f, enqueue aggregate+verify %.2f, device %.2f\n", sh.gb, sh.ge, m, nt,
+            nnew, nf, t_prep - t_start, t_enq1 - t_prep, t_dev1 - t_enq1, t_enq2 - t_dev1, now_ms() - t_enq2);
+  return 0;
+}
+
+// Phase two's upload of the call's verdicts per set, and the gate of a set add.  One segment: lk and w
+// are held since verify_().  Two phases: neither is; takes lk.  Leaves lk held, w as it was.
+int DutyShardAdd::gate_(const uint32_t* merged) {
   Hc& h = *hcs->h[0];
   hipStream_t s = h.s;
-  const size_t t = du.t, ng = sh.ge - sh.gb, n_sets = sets ? sets->n_sets : 0;
   if (split) {  // phase two: every shard's store sees the call's verdicts per set
     lk.lock();
     if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
@@ -3427,17 +3493,22 @@ int DutyShardAdd::store_(const uint32_t* merged) {
     if (upload_pinned(d, h, upm)) return -1;
     psetfirst = dm;
   }
-  const uint8_t* seen = (const uint8_t*)pst;  // what the storing rule reads as the items' statuses
+  st.vstatus = (const uint8_t*)pst;  // what the storing rule reads as the items' statuses
   if (sets) {
     TIMED(d, "k_duty_gate", s,
           launch_duty_gate((const uint8_t*)pst, dsid, (uint32_t)m, (const uint32_t*)psetfirst, (uint32_t)n_sets,
                            (uint8_t*)padmit, s));
-    seen = (const uint8_t*)padmit;
+    st.vstatus = (const uint8_t*)padmit;
   }
-  // store: the rule per touched group, then the stored partials' points out of the workspace
+  return 0;
+}
+
+// store: the rule per touched group, then the stored partials' points out of the workspace.  Needs lk;
+// hands w back if it is still held (one segment), then drops lk: leaves neither.
+int DutyShardAdd::store_rule_() {
+  hipStream_t s = hcs->h[0]->s;
   HCHK(hipMemsetAsync(pstored, 0, m, s));
   HCHK(hipMemsetAsync(pctr, 0, DUTY_CTRS * sizeof(uint32_t), s));
-  DutyStoreArgs st{};
   st.rec_idx = sh.rec_idx;
   st.rec_msg = sh.rec_msg;
   st.rec_serial = sh.rec_serial;
@@ -3446,7 +3517,6 @@ int DutyShardAdd::store_(const uint32_t* merged) {
   st.n_groups = (uint32_t)ng;
   st.max_stored = du.max_stored;
   st.t = du.t;
-  st.vstatus = seen;
   st.msg_idx = dmidx;
   st.serial = dserial;
   st.n = (uint32_t)m;
@@ -3476,9 +3546,16 @@ int DutyShardAdd::store_(const uint32_t* merged) {
     w = nullptr;
   }
   lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
-  const double t_enq1 = now_ms();
+  t_enq1 = now_ms();
+  return 0;
+}
+
+// The items' verdicts and stored flags to the caller, nf and hfired to the host, behind the stream's end.
+// Needs and leaves no lock and no workspace set.
+int DutyShardAdd::download_() {
+  hipStream_t s = hcs->h[0]->s;
   std::vector<uint8_t> hst(m), hstored(m);
-  std::vector<uint32_t> hfired(nt);
+  hfired.assign(nt, 0);
   uint32_t hctr[DUTY_CTRS] = {};
   if (sets && !split && n_sets)  // one shard: the sets' verdicts come back with the items'
     HCHK(hipMemcpyAsync(set_first.data(), psetfirst, n_sets * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
@@ -3488,161 +3565,108 @@ int DutyShardAdd::store_(const uint32_t* merged) {
   if (nt) HCHK(hipMemcpyAsync(hfired.data(), pfired, nt * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
   HCHK(hipStreamSynchronize(s));
   sh.hashed = nm;
-  const double t_dev1 = now_ms();
+  t_dev1 = now_ms();
   for (size_t q = 0; q < m; q++) {
-    vstatus[p.order[q]] = hst[q];
-    stored[p.order[q]] = hstored[q];
+    a.vstatus[p.order[q]] = hst[q];
+    a.stored[p.order[q]] = hstored[q];
     out.n_stored += hstored[q] ? 1 : 0;
   }
   out.n_full = hctr[DUTY_CTR_FULL];
-  const size_t nf = hctr[DUTY_CTR_FIRED];
-  if (nf > nt) return set_err(std::string(who) + ": the fired list is longer than the touched groups");
-  double t_enq2 = t_dev1;
-  if (nf) {
-    // phases 3 and 4 of slot_select_core over the fired groups, ascending: their members are in the store
-    std::sort(hfired.begin(), hfired.begin() + nf);
-    for (size_t k = 0; k < nf; k++)
-      if (hfired[k] >= nt) return set_err(std::string(who) + ": a fired row names no touched group");
-    lk.lock();
-    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-    uint32_t* dfrow;
-    PinnedUploads up2;
-    up2.add(I_DFROW, hfired.data(), nf, &dfrow);
-    void *pmem, *pser, *pfg, *pdv, *ptout, *ptst, *past;
-    if (upload_pinned(d, h, up2) || ensure_buf(h.io[I_CAND], nf * t * sizeof(uint32_t), &pmem) ||
-        ensure_buf(h.io[I_CHOSEN], nf * t * sizeof(uint32_t), &pser) || ensure_buf(h.io[I_DFGRP], nf * sizeof(uint32_t), &pfg) ||
-        ensure_buf(h.io[I_DVPK], 48 * nf, &pdv) || ensure_buf(h.io[I_TAOUT], 96 * nf, &ptout) ||
-        ensure_buf(h.io[I_TAST], nf, &ptst) || ensure_buf(h.io[I_AGGST], nf, &past))
-      return -1;
-    Ws& w2 = ws_acquire(d, s);
-    TaSelectArgs sa{};
-    uint8_t *pout, *pstt, *ast;
-    HmEntry *ppt, *apt;
-    if (wsbuf(w2, W_SELCIDX, nf * t, &sa.cidx) || wsbuf(w2, W_SELKEY, nf, &sa.key) || wsbuf(w2, W_SELSTATE, nf, &sa.state) ||
-        wsbuf(w2, W_SELGMSG, nf, &sa.gmsg) || wsbuf(w2, W_SELHIST, 2 * (size_t)TASEL_KEYS, &sa.hist) ||
-        wsbuf(w2, W_SELOFF, (size_t)TASEL_KEYS + 1, &sa.off) || wsbuf(w2, W_SELPERM, nf, &sa.perm) ||
-        wsbuf(w2, W_SELPMEM, nf * t, &sa.pmem) || wsbuf(w2, W_SELPIDX, nf * t, &sa.pidx) ||
-        wsbuf(w2, W_SELPGOFF, nf + 1, &sa.pgoff) || wsbuf(w2, W_SELPOUT, 96 * nf, &pout) || wsbuf(w2, W_SELPST, nf, &pstt) ||
-        wsbuf(w2, W_SELPPT, nf, &ppt) || wsbuf(w2, W_SELAPT, nf, &apt) || wsbuf(w2, W_SELAST, nf, &ast))
-      return -1;
-    sa.cur = sa.hist + TASEL_KEYS;
-    sa.n_groups = (uint32_t)nf;
-    sa.t = du.t;
-    sa.chosen = (uint32_t*)pmem;
-    HCHK(hipMemsetAsync(sa.hist, 0, 2 * (size_t)TASEL_KEYS * sizeof(uint32_t), s));
-    DutyGatherArgs ga{};
-    ga.n_fired = (uint32_t)nf;
-    ga.n_touched = (uint32_t)nt;
-    ga.n_groups = (uint32_t)ng;
-    ga.max_stored = du.max_stored;
-    ga.t = du.t;
-    ga.group_base = (uint32_t)sh.gb;
-    ga.frow = dfrow;
-    ga.tgroup = dtgrp;
-    ga.mslot = st.mslot;
-    ga.mserial = st.mserial;
-    ga.midx = st.midx;
-    ga.fmsg = st.fmsg;
-    ga.fkey = st.fkey;
-    ga.dv_pks = sh.dvpk;
-    ga.chosen = sa.chosen;
-    ga.cidx = sa.cidx;
-    ga.key = sa.key;
-    ga.state = sa.state;
-    ga.gmsg = sa.gmsg;
-    ga.hist = sa.hist;
-    ga.serials = (uint32_t*)pser;
-    ga.fired_g = (uint32_t*)pfg;
-    ga.dv_out = (uint8_t*)pdv;
-    TIMED(d, "k_duty_gather", s, launch_duty_gather(ga, s));
-    TIMED(d, "k_ta_sel_scan", s, launch_scan(sa.hist, TASEL_KEYS, sa.off, s));
-    TIMED(d, "k_ta_sel_fill", s, launch_ta_sel_fill(sa, s));
-    const uint8_t* sdone = nullptr;
-    if (ta_tail(d, w2, sh.store, sa.pmem, sh.store_st, sa.pidx, sa.pgoff, nf, nf * t, 0, pout, pstt, ppt, s, nullptr, nullptr,
-                &sdone))
-      return -1;
-    TaScatterArgs sc{};
-    sc.n_groups = (uint32_t)nf;
-    sc.perm = sa.perm;
-    sc.state = sa.state;
-    sc.pout = pout;
-    sc.pstatus = pstt;
-    sc.ppt = ppt;
-    sc.sdone = sdone;
-    sc.ta_out = (uint8_t*)ptout;
-    sc.ta_status = (uint8_t*)ptst;
-    sc.rows16 = (((uintptr_t)ptout | (uintptr_t)pout) & 15) == 0 ? 1 : 0;
-    sc.agg_pt = apt;
-    sc.agg_st = ast;
-    sc.ctr = sh.selctr;
-    TIMED(d, "k_ta_sel_scatter", s, launch_ta_sel_scatter(sc, s));
-    VerifyCall v2;  // the aggregates under the DV keys gathered by group id; the messages' lines are resident
-    v2.pks = (const uint8_t*)pdv;
-    v2.pre_sig = apt;
-    v2.pre_sigst = ast;
-    v2.msg_idx = sa.gmsg;
-    v2.hm = sh.hm;
-    v2.n = nf;
-    v2.n_groups = nf;
-    v2.status = (uint8_t*)past;
-    v2.s = s;
-    if (verify_pipeline(d, w2, v2)) return -1;
-    TIMED(d, "k_ta_sel_verdicts", s, launch_ta_sel_verdicts((const uint8_t*)ptst, (uint32_t)nf, (uint8_t*)past, s));
-    if (ws_release(w2, s)) return -1;
-    lk.unlock();
-    t_enq2 = now_ms();
-    out.fired.resize(nf);
-    out.chosen.resize(nf * t);
-    out.ta_out.resize(96 * nf);
-    out.ta_status.resize(nf);
-    out.agg_vstatus.resize(nf);
-    HCHK(hipMemcpyAsync(out.fired.data(), pfg, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HCHK(hipMemcpyAsync(out.chosen.data(), pser, nf * t * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
-    HCHK(hipMemcpyAsync(out.ta_out.data(), ptout, 96 * nf, hipMemcpyDeviceToHost, s));
-    HCHK(hipMemcpyAsync(out.ta_status.data(), ptst, nf, hipMemcpyDeviceToHost, s));
-    HCHK(hipMemcpyAsync(out.agg_vstatus.data(), past, nf, hipMemcpyDeviceToHost, s));
-    HCHK(hipStreamSynchronize(s));
-  }
-  if (host_timing())
-    fprintf(stderr, "hbls duty_add shard groups %zu..%zu n=%zu touched=%zu new msgs=%zu fired=%zu: plan %.2f ms, "
-            "enqueue verify+store %.2f, device %.2f, enqueue aggregate+verify %.2f, device %.2f\n", sh.gb, sh.ge, m, nt,
-            nnew, nf, t_prep - t_start, t_enq1 - t_prep, t_dev1 - t_enq1, t_enq2 - t_dev1, now_ms() - t_enq2);
+  nf = hctr[DUTY_CTR_FIRED];
+  if (nf > nt) return set_err(std::string(a.who) + ": the fired list is longer than the touched groups");
   return 0;
 }
 
-// sets: null for hbls_duty_add; else the call's sets, with set_first (n_sets entries) to fill
-int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
-             const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
-             uint8_t* stored, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status,
-             uint8_t* agg_vstatus, const DutySetCall* sets = nullptr, uint32_t* set_first = nullptr) {
-  const size_t nd = du.sh.size(), t = du.t, n_sets = sets ? sets->n_sets : 0;
-  const char* const who_c = !sets ? "hbls_duty_add" : sets->first ? "hbls_duty_add_sets_first" : "hbls_duty_add_sets";
-  const std::string who = who_c;
+// The fired groups, ascending: their members are in the store.  k_duty_gather fills the candidates;
+// behind it the shared tail, as phases 3 and 4 of slot_select_core.  Needs neither lk nor a workspace
+// set; takes lk and a set of its own, hands the set back, then drops lk: leaves neither.
+int DutyShardAdd::aggregate_fired_() {
+  Hc& h = *hcs->h[0];
+  hipStream_t s = h.s;
+  std::sort(hfired.begin(), hfired.begin() + nf);
+  for (size_t k = 0; k < nf; k++)
+    if (hfired[k] >= nt) return set_err(std::string(a.who) + ": a fired row names no touched group");
+  lk.lock();
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  uint32_t* dfrow;
+  PinnedUploads up2;
+  up2.add(I_DFROW, hfired.data(), nf, &dfrow);
+  void *pmem, *pdv;
+  if (upload_pinned(d, h, up2) || ensure_buf(h.io[I_CAND], nf * t * sizeof(uint32_t), &pmem) ||
+      ensure_buf(h.io[I_CHOSEN], nf * t * sizeof(uint32_t), &pser) || ensure_buf(h.io[I_DFGRP], nf * sizeof(uint32_t), &pfg) ||
+      ensure_buf(h.io[I_DVPK], 48 * nf, &pdv) || ensure_buf(h.io[I_TAOUT], 96 * nf, &ptout) ||
+      ensure_buf(h.io[I_TAST], nf, &ptst) || ensure_buf(h.io[I_AGGST], nf, &past))
+    return -1;
+  Ws& w2 = ws_acquire(d, s);
+  SelWs x;
+  if (sel_ws(w2, nf, t, s, x)) return -1;
+  TaSelectArgs& sa = x.sa;
+  sa.chosen = (uint32_t*)pmem;
+  DutyGatherArgs ga{};
+  ga.n_fired = (uint32_t)nf;
+  ga.n_touched = (uint32_t)nt;
+  ga.n_groups = (uint32_t)ng;
+  ga.max_stored = du.max_stored;
+  ga.t = du.t;
+  ga.group_base = (uint32_t)sh.gb;
+  ga.frow = dfrow;
+  ga.tgroup = dtgrp;
+  ga.mslot = st.mslot;
+  ga.mserial = st.mserial;
+  ga.midx = st.midx;
+  ga.fmsg = st.fmsg;
+  ga.fkey = st.fkey;
+  ga.dv_pks = sh.dvpk;
+  ga.chosen = sa.chosen;
+  ga.cidx = sa.cidx;
+  ga.key = sa.key;
+  ga.state = sa.state;
+  ga.gmsg = sa.gmsg;
+  ga.hist = sa.hist;
+  ga.serials = (uint32_t*)pser;
+  ga.fired_g = (uint32_t*)pfg;
+  ga.dv_out = (uint8_t*)pdv;
+  TIMED(d, "k_duty_gather", s, launch_duty_gather(ga, s));
+  if (sel_aggregate(d, w2, x, sh.store, sh.store_st, (uint8_t*)ptout, (uint8_t*)ptst, sh.selctr, s)) return -1;
+  VerifyCall v2;  // the aggregates under the DV keys gathered by group id; the messages' lines are resident
+  v2.pks = (const uint8_t*)pdv;
+  v2.hm = sh.hm;
+  if (sel_verify(d, w2, x, v2, (const uint8_t*)ptst, (uint8_t*)past, s)) return -1;
+  if (ws_release(w2, s)) return -1;
+  lk.unlock();
+  t_enq2 = now_ms();
+  return 0;
+}
+
+// The fired groups' rows to the shard's output.  No lock, no workspace set; waits for the stream.
+int DutyShardAdd::download_fired_() {
+  hipStream_t s = hcs->h[0]->s;
+  out.fired.resize(nf);
+  out.chosen.resize(nf * t);
+  out.ta_out.resize(96 * nf);
+  out.ta_status.resize(nf);
+  out.agg_vstatus.resize(nf);
+  HCHK(hipMemcpyAsync(out.fired.data(), pfg, nf * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(out.chosen.data(), pser, nf * t * sizeof(uint32_t), hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(out.ta_out.data(), ptout, 96 * nf, hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(out.ta_status.data(), ptst, nf, hipMemcpyDeviceToHost, s));
+  HCHK(hipMemcpyAsync(out.agg_vstatus.data(), past, nf, hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  return 0;
+}
+
+// A checked, non-empty add (duty_add_entry) over the duty's shards
+int duty_add(Duty& du, const DutyAddArgs& a) {
+  const DutySetCall* const sets = a.sets;
+  const size_t n = a.n, nd = du.sh.size(), t = du.t, n_sets = sets ? sets->n_sets : 0;
+  const std::string who = a.who;
   const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
   std::vector<std::vector<uint32_t>> items;
-  duty_route(group, n, du.n_groups, nd, items);
+  duty_route(a.group, n, du.n_groups, nd, items);
   std::vector<DutyShardOut> outs(nd);
-  std::vector<DutyShardAdd> adds(nd);
-  for (size_t k = 0; k < nd; k++) {
-    DutyShardAdd& a = adds[k];
-    a.du_ = &du;
-    a.sh_ = &du.sh[k];
-    a.pks = pks;
-    a.sigs = sigs;
-    a.msgs = msgs;
-    a.msg_off = msg_off;
-    a.msg_len = msg_len;
-    a.group = group;
-    a.share_idx = share_idx;
-    a.items_ = &items[k];
-    a.first_serial = du.next_serial;
-    a.gmax = gmax;
-    a.vstatus = vstatus;
-    a.stored = stored;
-    a.out_ = &outs[k];
-    a.sets = sets;
-    a.who = who_c;
-  }
+  std::vector<DutyShardAdd> adds;
+  adds.reserve(nd);
+  for (size_t k = 0; k < nd; k++) adds.emplace_back(du, du.sh[k], a, items[k], gmax, outs[k]);
   std::vector<int> rc(nd, 0);
   std::vector<std::string> errs(nd);
   // every shard runs fn concurrently (one host thread per shard beyond one), all joined before this returns
@@ -3692,15 +3716,15 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
         return set_err(who + ": a set's first failure lies outside the set");
       }
       rejected++;
-      for (uint32_t i = b; i < e; i++) lost += vstatus[i] == HBLS_OK ? 1 : 0;
+      for (uint32_t i = b; i < e; i++) lost += a.vstatus[i] == HBLS_OK ? 1 : 0;
     }
-    if (n_sets) memcpy(set_first, merged.data(), n_sets * sizeof(uint32_t));
+    if (n_sets) memcpy(a.set_first, merged.data(), n_sets * sizeof(uint32_t));
     du.set_stats[0] += n_sets;
     du.set_stats[1] += rejected;
     du.set_stats[2] += lost;
     if (sets->first) {
       du.first_stats[0] += n;
-      for (size_t i = 0; i < n; i++) du.first_stats[1] += vstatus[i] == HBLS_UNCHECKED ? 1 : 0;
+      for (size_t i = 0; i < n; i++) du.first_stats[1] += a.vstatus[i] == HBLS_UNCHECKED ? 1 : 0;
     }
   }
   size_t nf = 0;  // the shards own ascending ranges of the groups: their lists concatenate in order
@@ -3708,11 +3732,11 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
     const DutyShardOut& o = outs[k];
     const size_t f = o.fired.size();
     if (f) {
-      memcpy(fired + nf, o.fired.data(), f * sizeof(uint32_t));
-      memcpy(chosen + nf * t, o.chosen.data(), f * t * sizeof(uint32_t));
-      memcpy(ta_out + 96 * nf, o.ta_out.data(), 96 * f);
-      memcpy(ta_status + nf, o.ta_status.data(), f);
-      memcpy(agg_vstatus + nf, o.agg_vstatus.data(), f);
+      memcpy(a.fired + nf, o.fired.data(), f * sizeof(uint32_t));
+      memcpy(a.chosen + nf * t, o.chosen.data(), f * t * sizeof(uint32_t));
+      memcpy(a.ta_out + 96 * nf, o.ta_out.data(), 96 * f);
+      memcpy(a.ta_status + nf, o.ta_status.data(), f);
+      memcpy(a.agg_vstatus + nf, o.agg_vstatus.data(), f);
       nf += f;
     }
     du.stats[1] += o.n_stored;
@@ -3723,7 +3747,7 @@ int duty_add(Duty& du, const uint8_t* pks, const uint8_t* sigs, const uint8_t* m
   du.stats[0] += n;
   du.stats[4] += nf;
   du.next_serial += (uint32_t)n;
-  *n_fired = nf;
+  *a.n_fired = nf;
   return 0;
 }
 
@@ -3737,6 +3761,19 @@ int duty_state(Duty& du, uint32_t* stored_count, uint8_t* fired_flag) {
     HCHK(hipMemcpy(stored_count + s.gb, s.count, ng * sizeof(uint32_t), hipMemcpyDeviceToHost));
     HCHK(hipMemcpy(fired_flag + s.gb, s.fired, ng, hipMemcpyDeviceToHost));
   }
+  return 0;
+}
+
+// hbls_duty_stats, hbls_duty_set_stats and hbls_duty_first_stats: the first n of one of the duty's counter arrays
+template <size_t N>
+int duty_counters(const std::string& who, uint64_t duty, uint64_t (Duty::*ctr)[N], uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Duty> du = duty_find(duty);
+  if (!du) return set_err(who + ": no such duty (never opened, or closed)");
+  if (!out || n > N) return set_err(who + ": out is null or n above " + std::to_string(N));
+  std::lock_guard<std::mutex> l(du->mu);
+  if (du->closed) return set_err(who + ": the duty is closed");
+  for (size_t k = 0; k < n; k++) out[k] = ((*du).*ctr)[k];
   return 0;
 }
 
@@ -4451,71 +4488,51 @@ int hbls_duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, u
   return duty_open(dv_pks, n_groups, threshold, max_stored, duty);
 }
 
-int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
-                  const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
-                  uint8_t* stored, uint32_t* first_serial, uint32_t* fired, size_t* n_fired, uint32_t* chosen,
-                  uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_add: no such duty (never opened, or closed)");
-  std::lock_guard<std::mutex> l(du->mu);
-  if (du->closed) return set_err("hbls_duty_add: the duty is closed");
-  if (du->broken) return set_err("hbls_duty_add: an earlier add failed on a device; close the duty");
-  if (!first_serial || !n_fired) return set_err("hbls_duty_add: first_serial and n_fired are required");
-  if (n >= 0xffffffffull - du->next_serial) return set_err("hbls_duty_add: the duty would reach 2^32 - 1 partials");
-  if (n && (!pks || !sigs || !msg_off || !msg_len || !group || !share_idx || !vstatus || !stored))
-    return set_err("hbls_duty_add: pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
-  if (!msgs)
-    for (size_t i = 0; i < n; i++)
-      if (msg_len[i]) return set_err("hbls_duty_add: msgs is required");
-  if (std::min(n, du->n_groups) && (!fired || !chosen || !ta_out || !ta_status || !agg_vstatus))
-    return set_err("hbls_duty_add: fired, chosen, ta_out, ta_status and agg_vstatus are required");
-  *first_serial = du->next_serial;
-  *n_fired = 0;
-  if (!n) return 0;
-  return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
-                  ta_out, ta_status, agg_vstatus);
-}
-
-// hbls_duty_add_sets and hbls_duty_add_sets_first: one argument check, one call
-static int duty_add_sets_entry(bool first, uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
-                               const uint64_t* msg_off, const uint32_t* msg_len, const uint32_t* group,
-                               const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets, uint8_t* vstatus,
-                               uint8_t* stored, uint32_t* first_serial, uint32_t* set_first, uint32_t* fired, size_t* n_fired,
-                               uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
-  const std::string who = first ? "hbls_duty_add_sets_first" : "hbls_duty_add_sets";
+// hbls_duty_add, hbls_duty_add_sets and hbls_duty_add_sets_first: one argument check, in the order the
+// first failing one is reported in, one call.  sets: null for hbls_duty_add (its set ids are filled here)
+static int duty_add_entry(uint64_t duty, DutyAddArgs a, DutySetCall* sets) {
+  const std::string who = a.who;
+  const size_t n = a.n;
   if (ensure_init()) return -1;
   std::shared_ptr<Duty> du = duty_find(duty);
   if (!du) return set_err(who + ": no such duty (never opened, or closed)");
   std::lock_guard<std::mutex> l(du->mu);
   if (du->closed) return set_err(who + ": the duty is closed");
   if (du->broken) return set_err(who + ": an earlier add failed on a device; close the duty");
-  if (!first_serial || !n_fired) return set_err(who + ": first_serial and n_fired are required");
+  if (!a.first_serial || !a.n_fired) return set_err(who + ": first_serial and n_fired are required");
   if (n >= 0xffffffffull - du->next_serial) return set_err(who + ": the duty would reach 2^32 - 1 partials");
-  if (n_sets >= 0xffffffffull) return set_err(who + ": too many sets");
-  if (n_sets && !set_first) return set_err(who + ": set_first is required");
-  if (const char* bad = duty_check_sets(set_off, n_sets, n)) return set_err(who + ": " + bad);
-  if (n && (!pks || !sigs || !msg_off || !msg_len || !group || !share_idx || !vstatus || !stored))
+  if (sets) {
+    if (sets->n_sets >= 0xffffffffull) return set_err(who + ": too many sets");
+    if (sets->n_sets && !a.set_first) return set_err(who + ": set_first is required");
+    if (const char* bad = duty_check_sets(sets->set_off, sets->n_sets, n)) return set_err(who + ": " + bad);
+  }
+  if (n && (!a.pks || !a.sigs || !a.msg_off || !a.msg_len || !a.group || !a.share_idx || !a.vstatus || !a.stored))
     return set_err(who + ": pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
-  if (!msgs)
+  if (!a.msgs)
     for (size_t i = 0; i < n; i++)
-      if (msg_len[i]) return set_err(who + ": msgs is required");
-  if (std::min(n, du->n_groups) && (!fired || !chosen || !ta_out || !ta_status || !agg_vstatus))
+      if (a.msg_len[i]) return set_err(who + ": msgs is required");
+  if (std::min(n, du->n_groups) && (!a.fired || !a.chosen || !a.ta_out || !a.ta_status || !a.agg_vstatus))
     return set_err(who + ": fired, chosen, ta_out, ta_status and agg_vstatus are required");
-  *first_serial = du->next_serial;
-  *n_fired = 0;
-  if (!n) {  // empty sets only: seen, none rejected
-    for (size_t k = 0; k < n_sets; k++) set_first[k] = DUTY_NONE;
-    du->set_stats[0] += n_sets;
+  *a.first_serial = du->next_serial;
+  *a.n_fired = 0;
+  if (!n) {
+    if (sets) {  // empty sets only: seen, none rejected
+      for (size_t k = 0; k < sets->n_sets; k++) a.set_first[k] = DUTY_NONE;
+      du->set_stats[0] += sets->n_sets;
+    }
     return 0;
   }
-  DutySetCall sc;
-  sc.set_off = set_off;
-  sc.n_sets = n_sets;
-  sc.first = first;
-  duty_set_ids(set_off, n_sets, n, sc.set_of);
-  return duty_add(*du, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, fired, n_fired, chosen,
-                  ta_out, ta_status, agg_vstatus, &sc, set_first);
+  if (sets) duty_set_ids(sets->set_off, sets->n_sets, n, sets->set_of);
+  a.sets = sets;
+  return duty_add(*du, a);
+}
+
+int hbls_duty_add(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
+                  const uint32_t* msg_len, const uint32_t* group, const int64_t* share_idx, size_t n, uint8_t* vstatus,
+                  uint8_t* stored, uint32_t* first_serial, uint32_t* fired, size_t* n_fired, uint32_t* chosen,
+                  uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
+  return duty_add_entry(duty, {pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, first_serial, fired,
+                               n_fired, chosen, ta_out, ta_status, agg_vstatus, "hbls_duty_add"}, nullptr);
 }
 
 int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs, const uint64_t* msg_off,
@@ -4523,8 +4540,9 @@ int hbls_duty_add_sets(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, c
                        const uint32_t* set_off, size_t n_sets, uint8_t* vstatus, uint8_t* stored, uint32_t* first_serial,
                        uint32_t* set_first, uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
                        uint8_t* ta_status, uint8_t* agg_vstatus) {
-  return duty_add_sets_entry(false, duty, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, set_off, n_sets, vstatus,
-                             stored, first_serial, set_first, fired, n_fired, chosen, ta_out, ta_status, agg_vstatus);
+  DutySetCall sc{set_off, n_sets, {}, false};
+  return duty_add_entry(duty, {pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, first_serial, fired,
+                               n_fired, chosen, ta_out, ta_status, agg_vstatus, "hbls_duty_add_sets", nullptr, set_first}, &sc);
 }
 
 int hbls_duty_add_sets_first(uint64_t duty, const uint8_t* pks, const uint8_t* sigs, const uint8_t* msgs,
@@ -4532,30 +4550,17 @@ int hbls_duty_add_sets_first(uint64_t duty, const uint8_t* pks, const uint8_t* s
                              const int64_t* share_idx, size_t n, const uint32_t* set_off, size_t n_sets, uint8_t* vstatus,
                              uint8_t* stored, uint32_t* first_serial, uint32_t* set_first, uint32_t* fired, size_t* n_fired,
                              uint32_t* chosen, uint8_t* ta_out, uint8_t* ta_status, uint8_t* agg_vstatus) {
-  return duty_add_sets_entry(true, duty, pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, set_off, n_sets, vstatus,
-                             stored, first_serial, set_first, fired, n_fired, chosen, ta_out, ta_status, agg_vstatus);
+  DutySetCall sc{set_off, n_sets, {}, true};
+  return duty_add_entry(duty, {pks, sigs, msgs, msg_off, msg_len, group, share_idx, n, vstatus, stored, first_serial, fired,
+                               n_fired, chosen, ta_out, ta_status, agg_vstatus, "hbls_duty_add_sets_first", nullptr, set_first}, &sc);
 }
 
 int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_first_stats: no such duty (never opened, or closed)");
-  if (!out || n > 2) return set_err("hbls_duty_first_stats: out is null or n above 2");
-  std::lock_guard<std::mutex> l(du->mu);
-  if (du->closed) return set_err("hbls_duty_first_stats: the duty is closed");
-  for (size_t k = 0; k < n; k++) out[k] = du->first_stats[k];
-  return 0;
+  return duty_counters("hbls_duty_first_stats", duty, &Duty::first_stats, out, n);
 }
 
 int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_set_stats: no such duty (never opened, or closed)");
-  if (!out || n > 3) return set_err("hbls_duty_set_stats: out is null or n above 3");
-  std::lock_guard<std::mutex> l(du->mu);
-  if (du->closed) return set_err("hbls_duty_set_stats: the duty is closed");
-  for (size_t k = 0; k < n; k++) out[k] = du->set_stats[k];
-  return 0;
+  return duty_counters("hbls_duty_set_stats", duty, &Duty::set_stats, out, n);
 }
 
 int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag) {
@@ -4569,14 +4574,7 @@ int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag) 
 }
 
 int hbls_duty_stats(uint64_t duty, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_stats: no such duty (never opened, or closed)");
-  if (!out || n > 6) return set_err("hbls_duty_stats: out is null or n above 6");
-  std::lock_guard<std::mutex> l(du->mu);
-  if (du->closed) return set_err("hbls_duty_stats: the duty is closed");
-  for (size_t k = 0; k < n; k++) out[k] = du->stats[k];
-  return 0;
+  return duty_counters("hbls_duty_stats", duty, &Duty::stats, out, n);
 }
 
 int hbls_duty_close(uint64_t duty) {

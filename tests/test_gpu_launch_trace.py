@@ -10,7 +10,8 @@ was split into a plan and phases (the first-error and per-device-shard host trac
 before the host paths' grouping moved into hgroup.h; both recorded in two separate processes, which
 agreed); a change that is not meant to alter the sequence must reproduce it exactly, name by name.
 The cases and their inputs are the generator's own (CASES).  The large call's traces of the same
-file (traces_large) are checked by tests/test_gpu_robustness.py, on its fixture.
+file (traces_large) are checked by tests/test_gpu_robustness.py, on its fixture.  The slot select calls
+and the duty adds have a fixture of their own: tests/golden/select_traces.json (tests/test_gpu_select_trace.py).
 """
 import json
 import os
