@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "lib", "libhipbls.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["hipbls.hip", "pipeline.hip", "threshold.hip", "vbatch.hip", "vgroup.hip", "roots.hip", "hash.hip", "msm.hip",
-           "hashsplit.hip", "duty.hip", "dutyfirst.hip"]
+           "hashsplit.hip", "duty.hip", "dutyfirst.hip", "cluster.hip"]
 
 
 def build_id(defines=()) -> str:
@@ -759,6 +759,91 @@ def build_dutyfirstdev(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+CLUSTERCHECK_PREFIX = "hbls-clustercheck:"
+CLUSTERCHECK_HEADERS = ("cluster.h",)
+
+
+def clustercheck_build_id(root: str = "") -> str:
+    """The id embedded in the cluster handles' harness (tests/native/clustercheck.cpp,
+    `cc_build_id()`): sha256 over its source, the header it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "clustercheck.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in CLUSTERCHECK_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return CLUSTERCHECK_PREFIX + h.hexdigest()[:16]
+
+
+def build_clustercheck(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_clustercheck.so (tests/test_cluster_host.py): the key rule of a cluster
+    handle (cluster.h cluster_key) on the CPU; test-only.  Reused when its embedded id equals the
+    tree's, as build_dutysetcheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "clustercheck.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_clustercheck.so")
+    bid = clustercheck_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-clustercheck:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DCC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
+CLUSTERDEV_PREFIX = "hbls-clusterdev:"
+
+
+def clusterdev_build_id(root: str = "") -> str:
+    """The id embedded in the cluster handles' device harness (tests/native/clusterdev.hip,
+    tests/test_gpu_cluster_kernels.py; `cd_build_id()`): sha256 over its source, the device
+    harnesses' shared devblocks.h, the product source it compiles (cluster.hip), every header of
+    charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "clusterdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "cluster.hip")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return CLUSTERDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_clusterdev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_clusterdev.so: k_cluster_keys and k_cluster_wide on the device over
+    explicit words, a harness of its own like build_dutysetdev; test-only.  Reused when its embedded
+    id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "clusterdev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_clusterdev.so")
+    bid = clusterdev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-clusterdev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DCD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -822,7 +907,8 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     block harness): a failure to build one is printed and returned, never raised."""
     failed = []
     for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
-               build_subgdev, build_dutysetcheck, build_dutysetdev, build_dutyfirstcheck, build_dutyfirstdev):
+               build_subgdev, build_dutysetcheck, build_dutysetdev, build_dutyfirstcheck, build_dutyfirstdev,
+               build_clustercheck, build_clusterdev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

@@ -321,6 +321,70 @@ def sigagg_slot_host(impl_or_L, threshold: int, dv_pubkeys: Mapping[bytes, bytes
     return statuses, {pk: bytes(out[k]) for k, pk in enumerate(keys)}, used
 
 
+class Cluster:
+    """The cluster lock as an object of the library (hbls_cluster_open): every validator's DV key and
+    its pubshares of share indices 1 .. n, decompressed, subgroup-checked and (ladder_tables) given
+    ladder tables once, resident on the device for as long as the handle -- or a duty opened on it --
+    lives.  dv_pubkeys: {validator pubkey: DV key bytes} in cluster order; pubshares_by_key: {validator
+    pubkey: {share index: pubshare}} with the same indices 1 .. n for every validator.  A context
+    manager; ParSigDuty(..., cluster=this) opens duties that pass no keys.  `key_status`: per validator
+    the statuses of its 1 + n keys (DV key first) -- a bad key does not fail the open, every partial
+    that names it gets BAD_PUBKEY."""
+
+    def __init__(self, impl, dv_pubkeys: Mapping[bytes, bytes], pubshares_by_key: Mapping[bytes, Mapping[int, bytes]],
+                 ladder_tables: bool = True):
+        import ctypes
+
+        self.keys = list(dv_pubkeys)
+        self.dv_pubkeys, self.pubshares_by_key = dv_pubkeys, pubshares_by_key
+        self.n_validators = len(self.keys)
+        self.n_shares = max((max(pubshares_by_key[pk]) for pk in self.keys), default=1)
+        for pk in self.keys:
+            if sorted(pubshares_by_key[pk]) != list(range(1, self.n_shares + 1)):
+                raise TblsError("cluster: every validator needs the pubshares of share indices 1 .. n")
+        dv = b"".join(bytes(dv_pubkeys[pk]) for pk in self.keys)
+        sh = b"".join(bytes(pubshares_by_key[pk][j]) for pk in self.keys for j in range(1, self.n_shares + 1))
+        if len(dv) != 48 * self.n_validators or len(sh) != 48 * self.n_validators * self.n_shares:
+            raise TblsError("cluster: " + _LEN_ERR)
+        self._L = impl._L
+        row = 1 + self.n_shares
+        st = ctypes.create_string_buffer(max(self.n_validators * row, 1))
+        h = ctypes.c_uint64(0)
+        if self._L.hbls_cluster_open(ctypes.create_string_buffer(dv, max(len(dv), 1)),
+                                     ctypes.create_string_buffer(sh, max(len(sh), 1)), self.n_validators, self.n_shares,
+                                     1 if ladder_tables else 0, st, ctypes.byref(h)) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        self._h: Optional[int] = h.value
+        self.key_status = [list(st.raw[g * row:(g + 1) * row]) for g in range(self.n_validators)]
+
+    def __enter__(self) -> "Cluster":
+        return self
+
+    def __exit__(self, *exc) -> None:
+        self.close()
+
+    def handle(self) -> int:
+        if self._h is None:
+            raise TblsError("the cluster is closed")
+        return self._h
+
+    def stats(self) -> Dict[str, int]:
+        import ctypes
+
+        out = (ctypes.c_uint64 * 6)()
+        if self._L.hbls_cluster_stats(self.handle(), out, 6) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return dict(zip(("keys", "bad_keys", "ladder_tables", "partials_resolved", "partials_no_key", "dv_keys_resolved"),
+                        (int(x) for x in out)))
+
+    def close(self) -> None:
+        """Invalidates the handle; the device memory goes with the last duty opened on the cluster."""
+        if self._h is not None:
+            h, self._h = self._h, None
+            if self._L.hbls_cluster_close(h) != 0:
+                raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+
+
 class ParSigDuty:
     """ParSigEx.handle -> MemDB.StoreExternal -> Aggregator.Aggregate for ONE duty under the
     reference's arrival pattern (parsigex.go:93-98, parsigdb/memory.go:80-123 and 197-225,
@@ -343,17 +407,34 @@ class ParSigDuty:
     first_error: the calls that go through sets (reject_sets=True, store_external_many) stop a rejected
     set's verification at its first failing entry, as parsigex.go:93-98 does (hbls_duty_add_sets_first):
     the same results and errors -- the error of a rejected set is that of its first failing entry,
-    whose status is exact -- at a cost that does not grow with the number of bad entries."""
+    whose status is exact -- at a cost that does not grow with the number of bad entries.
+    cluster: an open Cluster -- the duty is opened on it (hbls_duty_open_cluster) and passes no keys: the
+    device resolves each partial's key from (validator, share index) and verifies the aggregates under
+    the cluster's DV keys.  dv_pubkeys and pubshares_by_key may then be None (the cluster's are used for
+    the pre-checks, which stay the shim's own and keep their two error strings).
+    The ONE place where a cluster duty still passes keys: a set with a failing pre-check.  The reference's
+    loop verifies the entries in front of that entry before it returns the pre-check's error, so a
+    failing signature among them wins.  A plain duty sends them as partials of no group ("verify only");
+    a cluster duty has no such partial (a group of no validator names no key), so they go through one
+    impl.verify_batch under the pubshares the pre-checks found (_verify_only), beside the duty, and
+    store_external_many sends that set in empty.  Nothing of it is stored either way."""
 
-    def __init__(self, impl, threshold: int, dv_pubkeys: Mapping[bytes, bytes],
-                 pubshares_by_key: Mapping[bytes, Mapping[int, bytes]], max_stored: int = 16, reject_sets: bool = False,
-                 first_error: bool = False):
+    def __init__(self, impl, threshold: int, dv_pubkeys: Optional[Mapping[bytes, bytes]] = None,
+                 pubshares_by_key: Optional[Mapping[bytes, Mapping[int, bytes]]] = None, max_stored: int = 16,
+                 reject_sets: bool = False, first_error: bool = False, cluster: Optional["Cluster"] = None):
         self._reject_sets = reject_sets
         self._first_error = first_error
+        self._cluster = cluster
+        self._impl = impl
+        if cluster is not None:
+            dv_pubkeys, pubshares_by_key = cluster.dv_pubkeys, cluster.pubshares_by_key
         self._keys = list(dv_pubkeys)
         self._group = {pk: g for g, pk in enumerate(self._keys)}
         self._shares = pubshares_by_key
-        self._duty = impl.duty_open([dv_pubkeys[pk] for pk in self._keys], threshold, max_stored)
+        if cluster is not None:
+            self._duty = impl.duty_open((), threshold, max_stored, cluster=cluster)
+        else:
+            self._duty = impl.duty_open([dv_pubkeys[pk] for pk in self._keys], threshold, max_stored)
 
     def __enter__(self) -> "ParSigDuty":
         return self
@@ -377,9 +458,16 @@ class ParSigDuty:
         sets behind it, which are stored and fire.  An error of the aggregation stage carries the set's
         other aggregates as `fired`; a rejected set's error carries an empty one."""
         pks, msgs, sigs, groups, idx, set_off, pres = [], [], [], [], [], [0], []
-        for signed_set in sets:
+        only: Dict[int, Optional[int]] = {}  # a cluster duty: sets verified beside the call -> first failing status
+        for j, signed_set in enumerate(sets):
             p, m, s, g, x, pre = self._checked(signed_set)
-            if pre is not None:  # the entries before the failing one are verified only
+            if pre is not None and self._cluster is not None:
+                # a cluster duty has no "verify only" group (a group of no validator names no key): the
+                # entries before the failing one are verified beside the call, and the set goes in empty
+                bad = [st for st in self._verify_only(p, m, s, x).vstatus if st != OK] if p else []
+                only[j] = bad[0] if bad else None
+                p, m, s, g, x = [], [], [], [], []
+            elif pre is not None:  # the entries before the failing one are verified only
                 g = [0xFFFFFFFF] * len(p)
             pks += p
             msgs += m
@@ -389,12 +477,14 @@ class ParSigDuty:
             set_off.append(len(pks))
             pres.append(pre)
         add = self._duty.add_sets_first if self._first_error else self._duty.add_sets
-        r = add(pks, msgs, sigs, groups, idx, set_off)
+        r = add(None if self._cluster is not None else pks, msgs, sigs, groups, idx, set_off)
         res: List[object] = []
         for j, pre in enumerate(pres):
             b, e = set_off[j], set_off[j + 1]
-            if r.set_first[j] is not None:  # the verification loop runs first in the reference: its error wins
-                err = _wrap("invalid partial signature", "invalid signature: " + _verr(r.vstatus[r.set_first[j]]))
+            if r.set_first[j] is not None or only.get(j) is not None:
+                # the verification loop runs first in the reference: its error wins
+                st = only[j] if only.get(j) is not None else r.vstatus[r.set_first[j]]
+                err = _wrap("invalid partial signature", "invalid signature: " + _verr(st))
                 err.fired = {}
                 res.append(err)
                 continue
@@ -421,6 +511,15 @@ class ParSigDuty:
             else:
                 res.append(out)
         return res
+
+    def _verify_only(self, pks, msgs, sigs, idx):
+        """The entries in front of a set's failing pre-check, verified and not stored: partials of no
+        group on a plain duty; on a cluster duty, where a group of no validator names no key, one
+        Verify batch under the pubshares the pre-checks found.  `.vstatus` either way."""
+        if self._cluster is None:
+            return self._duty.add(pks, msgs, sigs, [0xFFFFFFFF] * len(pks), idx)
+        from types import SimpleNamespace
+        return SimpleNamespace(vstatus=list(self._impl.verify_batch(pks, msgs, sigs)))
 
     def _checked(self, signed_set: Mapping[bytes, ParSig]):
         """The pre-checks of a set in set order, up to the first failing one: the entries that passed
@@ -475,7 +574,7 @@ class ParSigDuty:
             # nothing of a set with a failing entry is stored (parsigex.go:93-98 returns before StoreExternal):
             # the entries before it are verified only, for the error the reference's loop returns first
             if pks:
-                r = self._duty.add(pks, msgs, sigs, [0xFFFFFFFF] * len(pks), idx)
+                r = self._verify_only(pks, msgs, sigs, idx)
                 for st in r.vstatus:
                     if st != OK:
                         raise _wrap("invalid partial signature", "invalid signature: " + _verr(st))
@@ -488,7 +587,7 @@ class ParSigDuty:
         # The error then carries, as `fired`, the aggregates of the validators those entries brought to the
         # threshold: they fire once, so the caller must not lose them.  (reject_sets=True closes this
         # divergence: there the set is one set of hbls_duty_add_sets and is stored whole or not at all.)
-        r = self._duty.add(pks, msgs, sigs, groups, idx)
+        r = self._duty.add(None if self._cluster is not None else pks, msgs, sigs, groups, idx)
         out: Dict[bytes, bytes] = {}
         err: Optional[CallerError] = None
         for k, g in enumerate(r.fired):

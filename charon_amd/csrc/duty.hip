@@ -8,7 +8,7 @@
 //                 decompressed points from the verification's workspace into the duty's store
 //   k_duty_gather 1 lane / fired group, in ascending group order (the host sorted the list): its
 //                 members, share indices, class key and message into the tables threshold.hip's
-//                 k_ta_sel_fill reads, its members' serials and its DV key
+//                 k_ta_sel_fill reads, its members' serials and its DV key (none for a duty on a cluster)
 // hbls_duty_add_sets puts two kernels between the verification and k_duty_store:
 //   k_duty_set_first 1 lane / item: a lane whose verification failed folds its arrival index into its
 //                 set's entry of set_first with atomicMin; the failing lanes of a wave that share a
@@ -138,6 +138,7 @@ __global__ __launch_bounds__(64) void k_duty_gather(DutyGatherArgs a) {
   a.gmsg[k] = a.fmsg[u];
   atomicAdd(a.hist + key, 1u);
   a.fired_g[k] = a.group_base + g;
+  if (!a.dv_pks) return;  // a cluster duty: the DV keys come from the cluster by fired_g
   const uint4* in = reinterpret_cast<const uint4*>(a.dv_pks) + 3ull * g;
   uint4* o = reinterpret_cast<uint4*>(a.dv_out) + 3ull * k;
   HB_UNROLL for (int w = 0; w < 3; w++) o[w] = in[w];

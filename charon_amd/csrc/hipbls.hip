@@ -9,6 +9,7 @@
 // p2p/receive.go:52) and the RCCL exchange of slot results between processes.
 #include "layout.h"
 #include "../../include/hipbls.h"
+#include "cluster.h"
 #include "coalesce.h"
 #include "dutysel.h"
 #include "hduty.h"
@@ -373,6 +374,7 @@ enum IoId {
   // k_duty_store reads, and (several shards) the decompressed signatures kept from phase one for phase two
   I_DSETID, I_DARR, I_DSETFIRST, I_DADMIT, I_DVSIG,
   I_DGSEG,  // hbls_duty_add_sets_first: the verification groups' set ids
+  I_DCGRP, I_DCSHARE,  // a cluster duty's add: the items' groups and share indices (k_cluster_keys)
   I_COUNT
 };
 
@@ -1090,6 +1092,12 @@ struct VerifyCall {
   // hbls_slot_select_device's aggregates, sums of partials it decompressed and subgroup-checked
   const HmEntry* pre_sig = nullptr;
   const uint8_t* pre_sigst = nullptr;
+  // keys by cluster (a cluster duty's adds and its fired groups' aggregates; pks is then unused): the
+  // shard's resident keys and each item's group and share index (null: the groups' DV keys), resolved by
+  // k_cluster_keys where the lookup runs otherwise.  The out fields are the pipeline's.  Such a call
+  // neither reads nor writes the learned key cache and is outside the chain of Dev::kl_ev.
+  const ClusterKeysArgs* cluster = nullptr;
+  const G1WidePt* cluster_wide = nullptr;  // the cluster's ladder tables (null: none)
   // handed back: the decompressed signatures and their statuses (the host calls' signature-cache put)
   HmEntry* vsig = nullptr;
   uint8_t* vsigst = nullptr;
@@ -1270,8 +1278,8 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
   // (the lookup loads a key as three 16-byte words: a caller's array that is not 16-byte aligned
   // takes the plain decompression)
   const auto al16 = [](const void* q) { return ((uintptr_t)q & 15) == 0; };
-  const bool learn_pk = !c.key_cache && !(fold && fold->pk_table) && n && al16(c.pks);
-  const bool learn_dv = !c.key_cache && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
+  const bool learn_pk = !c.cluster && !c.key_cache && !(fold && fold->pk_table) && n && al16(c.pks);
+  const bool learn_dv = !c.cluster && !c.key_cache && n_agg && !fold->dv_pk_table && al16(fold->dv_pks);
   KeyLearnTab kl{};
   uint32_t *kmiss = nullptr, *kcnt = nullptr;  // taken here: whether there is a table is only known now
   uint32_t *kent = nullptr, *kment = nullptr;
@@ -1288,7 +1296,21 @@ int verify_decompress(Dev& d, Ws& w, const VerifyCall& c, const VerifyPlan& p, V
       b.kw.wide = b.akw.wide = kl.wide;
     }
   }
-  if (fold && fold->pk_table) {
+  if (c.cluster) {  // the cluster's own keys by (group, share index): no lookup, no miss, nothing learned
+    ClusterKeysArgs ck = *c.cluster;
+    ck.n = (uint32_t)n;
+    ck.vpk = b.vpk;
+    ck.vpkst = b.vpkst;
+    ck.went = nullptr;
+    ck.tables = c.cluster_wide ? 1u : 0u;
+    if (c.cluster_wide) {
+      if (wsbuf(w, W_KLENT, n, &kent)) return -1;
+      ck.went = kent;
+      b.kw.ent = kent;
+      b.kw.wide = c.cluster_wide;  // (b.kw.ctr stays null: the counters are the learned cache's)
+    }
+    TIMED(d, "k_cluster_keys", w.side[0], launch_cluster_keys(ck, w.side[0]));
+  } else if (fold && fold->pk_table) {
     b.vpk = const_cast<G1AEntry*>(fold->pk_table);
     b.vpkst = const_cast<uint8_t*>(fold->pk_table_st);
   } else if (c.key_cache && d.kc_n) {  // host-buffer call with the key cache: cached entries, the rest decompressed
@@ -3123,9 +3145,48 @@ int slot_select_host(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msg
 // messages with their lines, and per group max_stored slots of decompressed partials with their
 // share indices, message ids and serials, the count and the fired flag.
 // ---------------------------------------------------------------------------------------
+// Cluster handles (hbls_cluster_open / _close / _stats, hbls_duty_open_cluster; cluster.h is the rule,
+// cluster.hip the kernels): the keys of a cluster lock -- per validator its DV key and its n_shares
+// pubshares -- decompressed, subgroup-checked and (ladder_tables) given ladder tables once, resident per
+// shard (the duty's rule: contiguous ranges of the validators over the devices as they were at open).
+struct ClusterShard {
+  Dev* d = nullptr;
+  size_t gb = 0, ge = 0;
+  G1AEntry* ent = nullptr;  // (ge - gb) (1 + n_shares) entries, row-major: cluster.h's key numbers
+  uint8_t* st = nullptr;    // their statuses, as hbls_decompress_pubkeys_device reports them
+  G1WidePt* wide = nullptr;  // ladder_tables: 15 points per key (written for the good, finite keys only)
+  size_t n_keys = 0;
+};
+// INVARIANT: a cluster is immutable once hbls_cluster_open has returned.  Open writes the shards' buffers
+// on the library stream of each device and synchronises before the handle exists; after that every
+// kernel of every duty and call only reads them, so any number read them concurrently on any stream
+// with no lock and no event.  Nothing frees them while a reader can exist: the memory goes with the
+// last shared_ptr -- g_clusters' (hbls_cluster_close) or that of a duty opened on the cluster
+// (hbls_duty_close, behind the duty's last call).  The counters are the only thing that changes.
+struct Cluster {
+  size_t n_validators = 0;
+  uint32_t n_shares = 0;
+  bool tables = false;
+  std::vector<ClusterShard> sh;
+  std::atomic<uint64_t> stats[6] = {};  // hbls_cluster_stats
+  ~Cluster() {
+    for (ClusterShard& s : sh) {
+      if (!s.d) continue;
+      std::lock_guard<std::mutex> lk(s.d->mu);
+      if (hipSetDevice(s.d->ord) != hipSuccess) continue;
+      for (void* p : {(void*)s.ent, (void*)s.st, (void*)s.wide})
+        if (p) (void)hipFree(p);
+    }
+  }
+};
+std::mutex g_cluster_mu;
+std::unordered_map<uint64_t, std::shared_ptr<Cluster>> g_clusters;
+uint64_t g_cluster_next = 1;
+
 struct DutyShard {
   Dev* d = nullptr;
   size_t gb = 0, ge = 0;
+  const ClusterShard* cs = nullptr;  // a cluster duty: the shard's keys (Duty::cl keeps them alive)
   DutyMsgTable tab;   // the shard's messages (host); ids index hm
   size_t hashed = 0;  // messages resident in hm (a failed add may leave the table ahead of it)
   MsgEntry* hm = nullptr;
@@ -3147,8 +3208,14 @@ struct DutyShard {
 // as k_duty_store checks a touched group against the shard's groups.  hbls_duty_add_sets_first hands the
 // verification the groups' and items' set ids as well (VerifyCall::gseg / item_seg): dutyfirst.hip's kernels
 // check each against n_seg in the same way.
+// INVARIANT (cluster duties): a group or a share index of the caller's never becomes an address into
+// the cluster's keys except through cluster.h cluster_key -- in k_cluster_keys for every partial and
+// for every fired group's DV key, and on the host where hbls_cluster_stats is counted -- which compares
+// the full 64-bit share index and the group against the shard's own range; k_cluster_keys checks the
+// key's number against the shard's key count once more.
 struct Duty {
   std::mutex mu;
+  std::shared_ptr<Cluster> cl;  // a cluster duty (hbls_duty_open_cluster): its keys; the shards are the cluster's
   bool closed = false, broken = false;
   size_t n_groups = 0;
   uint32_t t = 0, max_stored = 0, next_serial = 0;
@@ -3189,33 +3256,40 @@ int duty_alloc_shard(DutyShard& s, const uint8_t* dv_pks, uint32_t max_stored) {
   HCHK(hipMalloc((void**)&s.rec_serial, slots * sizeof(uint32_t)));
   HCHK(hipMalloc((void**)&s.count, g1 * sizeof(uint32_t)));
   HCHK(hipMalloc((void**)&s.fired, g1));
-  HCHK(hipMalloc((void**)&s.dvpk, 48 * g1));
+  if (dv_pks || !ng) HCHK(hipMalloc((void**)&s.dvpk, 48 * g1));  // (a cluster duty keeps none: the DV keys are the cluster's)
   HCHK(hipMalloc((void**)&s.selctr, SEL_COUNTERS * sizeof(uint64_t)));
   HCHK(hipMemset(s.store_st, 0, slots));
   HCHK(hipMemset(s.count, 0, g1 * sizeof(uint32_t)));
   HCHK(hipMemset(s.fired, 0, g1));
   HCHK(hipMemset(s.selctr, 0, SEL_COUNTERS * sizeof(uint64_t)));
-  if (ng) HCHK(hipMemcpy(s.dvpk, dv_pks + 48 * s.gb, 48 * ng, hipMemcpyHostToDevice));
+  if (ng && dv_pks) HCHK(hipMemcpy(s.dvpk, dv_pks + 48 * s.gb, 48 * ng, hipMemcpyHostToDevice));
   HCHK(hipStreamSynchronize(nullptr));  // complete before any stream's kernel reads them
   return 0;
 }
 
-int duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored, uint64_t* handle) {
+// cl (nullable): a cluster duty -- no dv_pks, and the cluster's shards (devices and ranges as they were
+// when it was opened) in place of devs() as it is now
+int duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored, uint64_t* handle,
+              const std::shared_ptr<Cluster>& cl = nullptr) {
+  const std::string who = cl ? "hbls_duty_open_cluster" : "hbls_duty_open";
   auto du = std::make_shared<Duty>();
   du->n_groups = n_groups;
   du->t = threshold;
   du->max_stored = max_stored;
-  const std::vector<Dev*> ds = devs();
-  const size_t nd = slot_shards(ds.size(), n_groups);
+  du->cl = cl;
+  const std::vector<Dev*> ds = cl ? std::vector<Dev*>() : devs();
+  const size_t nd = cl ? cl->sh.size() : slot_shards(ds.size(), n_groups);
   du->sh.resize(nd);
   for (size_t k = 0; k < nd; k++) {
-    du->sh[k].d = ds[k];
-    du->sh[k].gb = n_groups * k / nd;
-    du->sh[k].ge = n_groups * (k + 1) / nd;
+    du->sh[k].d = cl ? cl->sh[k].d : ds[k];
+    du->sh[k].gb = cl ? cl->sh[k].gb : n_groups * k / nd;
+    du->sh[k].ge = cl ? cl->sh[k].ge : n_groups * (k + 1) / nd;
+    du->sh[k].cs = cl ? &cl->sh[k] : nullptr;
+    const int ord = du->sh[k].d->ord;
     if (duty_alloc_shard(du->sh[k], dv_pks, max_stored)) {
       const std::string err = g_err;
       for (size_t j = 0; j <= k; j++) duty_free_shard(du->sh[j]);  // nothing is left behind
-      return set_err("hbls_duty_open: device " + std::to_string(ds[k]->ord) + ": " + err);
+      return set_err(who + ": device " + std::to_string(ord) + ": " + err);
     }
   }
   std::lock_guard<std::mutex> l(g_duty_mu);
@@ -3229,6 +3303,7 @@ struct DutyShardOut {
   std::vector<uint32_t> fired, chosen;
   std::vector<uint8_t> ta_out, ta_status, agg_vstatus;
   uint64_t n_stored = 0, n_full = 0, n_new_msgs = 0, resident = 0;
+  uint64_t n_named = 0, n_nokey = 0, n_dv = 0;  // a cluster duty: hbls_cluster_stats [3], [4], [5] of this add
 };
 
 // hbls_duty_add_sets: the call's sets (hduty.h), every caller index's set id
@@ -3325,6 +3400,17 @@ struct DutyShardAdd {
   Ws* w = nullptr;  // the verification's workspace set, until it is handed back
   std::vector<uint32_t> set_first;  // the sets' first failures as this shard saw them (one shard: the call's)
 
+  // a cluster duty: the shard's keys for k_cluster_keys over items named by group (share: null, their DV keys)
+  void cluster_args_(ClusterKeysArgs& ck, const uint32_t* group, const int64_t* share) const {
+    ck.group = group;
+    ck.share_idx = share;
+    ck.group_base = (uint32_t)sh.gb;
+    ck.n_groups = (uint32_t)ng;
+    ck.n_shares = du.cl->n_shares;
+    ck.n_keys = (uint32_t)sh.cs->n_keys;
+    ck.ent = sh.cs->ent;
+    ck.st = sh.cs->st;
+  }
   int verify_(bool split);
   int store_(const uint32_t* merged);
   int gate_(const uint32_t* merged), store_rule_(), download_(), aggregate_fired_(), download_fired_();  // its steps
@@ -3363,10 +3449,25 @@ int DutyShardAdd::verify_(bool two_phases) {
   nm = sh.tab.size(), nnew = nm - sh.hashed, nt = p.n_touched(), np = p.tpos.size();
   out.n_new_msgs = nnew;
   out.resident = p.resident;
-  std::vector<uint8_t> hpk(48 * m), hsig(96 * m);
+  // the keys: the caller's 48 bytes per partial, or (a cluster duty) each partial's group and share index
+  // for k_cluster_keys -- as the plan orders them, like everything the verification reads per item
+  const ClusterShard* const cs = sh.cs;
+  std::vector<uint8_t> hpk(cs ? 0 : 48 * m), hsig(96 * m);
+  std::vector<uint32_t> hcg(cs ? m : 0);
+  std::vector<int64_t> hci(cs ? m : 0);
   for (size_t q = 0; q < m; q++) {
-    memcpy(&hpk[48 * q], a.pks + 48ull * p.order[q], 48);
+    if (cs) {
+      hcg[q] = a.group[p.order[q]];
+      hci[q] = a.share_idx[p.order[q]];
+    } else {
+      memcpy(&hpk[48 * q], a.pks + 48ull * p.order[q], 48);
+    }
     memcpy(&hsig[96 * q], a.sigs + 96ull * p.order[q], 96);
+  }
+  if (cs) {  // hbls_cluster_stats: the rule the kernel applies, on the host; duty_add counts it once the add has succeeded
+    for (size_t q = 0; q < m; q++)
+      out.n_named += cluster_key(hcg[q], hci[q], (uint32_t)sh.gb, (uint32_t)ng, du.cl->n_shares) != CLUSTER_NO_KEY ? 1 : 0;
+    out.n_nokey = m - out.n_named;
   }
   std::vector<uint64_t> noff(nnew);  // the new messages' offsets, from the first new byte
   const uint64_t nb0 = nnew ? sh.tab.t.off[sh.hashed] : 0;
@@ -3385,11 +3486,17 @@ int DutyShardAdd::verify_(bool two_phases) {
     sh.hm = nh;
     sh.hm_cap = cap;
   }
-  uint8_t *dpk, *dsig, *dmsg;
+  uint8_t *dpk = nullptr, *dsig, *dmsg;
   uint64_t* doff;
-  uint32_t *dlen, *dvgoff, *darr = nullptr, *dgseg = nullptr;
-  if (upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
+  uint32_t *dlen, *dvgoff, *darr = nullptr, *dgseg = nullptr, *dcg = nullptr;
+  int64_t* dci = nullptr;
+  if ((!cs && upload(d, I_PK, hpk.data(), hpk.size(), &dpk, &h)) || upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h))
+    return -1;
   PinnedUploads up;
+  if (cs) {
+    up.add(I_DCGRP, hcg.data(), m, &dcg);
+    up.add(I_DCSHARE, hci.data(), m, &dci);
+  }
   up.add(I_MSG, sh.tab.t.bytes.data() + nb0, sh.tab.t.bytes.size() - (nnew ? nb0 : sh.tab.t.bytes.size()), &dmsg);
   up.add(I_OFF, noff.data(), nnew, &doff);
   up.add(I_LEN, sh.tab.t.len.data() + sh.hashed, nnew, &dlen);
@@ -3434,6 +3541,12 @@ int DutyShardAdd::verify_(bool two_phases) {
   vc.s = s;
   vc.device_entry = true;
   vc.hm_ready = w.ev_side[2];
+  ClusterKeysArgs ck{};
+  if (cs) {
+    cluster_args_(ck, dcg, dci);
+    vc.cluster = &ck;
+    vc.cluster_wide = cs->wide;
+  }
   if (seg) {  // one first failure per set: the verification itself leaves set_first (preset by it)
     vc.gseg = dgseg;
     vc.n_seg = (uint32_t)n_sets;
@@ -3591,10 +3704,10 @@ int DutyShardAdd::aggregate_fired_() {
   uint32_t* dfrow;
   PinnedUploads up2;
   up2.add(I_DFROW, hfired.data(), nf, &dfrow);
-  void *pmem, *pdv;
+  void *pmem, *pdv = nullptr;  // (a cluster duty gathers no DV key bytes: k_cluster_keys resolves them by fired group id)
   if (upload_pinned(d, h, up2) || ensure_buf(h.io[I_CAND], nf * t * sizeof(uint32_t), &pmem) ||
       ensure_buf(h.io[I_CHOSEN], nf * t * sizeof(uint32_t), &pser) || ensure_buf(h.io[I_DFGRP], nf * sizeof(uint32_t), &pfg) ||
-      ensure_buf(h.io[I_DVPK], 48 * nf, &pdv) || ensure_buf(h.io[I_TAOUT], 96 * nf, &ptout) ||
+      (!sh.cs && ensure_buf(h.io[I_DVPK], 48 * nf, &pdv)) || ensure_buf(h.io[I_TAOUT], 96 * nf, &ptout) ||
       ensure_buf(h.io[I_TAST], nf, &ptst) || ensure_buf(h.io[I_AGGST], nf, &past))
     return -1;
   Ws& w2 = ws_acquire(d, s);
@@ -3616,7 +3729,7 @@ int DutyShardAdd::aggregate_fired_() {
   ga.midx = st.midx;
   ga.fmsg = st.fmsg;
   ga.fkey = st.fkey;
-  ga.dv_pks = sh.dvpk;
+  ga.dv_pks = sh.cs ? nullptr : sh.dvpk;
   ga.chosen = sa.chosen;
   ga.cidx = sa.cidx;
   ga.key = sa.key;
@@ -3631,6 +3744,13 @@ int DutyShardAdd::aggregate_fired_() {
   VerifyCall v2;  // the aggregates under the DV keys gathered by group id; the messages' lines are resident
   v2.pks = (const uint8_t*)pdv;
   v2.hm = sh.hm;
+  ClusterKeysArgs ck{};
+  if (sh.cs) {  // a cluster duty: the DV keys from the cluster by fired group id (no bytes were gathered: pdv is null)
+    cluster_args_(ck, (const uint32_t*)pfg, nullptr);
+    v2.cluster = &ck;
+    v2.cluster_wide = sh.cs->wide;
+    out.n_dv = nf;
+  }
   if (sel_verify(d, w2, x, v2, (const uint8_t*)ptst, (uint8_t*)past, s)) return -1;
   if (ws_release(w2, s)) return -1;
   lk.unlock();
@@ -3743,6 +3863,11 @@ int duty_add(Duty& du, const DutyAddArgs& a) {
     du.stats[2] += o.n_new_msgs;
     du.stats[3] += o.resident;
     du.stats[5] += o.n_full;
+    if (du.cl) {  // counted here, behind every shard's last download: a failed add counts nothing
+      du.cl->stats[3] += o.n_named;
+      du.cl->stats[4] += o.n_nokey;
+      du.cl->stats[5] += o.n_dv;
+    }
   }
   du.stats[0] += n;
   du.stats[4] += nf;
@@ -4506,7 +4631,11 @@ static int duty_add_entry(uint64_t duty, DutyAddArgs a, DutySetCall* sets) {
     if (sets->n_sets && !a.set_first) return set_err(who + ": set_first is required");
     if (const char* bad = duty_check_sets(sets->set_off, sets->n_sets, n)) return set_err(who + ": " + bad);
   }
-  if (n && (!a.pks || !a.sigs || !a.msg_off || !a.msg_len || !a.group || !a.share_idx || !a.vstatus || !a.stored))
+  if (du->cl) {  // a cluster duty resolves the keys itself: a caller that passes some mixes the two kinds of duty
+    if (a.pks) return set_err(who + ": pks must be NULL on a cluster duty (the keys are the cluster's)");
+    if (n && (!a.sigs || !a.msg_off || !a.msg_len || !a.group || !a.share_idx || !a.vstatus || !a.stored))
+      return set_err(who + ": sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
+  } else if (n && (!a.pks || !a.sigs || !a.msg_off || !a.msg_len || !a.group || !a.share_idx || !a.vstatus || !a.stored))
     return set_err(who + ": pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
   if (!a.msgs)
     for (size_t i = 0; i < n; i++)
@@ -4590,7 +4719,128 @@ int hbls_duty_close(uint64_t duty) {
   std::lock_guard<std::mutex> l(du->mu);  // behind the duty's call in flight, if any
   du->closed = true;
   for (DutyShard& s : du->sh) duty_free_shard(s);
+  du->cl.reset();  // a cluster duty: the last duty of a closed cluster frees the keys (no device lock is held here)
   return 0;
+}
+
+// One shard of hbls_cluster_open: its rows' compressed keys up, the decompression and membership test of
+// hbls_decompress_pubkeys_device into the resident table, the ladder tables, the statuses back; complete
+// (synchronised) when it returns.  Leaves what it allocated in s for the caller to free on failure.
+static int cluster_fill_shard(ClusterShard& s, const uint8_t* dv_pks, const uint8_t* pubshares, uint32_t n_shares,
+                              bool tables, uint8_t* hst, uint8_t** tmp) {
+  Dev& d = *s.d;
+  const size_t ng = s.ge - s.gb, row = 1 + (size_t)n_shares, nk = ng * row;
+  s.n_keys = nk;
+  if (!nk) return 0;
+  std::vector<uint8_t> keys(48 * nk);
+  for (size_t g = 0; g < ng; g++) {
+    memcpy(&keys[48 * g * row], dv_pks + 48 * (s.gb + g), 48);
+    memcpy(&keys[48 * (g * row + 1)], pubshares + 48 * (s.gb + g) * n_shares, 48 * (size_t)n_shares);
+  }
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  HCHK(hipMalloc((void**)&s.ent, nk * sizeof(G1AEntry)));
+  HCHK(hipMalloc((void**)&s.st, nk));
+  if (tables) HCHK(hipMalloc((void**)&s.wide, nk * KEY_WIDE_PTS * sizeof(G1WidePt)));
+  HCHK(hipMalloc((void**)tmp, 48 * nk));
+  HCHK(hipMemcpyAsync(*tmp, keys.data(), 48 * nk, hipMemcpyHostToDevice, d.stream));
+  TIMED(d, "k_dec_pk", d.stream, launch_dec_pk(*tmp, (uint32_t)nk, s.ent, s.st, d.stream));
+  if (tables) TIMED(d, "k_cluster_wide", d.stream, launch_cluster_wide(s.ent, s.st, (uint32_t)nk, s.wide, d.stream));
+  HCHK(hipMemcpyAsync(hst, s.st, nk, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));  // complete before any stream's kernel reads them: the cluster is immutable from here
+  return 0;
+}
+
+int hbls_cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_validators, uint32_t n_shares,
+                      uint32_t ladder_tables, uint8_t* key_status, uint64_t* cluster) {
+  if (ensure_init()) return -1;
+  if (!cluster) return set_err("hbls_cluster_open: cluster is required");
+  if (n_shares < 1 || n_shares > CLUSTER_MAX_SHARES)
+    return set_err("hbls_cluster_open: n_shares must be in 1.." + std::to_string(CLUSTER_MAX_SHARES));
+  if (ladder_tables > 1) return set_err("hbls_cluster_open: ladder_tables must be 0 or 1");
+  if (n_validators && (!dv_pks || !pubshares)) return set_err("hbls_cluster_open: dv_pks and pubshares are required");
+  // n_validators (1 + n_shares) < 2^32 - 1: a key's number is a uint32 entry number of the ladder-table
+  // path (KeyWideRef::ent), and KEY_WIDE_NONE is no key's
+  if (n_validators > 0xfffffffeull / (1 + (uint64_t)n_shares)) return set_err("hbls_cluster_open: too many keys");
+  auto cl = std::make_shared<Cluster>();  // (whatever a failing shard leaves allocated goes with it: nothing stays)
+  cl->n_validators = n_validators;
+  cl->n_shares = n_shares;
+  cl->tables = ladder_tables != 0;
+  const std::vector<Dev*> ds = devs();
+  const size_t nd = slot_shards(ds.size(), n_validators), row = 1 + (size_t)n_shares;
+  cl->sh.resize(nd);
+  std::vector<uint8_t> hst(n_validators * row);
+  for (size_t k = 0; k < nd; k++) {
+    ClusterShard& s = cl->sh[k];
+    s.d = ds[k];
+    s.gb = n_validators * k / nd;
+    s.ge = n_validators * (k + 1) / nd;
+    uint8_t* tmp = nullptr;
+    const int rc = cluster_fill_shard(s, dv_pks, pubshares, n_shares, cl->tables, hst.data() + s.gb * row, &tmp);
+    const std::string err = rc ? g_err : "";
+    if (tmp) {
+      std::lock_guard<std::mutex> lk(s.d->mu);
+      if (hipSetDevice(s.d->ord) == hipSuccess) (void)hipFree(tmp);
+    }
+    if (rc) return set_err("hbls_cluster_open: device " + std::to_string(ds[k]->ord) + ": " + err);
+  }
+  uint64_t bad = 0, built = 0;
+  for (size_t g = 0; g < n_validators; g++)
+    for (size_t j = 0; j < row; j++) {
+      const uint8_t st = hst[g * row + j];
+      const uint8_t* key = j ? pubshares + 48 * (g * n_shares + j - 1) : dv_pks + 48 * g;
+      bad += st ? 1 : 0;
+      built += (cl->tables && !st && !(key[0] & 0x40)) ? 1 : 0;  // good and finite (the compressed form's infinity bit)
+    }
+  if (key_status && !hst.empty()) memcpy(key_status, hst.data(), hst.size());
+  cl->stats[0] = hst.size();
+  cl->stats[1] = bad;
+  cl->stats[2] = built;
+  std::lock_guard<std::mutex> l(g_cluster_mu);
+  *cluster = g_cluster_next++;
+  g_clusters[*cluster] = cl;
+  return 0;
+}
+
+static std::shared_ptr<Cluster> cluster_find(uint64_t handle) {
+  std::lock_guard<std::mutex> l(g_cluster_mu);
+  auto it = g_clusters.find(handle);
+  return it == g_clusters.end() ? nullptr : it->second;
+}
+
+int hbls_cluster_close(uint64_t cluster) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl;
+  {
+    std::lock_guard<std::mutex> l(g_cluster_mu);
+    auto it = g_clusters.find(cluster);
+    if (it == g_clusters.end()) return set_err("hbls_cluster_close: no such cluster (never opened, or closed)");
+    cl = it->second;
+    g_clusters.erase(it);
+  }
+  return 0;  // (cl goes here, with no lock held: the keys with it unless a duty still holds them)
+}
+
+int hbls_cluster_stats(uint64_t cluster, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_stats: no such cluster (never opened, or closed)");
+  if (!out || n > 6) return set_err("hbls_cluster_stats: out is null or n above 6");
+  for (size_t k = 0; k < n; k++) out[k] = cl->stats[k].load();
+  return 0;
+}
+
+int hbls_duty_open_cluster(uint64_t cluster, uint32_t threshold, uint32_t max_stored, uint64_t* duty) {
+  if (ensure_init()) return -1;
+  if (!duty) return set_err("hbls_duty_open_cluster: duty is required");
+  if (threshold < 1 || threshold > (uint32_t)TA_SMALL_MAX)
+    return set_err("hbls_duty_open_cluster: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
+  if (max_stored < 1 || max_stored > DUTY_MAX_STORED)
+    return set_err("hbls_duty_open_cluster: max_stored must be in 1.." + std::to_string(DUTY_MAX_STORED));
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_duty_open_cluster: no such cluster (never opened, or closed)");
+  if (cl->n_validators >= 0xffffffffull / DUTY_MAX_STORED) return set_err("hbls_duty_open_cluster: too many groups");
+  return duty_open(nullptr, cl->n_validators, threshold, max_stored, duty, cl);
 }
 
 int hbls_timing(int enable) {

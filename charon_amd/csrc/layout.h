@@ -198,7 +198,7 @@ struct DutyGatherArgs {
   const uint32_t *mslot, *mserial;
   const int64_t* midx;
   const uint32_t *fmsg, *fkey;
-  const uint8_t* dv_pks;  // the shard's DV keys, by group
+  const uint8_t* dv_pks;  // the shard's DV keys, by group (null, a cluster duty: dv_out is not written)
   // per fired row: members as indices into the store, share indices, class key, state, message (what
   // k_ta_sel_fill reads; hist: the keys' histogram, zeroed by the caller), serials, group id, DV key
   uint32_t* chosen;
@@ -220,6 +220,26 @@ void launch_duty_set_first(const uint8_t* vstatus, const uint32_t* set_id, const
                            uint32_t* set_first, uint32_t n_sets, hipStream_t s);
 void launch_duty_gate(const uint8_t* vstatus, const uint32_t* set_id, uint32_t n, const uint32_t* set_first,
                       uint32_t n_sets, uint8_t* admit, hipStream_t s);
+
+// Cluster handles (cluster.hip k_cluster_keys / k_cluster_wide; the rule is cluster.h's).  One shard of a
+// cluster: n_keys = n_groups (1 + n_shares) resident entries with their statuses, row-major from group
+// group_base; `tables`: its good, finite keys have ladder tables (15 G1WidePt at 15 times the key's number).
+struct ClusterKeysArgs {
+  const uint32_t* group;     // per item: the group the caller names
+  const int64_t* share_idx;  // per item: the share index it names; null: the DV key of each group
+  uint32_t n;
+  uint32_t group_base, n_groups, n_shares, n_keys, tables;
+  const G1AEntry* ent;
+  const uint8_t* st;
+  // out, per item: the key phase's entry and status, and (went nullable) the key's number when it has a
+  // ladder table, else KEY_WIDE_NONE
+  G1AEntry* vpk;
+  uint8_t* vpkst;
+  uint32_t* went;
+};
+void launch_cluster_keys(const ClusterKeysArgs& a, hipStream_t s);
+// the ladder tables of the good, finite ones of n keys, key i's at wide[15 i ..]
+void launch_cluster_wide(const G1AEntry* ent, const uint8_t* st, uint32_t n, G1WidePt* wide, hipStream_t s);
 
 // Hashing and the pairing kernel (pipeline.hip).
 constexpr int GROUPS_PER_WAVE = 21;  // k_pair3: 3 lanes per pairing, 21 pairings per wave

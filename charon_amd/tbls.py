@@ -314,10 +314,13 @@ class HIPBLS:
         return list(st.raw[:g])
 
     # ------------------------------------------------------------------ duty sessions
-    def duty_open(self, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16) -> "Duty":
+    def duty_open(self, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16, cluster=None) -> "Duty":
         """A duty session over validators 0 .. len(dv_pks) - 1 (hbls_duty_open): each peer's set is one
         Duty.add, which verifies it, stores what the ParSigDB would store and returns the validators
-        that reached `threshold` through it with their verified aggregates."""
+        that reached `threshold` through it with their verified aggregates.  cluster: a callers.Cluster
+        -- the duty is opened on it (hbls_duty_open_cluster), over its validators and with its keys."""
+        if cluster is not None:
+            return Duty(self._L, (), threshold, max_stored, cluster=(cluster.handle(), cluster.n_validators))
         return Duty(self._L, dv_pks, threshold, max_stored)
 
 
@@ -341,11 +344,18 @@ class Duty:
     """One duty's state in device memory between calls (include/hipbls.h hbls_duty_*).  A context
     manager; calls on one Duty are serialised by the library."""
 
-    def __init__(self, L, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16):
-        self._L, self.n_groups, self.threshold = L, len(dv_pks), threshold
-        blob = b"".join(_need(p, PUBKEY_LEN, "public key") for p in dv_pks)
+    def __init__(self, L, dv_pks: Sequence[bytes], threshold: int, max_stored: int = 16, cluster=None):
+        """cluster: (handle, n_validators) of an open cluster (callers.Cluster) -- the duty then takes
+        its keys from it (hbls_duty_open_cluster): dv_pks is unused and every add passes pks=None."""
+        self._L, self.threshold, self._cluster = L, threshold, cluster is not None
         h = ctypes.c_uint64(0)
-        check(L.hbls_duty_open(_buf(blob), self.n_groups, threshold, max_stored, ctypes.byref(h)))
+        if cluster is not None:
+            self.n_groups = int(cluster[1])
+            check(L.hbls_duty_open_cluster(int(cluster[0]), threshold, max_stored, ctypes.byref(h)))
+        else:
+            self.n_groups = len(dv_pks)
+            blob = b"".join(_need(p, PUBKEY_LEN, "public key") for p in dv_pks)
+            check(L.hbls_duty_open(_buf(blob), self.n_groups, threshold, max_stored, ctypes.byref(h)))
         self._h: Optional[int] = h.value
 
     def __enter__(self) -> "Duty":
@@ -381,10 +391,13 @@ class Duty:
         return self._add(pks, msgs, sigs, groups, share_idx, [int(x) for x in set_off], first_error=True)
 
     def _add(self, pks, msgs, sigs, groups, share_idx, set_off, first_error=False):
-        n, t = len(pks), self.threshold
-        if not (n == len(msgs) == len(sigs) == len(groups) == len(share_idx)):
+        n, t = len(sigs), self.threshold
+        if not (n == len(msgs) == len(groups) == len(share_idx)) or (pks is not None and len(pks) != n):
             raise TblsError("duty add: length mismatch")
-        pk_blob = b"".join(_need(p, PUBKEY_LEN, "public key") for p in pks)
+        if self._cluster and pks is not None:
+            raise TblsError("duty add: a cluster duty takes no public keys (pks=None)")
+        # (pks=None on a plain duty goes down as NULL: the library's call error)
+        pk_arg = None if pks is None else _buf(b"".join(_need(p, PUBKEY_LEN, "public key") for p in pks))
         sig_blob = b"".join(_need(s, SIG_LEN, "signature") for s in sigs)
         mb, mo, ml = _pack_msgs([bytes(m) for m in msgs])
         rows = max(1, min(n, self.n_groups))
@@ -395,7 +408,7 @@ class Duty:
         grp = _u32_array([min(int(g), 0xFFFFFFFF) if g >= 0 else 0xFFFFFFFF for g in groups])
         idx = _i64_array([int(x) for x in share_idx])
         if set_off is None:
-            check(self._L.hbls_duty_add(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n, vst, stored,
+            check(self._L.hbls_duty_add(self._handle(), pk_arg, _buf(sig_blob), mb, mo, ml, grp, idx, n, vst, stored,
                                         ctypes.byref(first), fired, ctypes.byref(nf), chosen, out, tst, ast))
             r = DutyAdd()
         else:
@@ -404,7 +417,7 @@ class Duty:
             n_sets = max(len(set_off) - 1, 0)
             sf = (ctypes.c_uint32 * max(n_sets, 1))()
             call = self._L.hbls_duty_add_sets_first if first_error else self._L.hbls_duty_add_sets
-            check(call(self._handle(), _buf(pk_blob), _buf(sig_blob), mb, mo, ml, grp, idx, n,
+            check(call(self._handle(), pk_arg, _buf(sig_blob), mb, mo, ml, grp, idx, n,
                        _u32_array(set_off) if set_off else None, n_sets, vst, stored, ctypes.byref(first),
                        sf, fired, ctypes.byref(nf), chosen, out, tst, ast))
             r = DutySetsAdd()

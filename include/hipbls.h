@@ -490,6 +490,65 @@ int hbls_duty_add_sets_first(uint64_t duty, const uint8_t* pks, const uint8_t* s
                              uint32_t* fired, size_t* n_fired, uint32_t* chosen, uint8_t* ta_out,
                              uint8_t* ta_status, uint8_t* agg_vstatus);
 int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n);
+/* Cluster handles: the cluster lock as an object of the library, and duties that take their keys from
+ * it.  The reference ties a partial's key to its share index inside the verifier
+ * (core/parsigex/parsigex.go:146-170 NewEth2Verifier looks the pubshare up by (DV pubkey, ShareIdx) in
+ * the lock and fails with "unknown pubkey, not part of cluster lock" or "invalid shareIdx" before any
+ * pairing runs).  A duty opened on a cluster does the same on the device: its adds take no pks, each
+ * partial's key is resolved from (group[i], share_idx[i]), and the fired groups' aggregates are verified
+ * under the cluster's DV keys.
+ * hbls_cluster_open: row g of the cluster: entry 0 is validator g's DV key, entry j (1..n_shares) its
+ *   pubshare of share index j.  dv_pks: 48 n_validators bytes; pubshares: 48 n_validators n_shares
+ *   bytes, validator-major (share j of validator g at 48 (g n_shares + j - 1)).  key_status (nullable):
+ *   n_validators (1 + n_shares) bytes, row-major as above, each what hbls_decompress_pubkeys_device
+ *   reports for that key.  ladder_tables: 0 / 1 (1: every good, finite key also gets its ladder table,
+ *   15 points, as the learned key cache's HBLS_KEY_WIDE entries have).  1 <= n_shares <= 64;
+ *   n_validators (1 + n_shares) < 2^32 - 1.  The keys are decompressed and subgroup-checked once, sharded
+ *   over the devices as a duty's groups are (contiguous ranges, the devices as they are at open), and
+ *   live as long as the handle or any duty opened on it; after open the cluster never changes, and any
+ *   number of duties and calls read it concurrently.  A bad key does not fail the open: its status is
+ *   reported and kept, and every partial that names it gets HBLS_BAD_PUBKEY.  Nothing of the learned key
+ *   cache is used: hbls_pubkey_cache_clear, hbls_tune and HBLS_KEY_LEARN do not touch a cluster.
+ *   Device memory: 112 + 1 bytes per key, 1440 more with ladder tables -- about 1.7 GB at 100 000
+ *   validators x 11 keys with tables, 0.15 GB without.  That is what the cluster itself allocates and
+ *   what goes when it does.  Measured, device memory in use grew by 2.6 GB, not 1.7, across an open
+ *   with tables at that size (0.13 GB without tables): the other 0.9 GB is not the cluster's and does
+ *   not come back at close.  It is put down -- not verified -- to the scratch the HIP runtime reserves
+ *   on the queue of the device's library stream for the table builder's 3 096 bytes per lane.  Size
+ *   memory by the larger figure, once per process and device.  A failing device call leaves nothing
+ *   allocated.
+ * hbls_cluster_close invalidates the handle; the device memory goes when the last duty opened on the
+ *   cluster is closed.
+ * hbls_cluster_stats (n <= 6; counted on the host): out[0] keys held, out[1] keys with a non-zero
+ *   status, out[2] ladder tables built, out[3] partials of adds resolved to a key, out[4] partials of
+ *   adds that named no key, out[5] DV keys resolved for aggregates.  out[3..5] count the adds that
+ *   returned 0: an add that fails on a device call counts nothing.
+ * hbls_duty_open_cluster: a duty over the cluster's validators (n_groups = n_validators), threshold and
+ *   max_stored as hbls_duty_open takes them.  Its shards are the cluster's (same devices, same ranges),
+ *   whatever the device split is by now.  Every duty call serves it with unchanged signatures, except:
+ *   pks must be NULL in hbls_duty_add, hbls_duty_add_sets and hbls_duty_add_sets_first (a non-NULL pks
+ *   is a call error that writes nothing; on a plain duty a NULL pks stays the call error it is).
+ * Which key: partial i has a key iff group[i] < n_validators and 1 <= share_idx[i] <= n_shares, compared
+ *   on the full 64-bit share_idx (2^32 + 1, a negative value or INT64_MIN names no key; nothing is
+ *   truncated).  A partial that names no key gets HBLS_BAD_PUBKEY, is not stored, and is a set's first
+ *   failure like any other.  So a group[i] >= n_validators, which is "verify only" on a plain duty, has
+ *   no key on a cluster duty and fails the same way.  The shim tells the reference's two pre-errors apart
+ *   from its own group and share index when it sees HBLS_BAD_PUBKEY.
+ * DEFINING PROPERTY (the twin).  For any cluster and any sequence of calls, a cluster duty equals a plain
+ *   duty opened with the same dv_pks, threshold and max_stored under the same shard layout and fed the
+ *   same calls with pks[i] = the lock's 48 bytes for (group[i], share_idx[i]) where that names a key and
+ *   48 zero bytes (no compression flag: HBLS_BAD_PUBKEY) elsewhere: every output of every call (vstatus,
+ *   stored, first_serial, set_first, fired, n_fired, chosen, ta_out, ta_status, agg_vstatus),
+ *   hbls_duty_state, hbls_duty_stats, hbls_duty_set_stats and hbls_duty_first_stats are equal.  The one
+ *   exception is vstatus of hbls_duty_add_sets_first, held to that call's contract above against the
+ *   twin's exact statuses (as that call is against hbls_duty_add_sets).
+ * Not covered: hbls_slot_select_batch and the device entry points take no cluster, and nothing checks
+ *   that a validator's pubshares interpolate to its DV key. */
+int hbls_cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_validators, uint32_t n_shares,
+                      uint32_t ladder_tables, uint8_t* key_status, uint64_t* cluster);
+int hbls_cluster_close(uint64_t cluster);
+int hbls_cluster_stats(uint64_t cluster, uint64_t* out, size_t n);
+int hbls_duty_open_cluster(uint64_t cluster, uint32_t threshold, uint32_t max_stored, uint64_t* duty);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
