@@ -19,7 +19,7 @@ LIB = os.path.join(HERE, "lib", "libhipbls.so")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 
 SOURCES = ["hipbls.hip", "pipeline.hip", "threshold.hip", "vbatch.hip", "vgroup.hip", "roots.hip", "hash.hip", "msm.hip",
-           "hashsplit.hip", "duty.hip", "dutyfirst.hip", "cluster.hip"]
+           "hashsplit.hip", "duty.hip", "dutyfirst.hip", "cluster.hip", "lockcheck.hip"]
 
 
 def build_id(defines=()) -> str:
@@ -844,6 +844,92 @@ def build_clusterdev(force: bool = False, verbose: bool = True) -> str:
     return out
 
 
+LOCKCHECKHOST_PREFIX = "hbls-lockcheckhost:"
+LOCKCHECKHOST_HEADERS = ("lockcheck.h",)
+
+
+def lockcheckhost_build_id(root: str = "") -> str:
+    """The id embedded in the lock check's harness (tests/native/lockcheckhost.cpp, `lk_build_id()`):
+    sha256 over its source, the header it compiles and the flags."""
+    import hashlib
+    root = root or ROOT
+    h = hashlib.sha256()
+    for f in [os.path.join(root, "tests", "native", "lockcheckhost.cpp")] + \
+            [os.path.join(root, "charon_amd", "csrc", f) for f in LOCKCHECKHOST_HEADERS]:
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(HOSTCHECK_FLAGS).encode())
+    return LOCKCHECKHOST_PREFIX + h.hexdigest()[:16]
+
+
+def build_lockcheckhost(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_lockcheckhost.so (tests/test_lock_check_host.py): the rule of
+    hbls_cluster_check (lockcheck.h: the signed binomial coefficients, their bit length, the plan) on
+    the CPU; test-only.  Reused when its embedded id equals the tree's, as build_clustercheck."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "lockcheckhost.cpp")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_lockcheckhost.so")
+    bid = lockcheckhost_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-lockcheckhost:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DLK_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
+    subprocess.run(cmd, check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out}")
+    return out
+
+
+LOCKCHECKDEV_PREFIX = "hbls-lockcheckdev:"
+
+
+def lockcheckdev_build_id(root: str = "") -> str:
+    """The id embedded in the lock check's device harness (tests/native/lockcheckdev.hip,
+    tests/test_gpu_lock_check_kernels.py; `ld_build_id()`): sha256 over its source, the device
+    harnesses' shared devblocks.h, the product source it compiles (lockcheck.hip), every header of
+    charon_amd/csrc and the flags."""
+    import hashlib
+    root = root or ROOT
+    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
+    h = hashlib.sha256()
+    for f in [os.path.join(native, "lockcheckdev.hip"), os.path.join(native, "devblocks.h"),
+              os.path.join(csrc, "lockcheck.hip")] + \
+            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
+        h.update(os.path.relpath(f, root).encode() + b"\0")
+        with open(f, "rb") as fh:
+            h.update(fh.read())
+        h.update(b"\0")
+    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
+    return LOCKCHECKDEV_PREFIX + h.hexdigest()[:16]
+
+
+def build_lockcheckdev(force: bool = False, verbose: bool = True) -> str:
+    """tests/native/libhbls_lockcheckdev.so: k_lock_check and k_lock_fold on the device over the
+    test's keys and statuses, a harness of its own like build_clusterdev; test-only.  Reused when its
+    embedded id equals the tree's."""
+    import re
+    src = os.path.join(ROOT, "tests", "native", "lockcheckdev.hip")
+    out = os.path.join(ROOT, "tests", "native", "libhbls_lockcheckdev.so")
+    bid = lockcheckdev_build_id()
+    if not force and os.path.exists(out):
+        with open(out, "rb") as f:
+            m = re.search(rb"hbls-lockcheckdev:[0-9a-f]{16}", f.read())
+        if m and m.group(0).decode() == bid:
+            return out
+    t0 = time.time()
+    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DLD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
+                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s")
+    return out
+
+
 def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
     """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
     return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
@@ -908,7 +994,7 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     failed = []
     for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
                build_subgdev, build_dutysetcheck, build_dutysetdev, build_dutyfirstcheck, build_dutyfirstdev,
-               build_clustercheck, build_clusterdev):
+               build_clustercheck, build_clusterdev, build_lockcheckhost, build_lockcheckdev):
         try:
             fn(force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile

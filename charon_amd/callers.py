@@ -377,12 +377,60 @@ class Cluster:
         return dict(zip(("keys", "bad_keys", "ladder_tables", "partials_resolved", "partials_no_key", "dv_keys_resolved"),
                         (int(x) for x in out)))
 
+    def check(self, threshold: int) -> Tuple[List[int], List[int]]:
+        """hbls_cluster_check: do every validator's pubshares interpolate to its DV key under
+        `threshold` -> (row_status, row_windows), one entry per validator in cluster order.  Status OK:
+        consistent; BAD_PUBKEY: one of the row's keys has a non-zero key_status (nothing computed,
+        windows 0); NOT_VERIFIED: bit k of the row's windows is set iff the threshold-th forward
+        difference over its keys k .. k + threshold (0: the DV key, j: the pubshare of share index j)
+        does not vanish.  Only reads the cluster."""
+        import ctypes
+
+        st = ctypes.create_string_buffer(max(self.n_validators, 1))
+        win = (ctypes.c_uint64 * max(self.n_validators, 1))()
+        if self._L.hbls_cluster_check(self.handle(), threshold, st, win, None) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return list(st.raw[:self.n_validators]), [int(w) for w in win[:self.n_validators]]
+
+    def inconsistent(self, threshold: int) -> Dict[bytes, Tuple[int, List[int], List[int]]]:
+        """The validators check(threshold) does not report OK: {validator pubkey: (status, failing
+        windows, candidate positions)}; empty for a consistent lock.  The candidates
+        (lock_check_candidates) are a single wrong key's position where the windows determine it:
+        0 the DV key, j the pubshare of share index j."""
+        status, windows = self.check(threshold)
+        W = self.n_shares - threshold + 1
+        return {pk: (st, [k for k in range(W) if (w >> k) & 1], lock_check_candidates(self.n_shares, threshold, w))
+                for pk, st, w in zip(self.keys, status, windows) if st != OK}
+
+    def check_stats(self) -> Dict[str, int]:
+        import ctypes
+
+        out = (ctypes.c_uint64 * 2)()
+        if self._L.hbls_cluster_check_stats(self.handle(), out, 2) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return dict(zip(("checks", "rows_not_verified"), (int(x) for x in out)))
+
     def close(self) -> None:
         """Invalidates the handle; the device memory goes with the last duty opened on the cluster."""
         if self._h is not None:
             h, self._h = self._h, None
             if self._L.hbls_cluster_close(h) != 0:
                 raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+
+
+def lock_check_candidates(n_shares: int, threshold: int, windows: int) -> List[int]:
+    """The positions 0 .. n_shares of a row (0: the DV key, j: the pubshare of share index j) that lie in
+    every failing window of hbls_cluster_check's mask `windows` and in no passing one; window k holds the
+    positions k .. k + threshold.  One wrong key at p fails exactly the windows with k <= p <= k +
+    threshold, so p is always among its own mask's candidates, and alone wherever the windows
+    determine it; no failing window, or failures no single position explains, give []."""
+    W = n_shares - threshold + 1
+    if not 1 <= threshold <= n_shares or windows >> W:
+        raise TblsError("lock check: threshold must be in 1 .. n_shares and the mask within its windows")
+    if not windows:
+        return []
+    return [p for p in range(n_shares + 1)
+            if all(((windows >> k) & 1) == (1 if k <= p <= k + threshold else 0) for k in range(W))]
 
 
 class ParSigDuty:

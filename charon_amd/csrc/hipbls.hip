@@ -3169,6 +3169,7 @@ struct Cluster {
   bool tables = false;
   std::vector<ClusterShard> sh;
   std::atomic<uint64_t> stats[6] = {};  // hbls_cluster_stats
+  std::atomic<uint64_t> check_stats[2] = {};  // hbls_cluster_check_stats
   ~Cluster() {
     for (ClusterShard& s : sh) {
       if (!s.d) continue;
@@ -4827,6 +4828,74 @@ int hbls_cluster_stats(uint64_t cluster, uint64_t* out, size_t n) {
   if (!cl) return set_err("hbls_cluster_stats: no such cluster (never opened, or closed)");
   if (!out || n > 6) return set_err("hbls_cluster_stats: out is null or n above 6");
   for (size_t k = 0; k < n; k++) out[k] = cl->stats[k].load();
+  return 0;
+}
+
+// One shard of hbls_cluster_check: k_lock_check and k_lock_fold over the shard's own rows on its library
+// stream, the rows' statuses and window masks into the caller's host arrays (the shard's part of them);
+// complete (synchronised) when it returns.  The kernels only read the cluster.  What it allocates goes
+// when it returns, whatever it returns.
+static int cluster_check_shard(const ClusterShard& s, const LockPlan& plan, uint8_t* hstatus, uint64_t* hwindows) {
+  const size_t ng = s.ge - s.gb;
+  if (!ng) return 0;
+  Dev& d = *s.d;
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  struct Bufs {
+    void* p[3] = {};
+    ~Bufs() {
+      for (void* q : p)
+        if (q) (void)hipFree(q);
+    }
+  } b;
+  HCHK(hipMalloc(&b.p[0], ng * plan.windows));
+  HCHK(hipMalloc(&b.p[1], ng));
+  HCHK(hipMalloc(&b.p[2], ng * sizeof(uint64_t)));
+  HCHK(hipMemsetAsync(b.p[2], 0, ng * sizeof(uint64_t), d.stream));  // a row with a bad-status key: no window
+  TIMED(d, "k_lock_check", d.stream,
+        launch_lock_check(s.ent, s.st, (uint32_t)ng, plan, (uint8_t*)b.p[0], (uint8_t*)b.p[1], (uint64_t*)b.p[2], d.stream));
+  HCHK(hipMemcpyAsync(hstatus, b.p[1], ng, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipMemcpyAsync(hwindows, b.p[2], ng * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));
+  return 0;
+}
+
+int hbls_cluster_check(uint64_t cluster, uint32_t threshold, uint8_t* row_status, uint64_t* row_windows, size_t* n_bad) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_check: no such cluster (never opened, or closed)");
+  LockPlan plan;
+  if (!lock_plan(cl->n_shares, threshold, plan))
+    return set_err("hbls_cluster_check: threshold must be in 1.." + std::to_string(cl->n_shares) + " (the cluster's n_shares)");
+  if (cl->n_validators && !row_status) return set_err("hbls_cluster_check: row_status is required");
+  // the shards' results gather here: the caller's arrays are written once every shard has succeeded
+  std::vector<uint8_t> hst(cl->n_validators);
+  std::vector<uint64_t> hwin(cl->n_validators);
+  for (const ClusterShard& s : cl->sh) {
+    if (cluster_check_shard(s, plan, hst.data() + s.gb, hwin.data() + s.gb)) {
+      const std::string err = g_err;
+      return set_err("hbls_cluster_check: device " + std::to_string(s.d->ord) + ": " + err);
+    }
+  }
+  uint64_t bad = 0, inconsistent = 0;
+  for (uint8_t st : hst) {
+    bad += st ? 1 : 0;
+    inconsistent += st == ST_NOT_VERIFIED ? 1 : 0;
+  }
+  if (!hst.empty()) memcpy(row_status, hst.data(), hst.size());
+  if (row_windows && !hwin.empty()) memcpy(row_windows, hwin.data(), hwin.size() * sizeof(uint64_t));
+  if (n_bad) *n_bad = (size_t)bad;
+  cl->check_stats[0] += 1;
+  cl->check_stats[1] += inconsistent;
+  return 0;
+}
+
+int hbls_cluster_check_stats(uint64_t cluster, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_check_stats: no such cluster (never opened, or closed)");
+  if (!out || n > 2) return set_err("hbls_cluster_check_stats: out is null or n above 2");
+  for (size_t k = 0; k < n; k++) out[k] = cl->check_stats[k].load();
   return 0;
 }
 

@@ -7,6 +7,7 @@
 #include "ta_small.h"
 #include "tasel.h"
 #include "subgbatch.h"
+#include "lockcheck.h"
 
 // Occupancy targets (waves per SIMD) of the heavy kernels: 1 lets the compiler use all 512
 // registers of a lane, 2 gives each wave 256, 3 gives 168 (spilling the rest to scratch).  Chosen
@@ -240,6 +241,14 @@ struct ClusterKeysArgs {
 void launch_cluster_keys(const ClusterKeysArgs& a, hipStream_t s);
 // the ladder tables of the good, finite ones of n keys, key i's at wide[15 i ..]
 void launch_cluster_wide(const G1AEntry* ent, const uint8_t* st, uint32_t n, G1WidePt* wide, hipStream_t s);
+
+// hbls_cluster_check (lockcheck.hip k_lock_check / k_lock_fold; the rule and the plan are lockcheck.h's)
+// over one shard's n_rows rows of 1 + plan.n_shares resident entries with their statuses, read-only.
+// verdict: n_rows * plan.windows bytes of working space (a lane's D_k != O; the lanes of a row with a
+// bad-status key write none, and none of that row's is read).  Out, per row: row_status, and -- unless
+// the row has a bad-status key, whose word is left as it is -- row_windows.
+void launch_lock_check(const G1AEntry* ent, const uint8_t* st, uint32_t n_rows, const LockPlan& plan, uint8_t* verdict,
+                       uint8_t* row_status, uint64_t* row_windows, hipStream_t s);
 
 // Hashing and the pairing kernel (pipeline.hip).
 constexpr int GROUPS_PER_WAVE = 21;  // k_pair3: 3 lanes per pairing, 21 pairings per wave

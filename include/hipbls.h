@@ -542,13 +542,40 @@ int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n);
  *   hbls_duty_state, hbls_duty_stats, hbls_duty_set_stats and hbls_duty_first_stats are equal.  The one
  *   exception is vstatus of hbls_duty_add_sets_first, held to that call's contract above against the
  *   twin's exact statuses (as that call is against hbls_duty_add_sets).
- * Not covered: hbls_slot_select_batch and the device entry points take no cluster, and nothing checks
- *   that a validator's pubshares interpolate to its DV key. */
+ * hbls_cluster_check: is the lock consistent -- do the pubshares of every validator interpolate to its DV
+ *   key under `threshold`.  A lock with a wrong, swapped or stale pubshare opens clean (every key decodes
+ *   and is in the subgroup) and every partial verifies under its pubshare; only the aggregates fail
+ *   (agg_vstatus HBLS_NOT_VERIFIED), with no hint which key is at fault.  This call finds it beforehand.
+ *   Row g is P_0 (the DV key, node 0), P_1 .. P_n (the pubshares, nodes 1 .. n = n_shares): points of a
+ *   cyclic group of prime order on consecutive nodes, which lie on a polynomial of degree < threshold in
+ *   the exponent iff every threshold-th forward difference vanishes,
+ *       D_k = sum_{i=0..t} (-1)^(t-i) C(t,i) P_{k+i} = O     for k = 0 .. n - t   (W = n - t + 1 windows).
+ *   The criterion is exact both ways (the sequences with every D_k = O form a space of dimension t, the
+ *   polynomials of degree < t), and a row of lower degree passes too: the call answers "degree < t",
+ *   which is what interpolation from any t shares needs.  1 <= threshold <= n_shares; anything else, or
+ *   an unknown handle, is a call error (-1, hbls_last_error) that writes nothing.
+ *   row_status (n_validators bytes): HBLS_OK when all W differences of the row are O; HBLS_BAD_PUBKEY
+ *   when any of the row's 1 + n_shares keys has a non-zero key_status -- nothing is computed for such a
+ *   row and its row_windows is 0: it is not inconsistent, it is unusable; HBLS_NOT_VERIFIED when some
+ *   D_k != O.  row_windows (nullable, n_validators words): bit k set iff D_k != O (W <= 64).  If exactly
+ *   one key P_p of a row is wrong, exactly the windows with k <= p <= k + t fail, which locates it.
+ *   *n_bad (nullable): the rows with a non-zero status.  A key at infinity with status 0 is the identity
+ *   in the sums: the group law decides, nothing is special-cased into a status.
+ *   Blocking and thread-safe; it only reads the cluster, so it may run beside any number of duties and
+ *   adds on it and changes nothing they return.  It runs per shard, on the shard's device, over the
+ *   shard's own rows (the ranges as they were at open); a failing device call leaves nothing allocated
+ *   and writes nothing.
+ * hbls_cluster_check_stats (n <= 2; counted on the host): out[0] checks that returned 0, out[1] rows
+ *   those checks reported HBLS_NOT_VERIFIED.
+ * Not covered: hbls_slot_select_batch and the device entry points take no cluster. */
 int hbls_cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_validators, uint32_t n_shares,
                       uint32_t ladder_tables, uint8_t* key_status, uint64_t* cluster);
 int hbls_cluster_close(uint64_t cluster);
 int hbls_cluster_stats(uint64_t cluster, uint64_t* out, size_t n);
 int hbls_duty_open_cluster(uint64_t cluster, uint32_t threshold, uint32_t max_stored, uint64_t* duty);
+int hbls_cluster_check(uint64_t cluster, uint32_t threshold, uint8_t* row_status, uint64_t* row_windows,
+                       size_t* n_bad);
+int hbls_cluster_check_stats(uint64_t cluster, uint64_t* out, size_t n);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
