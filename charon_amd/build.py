@@ -1,13 +1,18 @@
-"""Build libhipbls.so (gfx950) in-tree, plus the test-only CPU harness, C client and device block
-harness.
+"""Build libhipbls.so (gfx950) in-tree, plus the test-only harnesses: the single-file CPU and device
+harnesses (the HARNESSES table), the C client and the multi-unit device block harnesses.
 
     python -m charon_amd.build            # product library + test harnesses
-The product library is compiled by hipcc for --offload-arch=gfx950 only.
+The product library is compiled by hipcc for --offload-arch=gfx950 only.  A new single-file harness
+is a row of HARNESSES: its id, its build and its place in build_test_extras follow from the row.
 """
 
 from __future__ import annotations
 
+import collections
+import functools
+import hashlib
 import os
+import re
 import subprocess
 import sys
 import time
@@ -67,32 +72,121 @@ def build_library(force: bool = False, verbose: bool = True, defines=(), out: st
 HOSTCHECK_PREFIX = "hbls-hostcheck:"
 HOSTCHECK_FLAGS = ["-O3", "-march=x86-64-v3", "-std=c++17", "-pthread", "-shared", "-fPIC"]
 
+# The single-file test harnesses, in the order they are built.  From the name follow the source
+# (tests/native/<name>.cpp for g++, .hip for hipcc), the output (tests/native/libhbls_<name>.so) and
+# the id's prefix (hbls-<name>:).  stem: the build passes -D<STEM>_BUILD_ID="<id>" and the harness
+# exports <stem>_build_id().  headers: the charon_amd/csrc headers hashed into the id -- ALL of
+# them, or exactly the ones the source includes, in this order (tests/test_harness_table.py holds
+# each list to the compiler's own include list).  sources: the product sources a device harness
+# compiles itself, hashed too, after the device harnesses' shared devblocks.h.
+HOST, DEVICE, ALL = "host", "device", "all"
+Harness = collections.namedtuple("Harness", "kind stem headers sources what")
+HARNESSES = {
+    "hostcheck": Harness(HOST, "HC", ALL, (), "the kernels' arithmetic on the CPU: cpu_baseline and the host tests"),
+    "widecheck": Harness(HOST, "WC", ALL, (), "the learned keys' ladder tables and the ladders through them on the CPU"),
+    "taselcheck": Harness(HOST, "TS", ("tasel.h",), (), "the verified-member selection rule of hbls_slot_select_device"),
+    "slothostcheck": Harness(HOST, "HS", ("hslot.h", "hgroup.h", "msgtable.h", "tasel.h"), (),
+                             "the host plan of hbls_slot_select_batch and its matching rule"),
+    "dutycheck": Harness(HOST, "DC", ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h", "tasel.h"), (),
+                         "the storing and firing rule of a duty session and the host plan of hbls_duty_add"),
+    "subgcheck": Harness(HOST, "SG", ("subgbatch.h", "sha256.h", "hd.h", "vplan.h"), (),
+                         "the batched subgroup test's digits and its plan"),
+    "widedev": Harness(DEVICE, "WD", ALL, (), "the learned keys' ladder tables and the ladders through them on the device"),
+    "subgdev": Harness(DEVICE, "SD", ALL, ("msm.hip",),
+                       "the batched subgroup test's class sums and weighted sums over explicit buckets"),
+    "dutysetcheck": Harness(HOST, "DS", ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h"), (),
+                            "the host side of hbls_duty_add_sets: set_off, set ids, the merge, admission, storing"),
+    "dutysetdev": Harness(DEVICE, "DSD", ALL, ("duty.hip",),
+                          "k_duty_set_first, k_duty_gate and k_duty_store behind the gate over explicit words"),
+    "dutyfirstcheck": Harness(HOST, "DF", ("dutyfirst.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h"), (),
+                              "the host side of hbls_duty_add_sets_first: the set-major plan and the descent rule"),
+    "dutyfirstdev": Harness(DEVICE, "DFD", ALL, ("dutyfirst.hip",),
+                            "the kernels of the segmented first-error verification over explicit bytes"),
+    "clustercheck": Harness(HOST, "CC", ("cluster.h",), (), "the key rule of a cluster handle (cluster_key)"),
+    "clusterdev": Harness(DEVICE, "CD", ALL, ("cluster.hip",), "k_cluster_keys and k_cluster_wide over explicit words"),
+    "lockcheckhost": Harness(HOST, "LK", ("lockcheck.h",), (),
+                             "the rule of hbls_cluster_check: signed binomial coefficients, their bit length, the plan"),
+    "lockcheckdev": Harness(DEVICE, "LD", ALL, ("lockcheck.hip",), "k_lock_check and k_lock_fold over the test's keys"),
+}
 
-def hostcheck_build_id(defines=(), flags=None, root: str = "") -> str:
-    """The id embedded in the CPU harness: sha256 (16 hex digits) over the harness source, every
-    header of charon_amd/csrc (it includes the kernels' arithmetic from there), the compiler flags
-    and the defines -- what `hc_build_id()` of a harness built from this tree returns."""
-    import hashlib
-    root = root or ROOT
+
+def _csrc_headers(root: str) -> list:
     csrc = os.path.join(root, "charon_amd", "csrc")
+    return sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+
+
+def _files_id(prefix: str, files, root: str, flags) -> str:
+    """prefix + sha256 (16 hex digits) over each file's root-relative path and bytes, then the flags."""
     h = hashlib.sha256()
-    files = [os.path.join(root, "tests", "native", "hostcheck.cpp")] + \
-        sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
     for f in files:
         h.update(os.path.relpath(f, root).encode() + b"\0")
         with open(f, "rb") as fh:
             h.update(fh.read())
         h.update(b"\0")
-    h.update(" ".join((flags or HOSTCHECK_FLAGS) + ["-D" + d for d in defines]).encode())
-    return HOSTCHECK_PREFIX + h.hexdigest()[:16]
+    h.update(" ".join(flags).encode())
+    return prefix + h.hexdigest()[:16]
 
 
-def embedded_hostcheck_id(path: str) -> str:
-    """The harness id inside a built harness file, read from its bytes (no loading)."""
-    import re
+def harness_source(name: str, root: str = "") -> str:
+    return os.path.join(root or ROOT, "tests", "native", name + (".hip" if HARNESSES[name].kind == DEVICE else ".cpp"))
+
+
+def harness_path(name: str) -> str:
+    return os.path.join(ROOT, "tests", "native", f"libhbls_{name}.so")
+
+
+def harness_build_id(name: str, root: str = "", defines=(), flags=None) -> str:
+    """The id embedded in a harness of the table, what its `<stem>_build_id()` returns when it was
+    built from this tree: over its source, for a device harness devblocks.h and its product sources,
+    its csrc headers, the compiler flags (flags: another set, e.g. SANITIZED_FLAGS) and the defines."""
+    root = root or ROOT
+    h, csrc = HARNESSES[name], os.path.join(root, "charon_amd", "csrc")
+    files = [harness_source(name, root)]
+    if h.kind == DEVICE:
+        files += [os.path.join(root, "tests", "native", "devblocks.h")] + [os.path.join(csrc, f) for f in h.sources]
+    files += _csrc_headers(root) if h.headers == ALL else [os.path.join(csrc, f) for f in h.headers]
+    flags = flags or (DEVBLOCKS_FLAGS if h.kind == DEVICE else HOSTCHECK_FLAGS)
+    return _files_id(f"hbls-{name}:", files, root, flags + ["-D" + d for d in defines])
+
+
+def embedded_harness_id(path: str, name: str) -> str:
+    """The id inside a built harness file, read from its bytes (no loading); "" if it has none."""
     with open(path, "rb") as f:
-        m = re.search(rb"hbls-hostcheck:[0-9a-f]{16}", f.read())
+        m = re.search(rb"hbls-" + name.encode() + rb":[0-9a-f]{16}", f.read())
     return m.group(0).decode() if m else ""
+
+
+def build_harness(name: str, force: bool = False, verbose: bool = True, defines=(), out: str = "") -> str:
+    """Build a harness of the table; test-only.  One whose embedded id equals this tree's is reused;
+    any other -- a hashed file touched, other flags -- is rebuilt.  defines / out: another build of
+    it (e.g. hostcheck with ("HB_HOST_MUL28",): the 28-bit host products)."""
+    h, src, out = HARNESSES[name], harness_source(name), out or harness_path(name)
+    bid = harness_build_id(name, defines=defines)
+    if not force and os.path.exists(out) and embedded_harness_id(out, name) == bid:
+        return out
+    t0 = time.time()
+    stamp = ["-D" + d for d in defines] + [f'-D{h.stem}_BUILD_ID="{bid}"']
+    if h.kind == DEVICE:
+        subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + stamp + ["-shared", "-o", out + ".tmp", src, "-Wl,-rpath,/opt/rocm/lib"],
+                       check=True, timeout=3000)
+    else:
+        subprocess.run(["g++"] + HOSTCHECK_FLAGS + stamp + ["-o", out + ".tmp", src], check=True, timeout=900)
+    os.replace(out + ".tmp", out)
+    if verbose:
+        print(f"built {out} in {time.time() - t0:.1f}s" if h.kind == DEVICE else f"built {out}")
+    return out
+
+
+# build_<name>(force=False, verbose=True) and <name>_build_id(root="") of every harness of the table
+for _name in HARNESSES:
+    globals()["build_" + _name] = functools.partial(build_harness, _name)
+    globals()[_name + "_build_id"] = functools.partial(harness_build_id, _name)
+embedded_hostcheck_id = functools.partial(embedded_harness_id, name="hostcheck")
+
+
+def hostcheck_build_id(defines=(), flags=None, root: str = "") -> str:
+    """harness_build_id("hostcheck") with the defines first, as its callers pass them."""
+    return harness_build_id("hostcheck", root, defines, flags)
 
 
 def check_hostcheck(path: str, defines=(), root: str = "") -> str:
@@ -102,270 +196,6 @@ def check_hostcheck(path: str, defines=(), root: str = "") -> str:
     if got != want:
         raise RuntimeError(f"stale CPU harness {path}: built as {got or '(unstamped)'}, the tree is {want}")
     return got
-
-
-def build_hostcheck(force: bool = False, verbose: bool = True, defines=(), out: str = "") -> str:
-    """defines / out: another build of the harness (e.g. ("HB_HOST_MUL28",): the 28-bit host
-    products, tests/test_sanitizers.py).  A harness whose embedded id (hc_build_id) equals this
-    tree's is reused; any other -- a header touched, other flags -- is rebuilt."""
-    src = os.path.join(ROOT, "tests", "native", "hostcheck.cpp")
-    out = out or os.path.join(ROOT, "tests", "native", "libhbls_hostcheck.so")
-    bid = hostcheck_build_id(defines)
-    if not force and os.path.exists(out) and embedded_hostcheck_id(out) == bid:
-        return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + ["-D" + d for d in defines] + [f'-DHC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-WIDECHECK_PREFIX = "hbls-widecheck:"
-
-
-def widecheck_build_id(root: str = "") -> str:
-    """The id embedded in the ladder-table harness (tests/native/widecheck.cpp, `wc_build_id()`):
-    sha256 over its source, every header of charon_amd/csrc and the compiler flags, as
-    hostcheck_build_id."""
-    import hashlib
-    root = root or ROOT
-    csrc = os.path.join(root, "charon_amd", "csrc")
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "widecheck.cpp")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return WIDECHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_widecheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_widecheck.so (tests/test_key_wide_host.py): the learned keys' ladder
-    tables and the ladders through them on the CPU; test-only.  Reused when its embedded id equals
-    the tree's, as build_hostcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "widecheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_widecheck.so")
-    bid = widecheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-widecheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DWC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-TASELCHECK_PREFIX = "hbls-taselcheck:"
-
-
-def taselcheck_build_id(root: str = "") -> str:
-    """The id embedded in the member-selection harness (tests/native/taselcheck.cpp, `ts_build_id()`):
-    sha256 over its source, the one header it compiles (charon_amd/csrc/tasel.h) and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "taselcheck.cpp"),
-              os.path.join(root, "charon_amd", "csrc", "tasel.h")]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return TASELCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_taselcheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_taselcheck.so (tests/test_tasel_host.py): the verified-member selection
-    rule of hbls_slot_select_device on the CPU; test-only.  Reused when its embedded id equals the
-    tree's, as build_hostcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "taselcheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_taselcheck.so")
-    bid = taselcheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-taselcheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DTS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-SLOTHOSTCHECK_PREFIX = "hbls-slothostcheck:"
-SLOTHOSTCHECK_HEADERS = ("hslot.h", "hgroup.h", "msgtable.h", "tasel.h")
-
-
-def slothostcheck_build_id(root: str = "") -> str:
-    """The id embedded in the host-buffer duty's harness (tests/native/slothostcheck.cpp,
-    `hs_build_id()`): sha256 over its source, the headers it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "slothostcheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in SLOTHOSTCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return SLOTHOSTCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_slothostcheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_slothostcheck.so (tests/test_hslot.py): the host plan of
-    hbls_slot_select_batch and its matching rule on the CPU; test-only.  Reused when its embedded id
-    equals the tree's, as build_hostcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "slothostcheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_slothostcheck.so")
-    bid = slothostcheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-slothostcheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DHS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-DUTYCHECK_PREFIX = "hbls-dutycheck:"
-DUTYCHECK_HEADERS = ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h", "tasel.h")
-
-
-def dutycheck_build_id(root: str = "") -> str:
-    """The id embedded in the duty sessions' harness (tests/native/dutycheck.cpp, `dc_build_id()`):
-    sha256 over its source, the headers it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "dutycheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return DUTYCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_dutycheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_dutycheck.so (tests/test_duty_host.py): the storing and firing rule of a
-    duty session and the host plan of hbls_duty_add on the CPU; test-only.  Reused when its embedded
-    id equals the tree's, as build_hostcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "dutycheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_dutycheck.so")
-    bid = dutycheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-dutycheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-DUTYSETCHECK_PREFIX = "hbls-dutysetcheck:"
-DUTYSETCHECK_HEADERS = ("dutysel.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h")
-
-
-def dutysetcheck_build_id(root: str = "") -> str:
-    """The id embedded in the set-atomic adds' harness (tests/native/dutysetcheck.cpp,
-    `ds_build_id()`): sha256 over its source, the headers it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "dutysetcheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYSETCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return DUTYSETCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_dutysetcheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_dutysetcheck.so (tests/test_duty_sets_host.py): the host side of
-    hbls_duty_add_sets on the CPU -- set_off's validation, the plan's set ids, the shards' merge, the
-    admission predicate and the storing rule behind it; test-only.  Reused when its embedded id
-    equals the tree's, as build_dutycheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "dutysetcheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_dutysetcheck.so")
-    bid = dutysetcheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-dutysetcheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDS_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-SUBGCHECK_PREFIX = "hbls-subgcheck:"
-SUBGCHECK_HEADERS = ("subgbatch.h", "sha256.h", "hd.h", "vplan.h")
-
-
-def subgcheck_build_id(root: str = "") -> str:
-    """The id embedded in the batched subgroup test's harness (tests/native/subgcheck.cpp,
-    `sg_build_id()`): sha256 over its source, the headers it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "subgcheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in SUBGCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return SUBGCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_subgcheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_subgcheck.so (tests/test_subgroup_batch_host.py): the batched subgroup
-    test's digits and its plan on the CPU; test-only.  Reused when its embedded id equals the tree's,
-    as build_hostcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "subgcheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_subgcheck.so")
-    bid = subgcheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-subgcheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DSG_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
 
 
 def build_c_client(force: bool = False, verbose: bool = True) -> str:
@@ -460,7 +290,6 @@ def devblocks_build_id(build: str = "64", root: str = "") -> str:
     tests/native/devblocks* file but the sources of the curve, hash, pair, vb and ta harnesses; each of those
     hashes its own sources, the shared devblocks*.h and the product sources its units compile
     themselves (DEVBLOCKS_PRODUCT_SOURCES)."""
-    import hashlib
     root = root or ROOT
     csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
     own_src = {u[0] for units in DEVBLOCKS_OWN.values() for u in units}
@@ -469,27 +298,16 @@ def devblocks_build_id(build: str = "64", root: str = "") -> str:
         mine = [f for f in mine if f.endswith(".h")] + sorted({u[0] for u in DEVBLOCKS_OWN[build]})
     else:
         mine = [f for f in mine if f not in own_src]
-    files = [os.path.join(native, f) for f in mine] + \
-        sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h"))
+    files = [os.path.join(native, f) for f in mine] + _csrc_headers(root)
     if build in DEVBLOCKS_OWN:
         files += [os.path.join(csrc, f) for f in DEVBLOCKS_PRODUCT_SOURCES[build]]
-    h = hashlib.sha256()
-    for f in files:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
     tag = [build] if build in DEVBLOCKS_OWN else []
-    h.update(" ".join(DEVBLOCKS_FLAGS + devblocks_flags(build) + [d for u in devblocks_units(build) for d in u[1]] + tag).encode())
-    return DEVBLOCKS_PREFIX + h.hexdigest()[:16]
+    return _files_id(DEVBLOCKS_PREFIX, files, root,
+                     DEVBLOCKS_FLAGS + devblocks_flags(build) + [d for u in devblocks_units(build) for d in u[1]] + tag)
 
 
-def embedded_devblocks_id(path: str) -> str:
-    """The harness id inside a built device block harness, read from its bytes (no loading)."""
-    import re
-    with open(path, "rb") as f:
-        m = re.search(rb"hbls-devblocks:[0-9a-f]{16}", f.read())
-    return m.group(0).decode() if m else ""
+# the id inside a built device block harness, read from its bytes (no loading)
+embedded_devblocks_id = functools.partial(embedded_harness_id, name="devblocks")
 
 
 def build_devblocks(force: bool = False, verbose: bool = True, builds=None) -> dict:
@@ -541,418 +359,17 @@ def build_devblocks(force: bool = False, verbose: bool = True, builds=None) -> d
     return paths
 
 
-WIDEDEV_PREFIX = "hbls-widedev:"
+def _build_devblocks_own(which: str):
+    def build_one(force: bool = False, verbose: bool = True) -> str:
+        return build_devblocks(force, verbose, builds=[which])[which]
+    build_one.__name__ = build_one.__qualname__ = "build_devblocks_" + which
+    build_one.__doc__ = f"The {which} harness (libhbls_devblocks{which}.so), built and reused as build_devblocks' builds."
+    return build_one
 
 
-def widedev_build_id(root: str = "") -> str:
-    """The id embedded in the ladder-table device harness (tests/native/widedev.hip,
-    tests/test_gpu_key_wide.py; `wd_build_id()`): sha256 over its source, the device harnesses'
-    shared devblocks.h, every header of charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "widedev.hip"), os.path.join(native, "devblocks.h")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return WIDEDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_widedev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_widedev.so: the learned keys' ladder tables and the ladders through them
-    on the device, a harness of its own like the curve and hash harnesses (one unit, fp.h's default
-    HB_ARG_LANES); test-only.  Reused when its embedded id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "widedev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_widedev.so")
-    bid = widedev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-widedev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DWD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-SUBGDEV_PREFIX = "hbls-subgdev:"
-
-
-def subgdev_build_id(root: str = "") -> str:
-    """The id embedded in the batched subgroup test's device harness (tests/native/subgdev.hip,
-    tests/test_gpu_subgroup_batch.py; `sd_build_id()`): sha256 over its source, the device
-    harnesses' shared devblocks.h, the product source it compiles (msm.hip), every header of
-    charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "subgdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "msm.hip")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return SUBGDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_subgdev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_subgdev.so: the batched subgroup test's class sums and weighted sums on
-    the device over explicit buckets, a harness of its own like build_widedev; test-only.  Reused
-    when its embedded id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "subgdev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_subgdev.so")
-    bid = subgdev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-subgdev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DSD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-DUTYSETDEV_PREFIX = "hbls-dutysetdev:"
-
-
-def dutysetdev_build_id(root: str = "") -> str:
-    """The id embedded in the set-atomic adds' device harness (tests/native/dutysetdev.hip,
-    tests/test_gpu_duty_sets_kernels.py; `dsd_build_id()`): sha256 over its source, the device
-    harnesses' shared devblocks.h, the product source it compiles (duty.hip), every header of
-    charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "dutysetdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "duty.hip")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return DUTYSETDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_dutysetdev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_dutysetdev.so: k_duty_set_first, k_duty_gate and k_duty_store behind the
-    gate on the device over explicit words, a harness of its own like build_subgdev; test-only.
-    Reused when its embedded id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "dutysetdev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_dutysetdev.so")
-    bid = dutysetdev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-dutysetdev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DDSD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-DUTYFIRSTCHECK_PREFIX = "hbls-dutyfirstcheck:"
-DUTYFIRSTCHECK_HEADERS = ("dutyfirst.h", "hduty.h", "hslot.h", "hgroup.h", "msgtable.h")
-
-
-def dutyfirstcheck_build_id(root: str = "") -> str:
-    """The id embedded in the first-error set adds' harness (tests/native/dutyfirstcheck.cpp,
-    `df_build_id()`): sha256 over its source, the headers it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "dutyfirstcheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in DUTYFIRSTCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return DUTYFIRSTCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_dutyfirstcheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_dutyfirstcheck.so (tests/test_duty_first_host.py): the host side of
-    hbls_duty_add_sets_first on the CPU -- the set-major plan and the descent rule of the segmented
-    first-error verification; test-only.  Reused when its embedded id equals the tree's, as
-    build_dutycheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "dutyfirstcheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_dutyfirstcheck.so")
-    bid = dutyfirstcheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-dutyfirstcheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DDF_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-DUTYFIRSTDEV_PREFIX = "hbls-dutyfirstdev:"
-
-
-def dutyfirstdev_build_id(root: str = "") -> str:
-    """The id embedded in the first-error set adds' device harness (tests/native/dutyfirstdev.hip,
-    tests/test_gpu_duty_first_kernels.py; `dfd_build_id()`): sha256 over its source, the device
-    harnesses' shared devblocks.h, the product source it compiles (dutyfirst.hip), every header of
-    charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "dutyfirstdev.hip"), os.path.join(native, "devblocks.h"),
-              os.path.join(csrc, "dutyfirst.hip")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return DUTYFIRSTDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_dutyfirstdev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_dutyfirstdev.so: the kernels of the segmented first-error verification on
-    the device over explicit bytes, a harness of its own like build_dutysetdev; test-only.  Reused
-    when its embedded id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "dutyfirstdev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_dutyfirstdev.so")
-    bid = dutyfirstdev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-dutyfirstdev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DDFD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-CLUSTERCHECK_PREFIX = "hbls-clustercheck:"
-CLUSTERCHECK_HEADERS = ("cluster.h",)
-
-
-def clustercheck_build_id(root: str = "") -> str:
-    """The id embedded in the cluster handles' harness (tests/native/clustercheck.cpp,
-    `cc_build_id()`): sha256 over its source, the header it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "clustercheck.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in CLUSTERCHECK_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return CLUSTERCHECK_PREFIX + h.hexdigest()[:16]
-
-
-def build_clustercheck(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_clustercheck.so (tests/test_cluster_host.py): the key rule of a cluster
-    handle (cluster.h cluster_key) on the CPU; test-only.  Reused when its embedded id equals the
-    tree's, as build_dutysetcheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "clustercheck.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_clustercheck.so")
-    bid = clustercheck_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-clustercheck:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DCC_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-CLUSTERDEV_PREFIX = "hbls-clusterdev:"
-
-
-def clusterdev_build_id(root: str = "") -> str:
-    """The id embedded in the cluster handles' device harness (tests/native/clusterdev.hip,
-    tests/test_gpu_cluster_kernels.py; `cd_build_id()`): sha256 over its source, the device
-    harnesses' shared devblocks.h, the product source it compiles (cluster.hip), every header of
-    charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "clusterdev.hip"), os.path.join(native, "devblocks.h"), os.path.join(csrc, "cluster.hip")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return CLUSTERDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_clusterdev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_clusterdev.so: k_cluster_keys and k_cluster_wide on the device over
-    explicit words, a harness of its own like build_dutysetdev; test-only.  Reused when its embedded
-    id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "clusterdev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_clusterdev.so")
-    bid = clusterdev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-clusterdev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DCD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-LOCKCHECKHOST_PREFIX = "hbls-lockcheckhost:"
-LOCKCHECKHOST_HEADERS = ("lockcheck.h",)
-
-
-def lockcheckhost_build_id(root: str = "") -> str:
-    """The id embedded in the lock check's harness (tests/native/lockcheckhost.cpp, `lk_build_id()`):
-    sha256 over its source, the header it compiles and the flags."""
-    import hashlib
-    root = root or ROOT
-    h = hashlib.sha256()
-    for f in [os.path.join(root, "tests", "native", "lockcheckhost.cpp")] + \
-            [os.path.join(root, "charon_amd", "csrc", f) for f in LOCKCHECKHOST_HEADERS]:
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(HOSTCHECK_FLAGS).encode())
-    return LOCKCHECKHOST_PREFIX + h.hexdigest()[:16]
-
-
-def build_lockcheckhost(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_lockcheckhost.so (tests/test_lock_check_host.py): the rule of
-    hbls_cluster_check (lockcheck.h: the signed binomial coefficients, their bit length, the plan) on
-    the CPU; test-only.  Reused when its embedded id equals the tree's, as build_clustercheck."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "lockcheckhost.cpp")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_lockcheckhost.so")
-    bid = lockcheckhost_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-lockcheckhost:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    cmd = ["g++"] + HOSTCHECK_FLAGS + [f'-DLK_BUILD_ID="{bid}"', "-o", out + ".tmp", src]
-    subprocess.run(cmd, check=True, timeout=900)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out}")
-    return out
-
-
-LOCKCHECKDEV_PREFIX = "hbls-lockcheckdev:"
-
-
-def lockcheckdev_build_id(root: str = "") -> str:
-    """The id embedded in the lock check's device harness (tests/native/lockcheckdev.hip,
-    tests/test_gpu_lock_check_kernels.py; `ld_build_id()`): sha256 over its source, the device
-    harnesses' shared devblocks.h, the product source it compiles (lockcheck.hip), every header of
-    charon_amd/csrc and the flags."""
-    import hashlib
-    root = root or ROOT
-    csrc, native = os.path.join(root, "charon_amd", "csrc"), os.path.join(root, "tests", "native")
-    h = hashlib.sha256()
-    for f in [os.path.join(native, "lockcheckdev.hip"), os.path.join(native, "devblocks.h"),
-              os.path.join(csrc, "lockcheck.hip")] + \
-            sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".h")):
-        h.update(os.path.relpath(f, root).encode() + b"\0")
-        with open(f, "rb") as fh:
-            h.update(fh.read())
-        h.update(b"\0")
-    h.update(" ".join(DEVBLOCKS_FLAGS).encode())
-    return LOCKCHECKDEV_PREFIX + h.hexdigest()[:16]
-
-
-def build_lockcheckdev(force: bool = False, verbose: bool = True) -> str:
-    """tests/native/libhbls_lockcheckdev.so: k_lock_check and k_lock_fold on the device over the
-    test's keys and statuses, a harness of its own like build_clusterdev; test-only.  Reused when its
-    embedded id equals the tree's."""
-    import re
-    src = os.path.join(ROOT, "tests", "native", "lockcheckdev.hip")
-    out = os.path.join(ROOT, "tests", "native", "libhbls_lockcheckdev.so")
-    bid = lockcheckdev_build_id()
-    if not force and os.path.exists(out):
-        with open(out, "rb") as f:
-            m = re.search(rb"hbls-lockcheckdev:[0-9a-f]{16}", f.read())
-        if m and m.group(0).decode() == bid:
-            return out
-    t0 = time.time()
-    subprocess.run([HIPCC] + DEVBLOCKS_FLAGS + [f'-DLD_BUILD_ID="{bid}"', "-shared", "-o", out + ".tmp", src,
-                                                "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=3000)
-    os.replace(out + ".tmp", out)
-    if verbose:
-        print(f"built {out} in {time.time() - t0:.1f}s")
-    return out
-
-
-def build_devblocks_curve(force: bool = False, verbose: bool = True) -> str:
-    """The curve harness (tests/test_gpu_curve.py), built and reused as build_devblocks' builds."""
-    return build_devblocks(force, verbose, builds=[DEVBLOCKS_CURVE])[DEVBLOCKS_CURVE]
-
-
-def build_devblocks_hash(force: bool = False, verbose: bool = True) -> str:
-    """The hash-to-curve harness (tests/test_gpu_hash.py), built and reused as build_devblocks' builds."""
-    return build_devblocks(force, verbose, builds=[DEVBLOCKS_HASH])[DEVBLOCKS_HASH]
-
-
-def build_devblocks_pair(force: bool = False, verbose: bool = True) -> str:
-    """The pair harness (tests/test_gpu_pairing.py), built and reused as build_devblocks' builds."""
-    return build_devblocks(force, verbose, builds=[DEVBLOCKS_PAIR])[DEVBLOCKS_PAIR]
-
-
-def build_devblocks_vb(force: bool = False, verbose: bool = True) -> str:
-    """The vb harness (tests/test_gpu_vbatch.py), built and reused as build_devblocks' builds."""
-    return build_devblocks(force, verbose, builds=[DEVBLOCKS_VB])[DEVBLOCKS_VB]
-
-
-def build_devblocks_ta(force: bool = False, verbose: bool = True) -> str:
-    """The ta harness (tests/test_gpu_threshold.py), built and reused as build_devblocks' builds."""
-    return build_devblocks(force, verbose, builds=[DEVBLOCKS_TA])[DEVBLOCKS_TA]
+# build_devblocks_curve, _hash, _pair, _vb, _ta(force=False, verbose=True): one harness of DEVBLOCKS_OWN
+for _name in DEVBLOCKS_OWN:
+    globals()["build_devblocks_" + _name] = _build_devblocks_own(_name)
 
 
 def build_devblocks_all(force: bool = False, verbose: bool = True) -> dict:
@@ -989,17 +406,19 @@ def main(argv=None):
 
 
 def build_test_extras(force: bool = False, verbose: bool = True) -> list:
-    """The test-only artefacts the product does not depend on (the C client of the ABI, the device
-    block harness): a failure to build one is printed and returned, never raised."""
+    """The test-only artefacts the product does not depend on: the C client of the ABI, then the
+    table's harnesses in its order (hostcheck is the benchmark's too: its failure is raised, by the
+    callers), the device block harnesses before the first single-file device harness.  One after the
+    other; a failure to build one is printed and returned, never raised."""
+    steps = ["c_client"] + [n for n in HARNESSES if n != "hostcheck"]
+    steps.insert(steps.index("widedev"), "devblocks_all")
     failed = []
-    for fn in (build_c_client, build_widecheck, build_taselcheck, build_slothostcheck, build_dutycheck, build_subgcheck, build_devblocks_all, build_widedev,
-               build_subgdev, build_dutysetcheck, build_dutysetdev, build_dutyfirstcheck, build_dutyfirstdev,
-               build_clustercheck, build_clusterdev, build_lockcheckhost, build_lockcheckdev):
+    for fn in ("build_" + s for s in steps):
         try:
-            fn(force, verbose)
+            globals()[fn](force, verbose)
         except Exception as e:  # noqa: BLE001 -- a compiler missing, a harness that does not compile
-            print(f"WARNING: {fn.__name__} failed ({type(e).__name__}: {e}); the tests that need it will fail")
-            failed.append(fn.__name__)
+            print(f"WARNING: {fn} failed ({type(e).__name__}: {e}); the tests that need it will fail")
+            failed.append(fn)
     return failed
 
 

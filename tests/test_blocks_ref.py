@@ -14,8 +14,8 @@ from oracle import bls12381 as B
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    return ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    return harness.load("hostcheck")
 
 
 def test_lane_map_matches_hc_pairing(hc):

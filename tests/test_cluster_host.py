@@ -28,8 +28,8 @@ def cluster_key(group, share_idx, group_base, n_groups, n_shares, dv=False):
 
 @pytest.fixture(scope="module")
 def H():
-    from charon_amd.build import build_clustercheck
-    lib = ctypes.CDLL(build_clustercheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("clustercheck")
     V, SZ, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
     lib.cc_no_key.restype = U32
     lib.cc_max_shares.restype = U32

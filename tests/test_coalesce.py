@@ -9,8 +9,8 @@ import pytest
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    lib = ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("hostcheck")
     lib.hc_coalesce_stress.argtypes = [ctypes.c_int] * 5 + [ctypes.POINTER(ctypes.c_int)]
     return lib
 

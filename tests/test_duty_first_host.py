@@ -16,10 +16,8 @@ PASS, FAILED, UNCHECKED, NOT_READY = 0, 3, 0x80, 0x81
 
 @pytest.fixture(scope="module")
 def H():
-    from charon_amd.build import build_dutyfirstcheck, dutyfirstcheck_build_id
-    lib = ctypes.CDLL(build_dutyfirstcheck(verbose=False))
-    lib.df_build_id.restype = ctypes.c_char_p
-    assert lib.df_build_id().decode() == dutyfirstcheck_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("dutyfirstcheck")
     V, SZ, U32, I = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32, ctypes.c_int
     lib.df_plan.argtypes = [V, V, V, SZ, V, SZ, I, SZ, SZ, SZ, U32, SZ] + [V] * 10
     lib.df_rule.argtypes = [SZ, SZ, U32, V, V, V, U32, V, V, V, V]

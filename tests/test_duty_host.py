@@ -15,8 +15,8 @@ FEW = 1
 
 @pytest.fixture(scope="module")
 def H():
-    from charon_amd.build import build_dutycheck
-    lib = ctypes.CDLL(build_dutycheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("dutycheck")
     lib.dc_session_new.restype = ctypes.c_void_p
     lib.dc_session_new.argtypes = [ctypes.c_size_t, ctypes.c_size_t]
     lib.dc_session_free.argtypes = [ctypes.c_void_p]

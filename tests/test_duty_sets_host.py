@@ -17,8 +17,8 @@ REJECTED = 0xFF
 
 @pytest.fixture(scope="module")
 def H():
-    from charon_amd.build import build_dutysetcheck
-    lib = ctypes.CDLL(build_dutysetcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("dutysetcheck")
     V, SZ, U32 = ctypes.c_void_p, ctypes.c_size_t, ctypes.c_uint32
     lib.ds_check_sets.restype = ctypes.c_char_p
     lib.ds_check_sets.argtypes = [V, SZ, SZ]

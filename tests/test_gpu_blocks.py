@@ -10,7 +10,6 @@ representative itself, R = 2^392, any value below 2p), lazy limbs (14 x 28 bits)
 values (three Fp4Entry).  Every comparison is exact, against Python integers (tests/blocks_ref.py);
 the host harness is never the reference."""
 import ctypes
-import os
 import random
 
 import numpy as np
@@ -107,25 +106,18 @@ class Harness:
 def db(request):
     """The harness of one build, loaded only if it was built from this tree (its embedded id);
     otherwise built now, and a failure of that fails the tests."""
-    from charon_amd import build
+    from gpu_helpers import harness
     which = request.param
-    path, want = build.devblocks_path(which), build.devblocks_build_id(which)
-    if not os.path.exists(path) or build.embedded_devblocks_id(path) != want:
-        try:
-            build.build_devblocks(verbose=False)
-        except Exception as e:  # noqa: BLE001
-            pytest.fail(f"the device block harness is stale or missing and does not build: {e}")
-    lib = ctypes.CDLL(path)
+    lib = harness.load_devblocks(which)
     h = Harness(lib, int(which))
-    assert lib.db_build_id().decode() == want
     assert lib.db_arg_lanes() == int(which)
     return h
 
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    return ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    return harness.load("hostcheck")
 
 
 def _launches(cases, size, extra=(1,)):

@@ -23,10 +23,8 @@ LAM = (-B.X_PARAM ** 2) % B.R  # phi(P) = [lambda] P on G1 (rlc.h)
 
 @pytest.fixture(scope="module")
 def D(hipbls):
-    from charon_amd.build import build_clusterdev, clusterdev_build_id
-    lib = ctypes.CDLL(build_clusterdev(verbose=False))
-    lib.cd_build_id.restype = ctypes.c_char_p
-    assert lib.cd_build_id().decode() == clusterdev_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("clusterdev")
     I, V, U32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32
     lib.cd_keys.argtypes = [I, V, V, U32, U32, U32, U32, U32, V, V, I, V, V, V]
     lib.cd_wide.argtypes = [I, V, V, I, V, V]

@@ -165,17 +165,8 @@ class Curve:
 def cv():
     """The curve harness, loaded only if it was built from this tree (its embedded id); otherwise
     built now, and a failure of that fails the tests."""
-    from charon_amd import build
-    path, want = build.devblocks_path(build.DEVBLOCKS_CURVE), build.devblocks_build_id(build.DEVBLOCKS_CURVE)
-    if not os.path.exists(path) or build.embedded_devblocks_id(path) != want:
-        try:
-            build.build_devblocks_curve(verbose=False)
-        except Exception as e:  # noqa: BLE001
-            pytest.fail(f"the curve harness is stale or missing and does not build: {e}")
-    lib = ctypes.CDLL(path)
-    lib.db_build_id.restype = ctypes.c_char_p
-    assert lib.db_build_id().decode() == want
-    return Curve(lib)
+    from gpu_helpers import harness
+    return Curve(harness.load_devblocks("curve"))
 
 
 @pytest.fixture(scope="module")

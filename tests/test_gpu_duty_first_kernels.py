@@ -22,10 +22,8 @@ OK, BAD_PUBKEY, BAD_SIGNATURE, NOT_VERIFIED, UNCHECKED = 0, 1, 2, 3, 7
 
 @pytest.fixture(scope="module")
 def D(hipbls):
-    from charon_amd.build import build_dutyfirstdev, dutyfirstdev_build_id
-    lib = ctypes.CDLL(build_dutyfirstdev(verbose=False))
-    lib.dfd_build_id.restype = ctypes.c_char_p
-    assert lib.dfd_build_id().decode() == dutyfirstdev_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("dutyfirstdev")
     I, V = ctypes.c_int, ctypes.c_void_p
     lib.dfd_batch_verdict.argtypes = [I, V, V, I, I, I, V, I, I, V, V, V, V]
     lib.dfd_first_group.argtypes = [I, V, V, I, I, V]

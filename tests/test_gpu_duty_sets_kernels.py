@@ -18,10 +18,8 @@ S8, S32 = 0xA5, 0xA5A5A5A5
 
 @pytest.fixture(scope="module")
 def D(hipbls):
-    from charon_amd.build import build_dutysetdev, dutysetdev_build_id
-    lib = ctypes.CDLL(build_dutysetdev(verbose=False))
-    lib.dsd_build_id.restype = ctypes.c_char_p
-    assert lib.dsd_build_id().decode() == dutysetdev_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("dutysetdev")
     I, V = ctypes.c_int, ctypes.c_void_p
     lib.dsd_set_first.argtypes = [I, V, V, V, I, I, V]
     lib.dsd_gate.argtypes = [I, V, V, V, I, I, V]

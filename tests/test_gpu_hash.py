@@ -26,7 +26,6 @@ Ranges, derived from the code's comments:
   messages      any length; every off[i] + len[i] inside the uploaded buffer (checked on the host).
   points        Jacobian (X, Y, Z) in stored words below 2p; infinity is Z == 0 (mod p), whatever X, Y.
 """
-import ctypes
 import hashlib
 import os
 import random
@@ -64,17 +63,8 @@ def _ok(rc, what):
 def hh():
     """The hash harness, loaded only if it was built from this tree (its embedded id); otherwise built
     now, and a failure of that fails the tests."""
-    from charon_amd import build
-    path, want = build.devblocks_path(build.DEVBLOCKS_HASH), build.devblocks_build_id(build.DEVBLOCKS_HASH)
-    if not os.path.exists(path) or build.embedded_devblocks_id(path) != want:
-        try:
-            build.build_devblocks_hash(verbose=False)
-        except Exception as e:  # noqa: BLE001
-            pytest.fail(f"the hash harness is stale or missing and does not build: {e}")
-    lib = ctypes.CDLL(path)
-    lib.db_build_id.restype = ctypes.c_char_p
-    assert lib.db_build_id().decode() == want
-    return H.Hash(lib, _ok)
+    from gpu_helpers import harness
+    return H.Hash(harness.load_devblocks("hash"), _ok)
 
 
 # ---- stored words -> values ------------------------------------------------------------------

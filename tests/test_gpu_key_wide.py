@@ -250,10 +250,8 @@ def test_call_too_small_to_chunk(L):
 
 @pytest.fixture(scope="module")
 def wide_lib(hipbls):
-    from charon_amd.build import build_widedev, widedev_build_id
-    W = ctypes.CDLL(build_widedev(verbose=False))
-    W.wd_build_id.restype = ctypes.c_char_p
-    assert W.wd_build_id().decode() == widedev_build_id()
+    from gpu_helpers import harness
+    W = harness.load("widedev")
     u32p = ctypes.POINTER(ctypes.c_uint32)
     W.wd_chunks.argtypes = [ctypes.c_int, ctypes.c_char_p, u32p, ctypes.c_int, u32p, u32p, ctypes.c_char_p,
                             ctypes.c_char_p]

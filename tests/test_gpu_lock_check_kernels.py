@@ -34,10 +34,8 @@ S8, S64 = 0xA5, 0xA5A5A5A5A5A5A5A5
 
 @pytest.fixture(scope="module")
 def D(hipbls):
-    from charon_amd.build import build_lockcheckdev, lockcheckdev_build_id
-    lib = ctypes.CDLL(build_lockcheckdev(verbose=False))
-    lib.ld_build_id.restype = ctypes.c_char_p
-    assert lib.ld_build_id().decode() == lockcheckdev_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("lockcheckdev")
     I, V, U32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_uint32
     lib.ld_check.argtypes = [I, U32, U32, V, V, I, V, V, V]
     return lib

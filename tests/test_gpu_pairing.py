@@ -47,7 +47,6 @@ Which shape reaches which branch:
   k_batch_sum    k = 1 and MML_PAIRS with ng no multiple of k, one and two blocks.
 """
 import ctypes
-import os
 import random
 
 import numpy as np
@@ -221,17 +220,8 @@ class Pair:
 def pp():
     """The pair harness, loaded only if it was built from this tree (its embedded id); otherwise
     built now, and a failure of that fails the tests."""
-    from charon_amd import build
-    path, want = build.devblocks_path(build.DEVBLOCKS_PAIR), build.devblocks_build_id(build.DEVBLOCKS_PAIR)
-    if not os.path.exists(path) or build.embedded_devblocks_id(path) != want:
-        try:
-            build.build_devblocks_pair(verbose=False)
-        except Exception as e:  # noqa: BLE001
-            pytest.fail(f"the pair harness is stale or missing and does not build: {e}")
-    lib = ctypes.CDLL(path)
-    lib.db_build_id.restype = ctypes.c_char_p
-    assert lib.db_build_id().decode() == want
-    return Pair(lib)
+    from gpu_helpers import harness
+    return Pair(harness.load_devblocks("pair"))
 
 
 # ---- records ------------------------------------------------------------------------------------

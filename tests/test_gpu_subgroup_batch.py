@@ -271,10 +271,8 @@ R13 = 13 ** 4
 
 @pytest.fixture(scope="module")
 def subg_lib(hipbls):
-    from charon_amd.build import build_subgdev, subgdev_build_id
-    D = ctypes.CDLL(build_subgdev(verbose=False))
-    D.sd_build_id.restype = ctypes.c_char_p
-    assert D.sd_build_id().decode() == subgdev_build_id()
+    from gpu_helpers import harness
+    D = harness.load("subgdev")
     assert D.sd_keys() == 5 * R13
     D.sd_sums.argtypes = [ctypes.c_int, ctypes.POINTER(ctypes.c_uint32), ctypes.c_char_p, ctypes.c_char_p]
     return D

@@ -229,8 +229,8 @@ class TA:
 def ta():
     """The ta harness, loaded only if it was built from this tree (its embedded id); otherwise built now,
     and a failure of that fails the tests with the id in the message."""
-    from charon_amd import build
-    return TA(VB._load(build, build.DEVBLOCKS_TA, build.build_devblocks_ta))
+    from gpu_helpers import harness
+    return TA(harness.load_devblocks("ta"))
 
 
 @pytest.fixture(scope="module")

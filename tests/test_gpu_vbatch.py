@@ -40,7 +40,6 @@ Which shape reaches which branch:
 """
 import ctypes
 import itertools
-import os
 import random
 
 import numpy as np
@@ -104,19 +103,6 @@ def _offsets(sizes):
     for s in sizes:
         off.append(off[-1] + s)
     return off
-
-
-def _load(build, which, builder):
-    path, want = build.devblocks_path(which), build.devblocks_build_id(which)
-    if not os.path.exists(path) or build.embedded_devblocks_id(path) != want:
-        try:
-            builder(verbose=False)
-        except Exception as e:  # noqa: BLE001
-            pytest.fail(f"the {which} harness is not the tree's ({want}) and does not build: {e}")
-    lib = ctypes.CDLL(path)
-    lib.db_build_id.restype = ctypes.c_char_p
-    assert lib.db_build_id().decode() == want
-    return lib
 
 
 class VB:
@@ -237,10 +223,8 @@ def vb():
     """The vb harness and the pair harness (the verdict kernels are vgroup.hip's), each loaded only if
     it was built from this tree (its embedded id); otherwise built now, and a failure of that fails the
     tests with the id in the message."""
-    from charon_amd import build
-    lib = _load(build, build.DEVBLOCKS_VB, build.build_devblocks_vb)
-    pair = _load(build, build.DEVBLOCKS_PAIR, build.build_devblocks_pair)
-    return VB(lib, pair)
+    from gpu_helpers import harness
+    return VB(harness.load_devblocks("vb"), harness.load_devblocks("pair"))
 
 
 # ---- the world: keys k_i G1, signatures k_i Q ---------------------------------------------------

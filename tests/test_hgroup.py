@@ -25,8 +25,8 @@ U32, U64 = np.uint32, np.uint64
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    lib = ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("hostcheck")
     P, Q = ctypes.c_void_p, ctypes.c_uint64
     for name, args, res in (("hc_call_gmax", [Q, Q, Q, Q], Q), ("hc_defer_lines", [Q, Q, Q], ctypes.c_int),
                             ("hc_group_by_message", [P, Q, Q, Q, P, P, P], Q), ("hc_group_runs", [P, Q, Q, P], Q),

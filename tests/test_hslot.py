@@ -23,8 +23,8 @@ KEY_NONE = 0x10000
 
 @pytest.fixture(scope="module")
 def hs():
-    from charon_amd.build import build_slothostcheck
-    lib = ctypes.CDLL(build_slothostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("slothostcheck")
     P, U, SZ = ctypes.c_void_p, ctypes.c_uint32, ctypes.c_size_t
     lib.hs_select.argtypes, lib.hs_select.restype = [U, P, P, U, P, P, U, U, U, P, P, P], None
     lib.hs_plan_new.argtypes, lib.hs_plan_new.restype = [P, P, P, SZ, P, P, SZ, SZ, SZ], P

@@ -13,10 +13,8 @@ from oracle import bls12381 as B
 
 @pytest.fixture(scope="module")
 def lib():
-    from charon_amd.build import build_widecheck, widecheck_build_id
-    L = ctypes.CDLL(build_widecheck(verbose=False))
-    L.wc_build_id.restype = ctypes.c_char_p
-    assert L.wc_build_id().decode() == widecheck_build_id()
+    from gpu_helpers import harness
+    L = harness.load("widecheck")
     u32p = ctypes.POINTER(ctypes.c_uint32)
     L.wc_table.argtypes = [ctypes.c_char_p, ctypes.c_char_p]
     L.wc_chunk_wide.argtypes = [ctypes.c_int, ctypes.c_char_p, u32p, ctypes.c_char_p]

@@ -18,10 +18,8 @@ S64 = -0x5A5A5A5A5A5A5A5B
 
 @pytest.fixture(scope="module")
 def H():
-    from charon_amd.build import build_lockcheckhost, lockcheckhost_build_id
-    lib = ctypes.CDLL(build_lockcheckhost(verbose=False))
-    lib.lk_build_id.restype = ctypes.c_char_p
-    assert lib.lk_build_id().decode() == lockcheckhost_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("lockcheckhost")
     V, U32 = ctypes.c_void_p, ctypes.c_uint32
     lib.lk_max_t.restype = U32
     lib.lk_coeffs.argtypes = [U32, V]

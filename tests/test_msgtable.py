@@ -11,8 +11,8 @@ import pytest
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    lib = ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("hostcheck")
     lib.hc_dedup.argtypes = [ctypes.c_void_p] * 3 + [ctypes.c_size_t, ctypes.c_int, ctypes.c_void_p]
     lib.hc_dedup.restype = ctypes.c_long
     return lib

@@ -22,10 +22,8 @@ BASE, DIGITS, WINDOWS, RANGE = 13, 4, 5, 13 ** 4
 
 @pytest.fixture(scope="module")
 def S():
-    from charon_amd.build import build_subgcheck, subgcheck_build_id
-    lib = ctypes.CDLL(build_subgcheck(verbose=False))
-    lib.sg_build_id.restype = ctypes.c_char_p
-    assert lib.sg_build_id().decode() == subgcheck_build_id()
+    from gpu_helpers import harness
+    lib = harness.load("subgcheck")
     lib.sg_max_multiplicity.restype = ctypes.c_uint64
     for f in (lib.sg_window_of, lib.sg_digit_of, lib.sg_class_member_of):
         f.restype = ctypes.c_uint32
@@ -114,8 +112,8 @@ def test_plan(S):
 
 def test_plan_fields_default_off_in_the_general_harness():
     """tests/native/hostcheck.cpp fills plans without the new inputs: no batched test"""
-    from charon_amd.build import build_hostcheck
-    lib = ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("hostcheck")
     out = (ctypes.c_uint64 * 32)()
     err = ctypes.create_string_buffer(256)
     inp = (ctypes.c_uint64 * 14)(1_000_000, 100_000, 0, 1, 0, 0, 256, 0, 65536, 65536, 128, 32768, 65536, 1)

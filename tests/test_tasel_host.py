@@ -19,8 +19,8 @@ ST_OK, ST_FEW, ST_MIXED = 0, 1, 2
 
 @pytest.fixture(scope="module")
 def ts():
-    from charon_amd.build import build_taselcheck
-    lib = ctypes.CDLL(build_taselcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("taselcheck")
     P, U = ctypes.c_void_p, ctypes.c_uint32
     lib.ts_select.argtypes, lib.ts_select.restype = [P, P, U, P, P, U, U, U, P, P, P], None
     lib.ts_max.restype = lib.ts_key_none.restype = U

@@ -23,8 +23,8 @@ NO_DEFER = "verify: deferred Miller lines need the batched final exponentiation"
 
 @pytest.fixture(scope="module")
 def hc():
-    from charon_amd.build import build_hostcheck
-    lib = ctypes.CDLL(build_hostcheck(verbose=False))
+    from gpu_helpers import harness
+    lib = harness.load("hostcheck")
     lib.hc_verify_plan.argtypes = [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_char_p, ctypes.c_size_t]
     lib.hc_verify_plan.restype = ctypes.c_int
     return lib
