@@ -44,6 +44,7 @@ EXPORTS = (
     "hbls_duty_add_sets", "hbls_duty_set_stats", "hbls_duty_add_sets_first", "hbls_duty_first_stats",
     "hbls_cluster_open", "hbls_cluster_close", "hbls_cluster_stats", "hbls_duty_open_cluster",
     "hbls_cluster_check", "hbls_cluster_check_stats",
+    "hbls_cluster_verify_batch", "hbls_cluster_verify_aggregate", "hbls_cluster_verify_stats",
 )
 
 ALL_DEVICES = 0xFFFFFFFF
@@ -164,6 +165,9 @@ def _declare(lib):
         "hbls_duty_open_cluster": ([ctypes.c_uint64, U32, U32, P], ctypes.c_int),
         "hbls_cluster_check": ([ctypes.c_uint64, U32, P, P, P], ctypes.c_int),
         "hbls_cluster_check_stats": ([ctypes.c_uint64, P, SZ], ctypes.c_int),
+        "hbls_cluster_verify_batch": ([ctypes.c_uint64, P, P, P, P, P, P, SZ, P], ctypes.c_int),
+        "hbls_cluster_verify_aggregate": ([ctypes.c_uint64, ctypes.c_uint64, U32, P, P, U32, P], ctypes.c_int),
+        "hbls_cluster_verify_stats": ([ctypes.c_uint64, P, SZ], ctypes.c_int),
         "hbls_hm_entry_bytes": ([], SZ),
         "hbls_sync": ([P], ctypes.c_int),
         "hbls_status_bitmap": ([P, SZ, P, P], ctypes.c_int),

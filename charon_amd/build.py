@@ -4,6 +4,7 @@ harnesses (the HARNESSES table), the C client and the multi-unit device block ha
     python -m charon_amd.build            # product library + test harnesses
 The product library is compiled by hipcc for --offload-arch=gfx950 only.  A new single-file harness
 is a row of HARNESSES: its id, its build and its place in build_test_extras follow from the row.
+Rows added since that table's names were pinned by its test are MORE_HARNESSES, on the same terms.
 """
 
 from __future__ import annotations
@@ -108,6 +109,19 @@ HARNESSES = {
                              "the rule of hbls_cluster_check: signed binomial coefficients, their bit length, the plan"),
     "lockcheckdev": Harness(DEVICE, "LD", ALL, ("lockcheck.hip",), "k_lock_check and k_lock_fold over the test's keys"),
 }
+# Rows under the same recipe that came after tests/test_harness_table.py pinned HARNESSES' names and its
+# build order (that test also owns every source directly under tests/native): their sources are
+# tests/native/more/<name>.cpp / .hip, their outputs and ids as the table's, and build_more_harnesses
+# builds them behind build_test_extras.  tests/test_harness_more.py holds them to the table's terms.
+MORE_HARNESSES = {
+    "clusterselcheck": Harness(HOST, "CS", ("clustersel.h",), (),
+                               "the selection rule of hbls_cluster_verify_aggregate: the selected entries, the call errors"),
+    "clustersumdev": Harness(DEVICE, "CSD", ALL, ("cluster.hip",), "k_cluster_row_sum over the test's keys"),
+}
+
+
+def harness_row(name: str) -> Harness:
+    return HARNESSES[name] if name in HARNESSES else MORE_HARNESSES[name]
 
 
 def _csrc_headers(root: str) -> list:
@@ -128,7 +142,8 @@ def _files_id(prefix: str, files, root: str, flags) -> str:
 
 
 def harness_source(name: str, root: str = "") -> str:
-    return os.path.join(root or ROOT, "tests", "native", name + (".hip" if HARNESSES[name].kind == DEVICE else ".cpp"))
+    sub = () if name in HARNESSES else ("more",)
+    return os.path.join(root or ROOT, "tests", "native", *sub, name + (".hip" if harness_row(name).kind == DEVICE else ".cpp"))
 
 
 def harness_path(name: str) -> str:
@@ -140,7 +155,7 @@ def harness_build_id(name: str, root: str = "", defines=(), flags=None) -> str:
     built from this tree: over its source, for a device harness devblocks.h and its product sources,
     its csrc headers, the compiler flags (flags: another set, e.g. SANITIZED_FLAGS) and the defines."""
     root = root or ROOT
-    h, csrc = HARNESSES[name], os.path.join(root, "charon_amd", "csrc")
+    h, csrc = harness_row(name), os.path.join(root, "charon_amd", "csrc")
     files = [harness_source(name, root)]
     if h.kind == DEVICE:
         files += [os.path.join(root, "tests", "native", "devblocks.h")] + [os.path.join(csrc, f) for f in h.sources]
@@ -160,7 +175,7 @@ def build_harness(name: str, force: bool = False, verbose: bool = True, defines=
     """Build a harness of the table; test-only.  One whose embedded id equals this tree's is reused;
     any other -- a hashed file touched, other flags -- is rebuilt.  defines / out: another build of
     it (e.g. hostcheck with ("HB_HOST_MUL28",): the 28-bit host products)."""
-    h, src, out = HARNESSES[name], harness_source(name), out or harness_path(name)
+    h, src, out = harness_row(name), harness_source(name), out or harness_path(name)
     bid = harness_build_id(name, defines=defines)
     if not force and os.path.exists(out) and embedded_harness_id(out, name) == bid:
         return out
@@ -178,7 +193,7 @@ def build_harness(name: str, force: bool = False, verbose: bool = True, defines=
 
 
 # build_<name>(force=False, verbose=True) and <name>_build_id(root="") of every harness of the table
-for _name in HARNESSES:
+for _name in list(HARNESSES) + list(MORE_HARNESSES):
     globals()["build_" + _name] = functools.partial(build_harness, _name)
     globals()[_name + "_build_id"] = functools.partial(harness_build_id, _name)
 embedded_hostcheck_id = functools.partial(embedded_harness_id, name="hostcheck")
@@ -403,6 +418,7 @@ def main(argv=None):
     build_library(force)
     build_hostcheck(force)
     build_test_extras(force)
+    build_more_harnesses(force)
 
 
 def build_test_extras(force: bool = False, verbose: bool = True) -> list:
@@ -412,6 +428,15 @@ def build_test_extras(force: bool = False, verbose: bool = True) -> list:
     other; a failure to build one is printed and returned, never raised."""
     steps = ["c_client"] + [n for n in HARNESSES if n != "hostcheck"]
     steps.insert(steps.index("widedev"), "devblocks_all")
+    return _build_steps(steps, force, verbose)
+
+
+def build_more_harnesses(force: bool = False, verbose: bool = True) -> list:
+    """MORE_HARNESSES in its order, on build_test_extras' terms (it runs behind it)."""
+    return _build_steps(list(MORE_HARNESSES), force, verbose)
+
+
+def _build_steps(steps, force: bool, verbose: bool) -> list:
     failed = []
     for fn in ("build_" + s for s in steps):
         try:

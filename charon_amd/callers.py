@@ -410,6 +410,82 @@ class Cluster:
             raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
         return dict(zip(("checks", "rows_not_verified"), (int(x) for x in out)))
 
+    def verify(self, items: Sequence[Tuple[bytes, int, bytes, bytes]]) -> List[int]:
+        """hbls_cluster_verify_batch: items of (validator pubkey, key index, message, signature), each
+        verified under the lock key it names -- key index 0 the validator's DV key, j in 1 .. n its
+        pubshare of share index j -> the statuses.  A validator pubkey that is not in the cluster is sent
+        with a group at or above n_validators, so the library itself answers BAD_PUBKEY (as it does for a
+        key index that names no key).  Only reads the cluster."""
+        import ctypes
+
+        n = len(items)
+        if not n:
+            return []
+        row = {pk: g for g, pk in enumerate(self.keys)}
+        msgs = b"".join(bytes(m) for _, _, m, _ in items)
+        sigs = b"".join(bytes(s) for _, _, _, s in items)
+        if len(sigs) != 96 * n:
+            raise TblsError("cluster verify: " + _LEN_ERR)
+        group = (ctypes.c_uint32 * n)(*[row.get(pk, self.n_validators) for pk, _, _, _ in items])
+        idx = (ctypes.c_int64 * n)(*[int(j) for _, j, _, _ in items])
+        length = (ctypes.c_uint32 * n)(*[len(m) for _, _, m, _ in items])
+        off = (ctypes.c_uint64 * n)()
+        for i in range(1, n):
+            off[i] = off[i - 1] + length[i - 1]
+        st = ctypes.create_string_buffer(n)
+        if self._L.hbls_cluster_verify_batch(self.handle(), group, idx, ctypes.create_string_buffer(sigs, len(sigs)),
+                                             ctypes.create_string_buffer(msgs, max(len(msgs), 1)), off, length, n, st) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return list(st.raw[:n])
+
+    def verify_aggregate(self, signature: bytes, message: bytes, shares: Optional[Sequence[int]] = None,
+                         with_dv: bool = False) -> int:
+        """hbls_cluster_verify_aggregate: FastAggregateVerify of one signature over one message under the
+        sum of every validator's selected keys -> the status.  shares: the share indices whose pubshares
+        are selected (None: all of them); with_dv: the DV keys as well.  Only reads the cluster."""
+        import ctypes
+
+        if len(signature) != 96:
+            raise TblsError("cluster verify aggregate: " + _LEN_ERR)
+        mask = 0
+        for j in range(1, self.n_shares + 1) if shares is None else shares:
+            if j < 1 or j > 64:
+                raise TblsError("cluster verify aggregate: a share index is 1 .. 64")
+            mask |= 1 << (j - 1)
+        st = ctypes.create_string_buffer(1)
+        if self._L.hbls_cluster_verify_aggregate(self.handle(), mask, 1 if with_dv else 0,
+                                                 ctypes.create_string_buffer(bytes(signature), 96),
+                                                 ctypes.create_string_buffer(bytes(message), max(len(message), 1)),
+                                                 len(message), st) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return st.raw[0]
+
+    def verify_lock_signatures(self, signature_aggregate: bytes, lock_hash: bytes,
+                               registrations: Optional[Mapping[bytes, Tuple[bytes, bytes]]] = None) -> None:
+        """The BLS part of Lock.VerifySignatures (lock.go:151-196) on the open cluster.  First the
+        aggregate over every validator's every pubshare against the lock hash (lock.go:185), its error
+        wrapped as lock_verify_signatures wraps it; then `registrations`, {validator pubkey: (signing
+        root, signature)}, in cluster order under the DV keys (verifyBuilderRegistrations, lock.go:235-281):
+        the first failing one is raised as lock.go:190 and :274-276 wrap the tbls.Verify error."""
+        st = self.verify_aggregate(signature_aggregate, lock_hash)
+        if st != OK:
+            raise _wrap("verify lock signature aggregate", status_error("verify_aggregate", st))
+        if not registrations:
+            return
+        regs = [(pk,) + tuple(registrations[pk]) for pk in self.keys if pk in registrations]
+        for s in self.verify([(pk, 0, root, sig) for pk, root, sig in regs]):
+            if s != OK:
+                raise _wrap("verify pre-generated builder registrations", "verify builder registration signature: " + _verr(s))
+
+    def verify_stats(self) -> Dict[str, int]:
+        import ctypes
+
+        out = (ctypes.c_uint64 * 5)()
+        if self._L.hbls_cluster_verify_stats(self.handle(), out, 5) != 0:
+            raise TblsError("hipbls: " + self._L.hbls_last_error().decode(errors="replace"))
+        return dict(zip(("verify_calls", "items_resolved", "items_no_key", "aggregate_calls", "aggregate_keys"),
+                        (int(x) for x in out)))
+
     def close(self) -> None:
         """Invalidates the handle; the device memory goes with the last duty opened on the cluster."""
         if self._h is not None:

@@ -10,6 +10,7 @@
 #include "layout.h"
 #include "../../include/hipbls.h"
 #include "cluster.h"
+#include "clustersel.h"
 #include "coalesce.h"
 #include "dutysel.h"
 #include "hduty.h"
@@ -2719,17 +2720,20 @@ int verify_coalesced(const uint8_t* pks, const uint8_t* sigs, const uint8_t* msg
 // ---------------------------------------------------------------------------------------
 constexpr uint32_t VA_SEG = 32;
 
-int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* goff, size_t ng, const uint8_t* dsig,
-                const MsgEntry* hm, uint8_t* dst, hipStream_t s, const std::function<int()>& hash_fn) {
-  if (ng == 0) return 0;
-  if (np > 0xffffffffull || ng > 0x7fffffffull) return set_err("verify aggregate: too many keys");
-  // plan: boundaries of every pass, then the sum index of each group, then the identity map
-  std::vector<uint32_t> plan, lo(ng), hi(ng);
+// The reduction's plan: the segment boundaries of every pass (pass k: pass_n[k] segments from
+// plan[pass_off[k]]), then the sum index of each group (0xffffffff: an empty group), then the identity map.
+struct VaPlan {
+  std::vector<uint32_t> plan;
   std::vector<size_t> pass_off, pass_n;
+  size_t sog_off = 0, iota_off = 0;
+};
+void va_plan(const uint32_t* goff, size_t ng, size_t np, VaPlan& v) {
+  std::vector<uint32_t>& plan = v.plan;
+  std::vector<uint32_t> lo(ng), hi(ng);
   for (size_t g = 0; g < ng; g++) lo[g] = goff[g], hi[g] = goff[g + 1];
   bool more = np > 0;
   while (more) {
-    pass_off.push_back(plan.size());
+    v.pass_off.push_back(plan.size());
     plan.push_back(0);
     uint32_t out = 0;
     more = false;
@@ -2744,23 +2748,61 @@ int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* go
       hi[g] = out;
       more |= out - first > 1;
     }
-    pass_n.push_back(out);
+    v.pass_n.push_back(out);
   }
-  const size_t sog_off = plan.size();
+  v.sog_off = plan.size();
   for (size_t g = 0; g < ng; g++) plan.push_back(hi[g] > lo[g] ? lo[g] : 0xffffffffu);
-  const size_t iota_off = plan.size();
+  v.iota_off = plan.size();
   for (size_t g = 0; g < ng; g++) plan.push_back((uint32_t)g);
+}
+
+// The plan's passes on stream s0 over `in` (affine entries, or Jacobian partial sums: every pass is then
+// k_seg_sum<false>) with their flags, alternating between (sa, sta) and (sb, stb); out / out_st: where the
+// last pass left the groups' sums (sa / sta when the plan has no pass).
+int va_reduce(Dev& d, const VaPlan& v, const uint32_t* dplan, bool affine, const void* in, const uint8_t* in_st, G1JEntry* sa,
+              uint8_t* sta, G1JEntry* sb, uint8_t* stb, hipStream_t s0, G1JEntry** out, uint8_t** out_st) {
+  *out = sa;
+  *out_st = sta;
+  for (size_t k = 0; k < v.pass_n.size(); k++) {
+    *out = (k & 1) ? sb : sa;
+    *out_st = (k & 1) ? stb : sta;
+    TIMED(d, "k_seg_sum", s0,
+          launch_seg_sum(affine && k == 0, in, in_st, dplan + v.pass_off[k], (uint32_t)v.pass_n[k], *out, *out_st, s0));
+    in = *out;
+    in_st = *out_st;
+  }
+  return 0;
+}
+
+// Where va_pipeline's np summands come from: compressed public keys (hbls_verify_aggregate_batch and the
+// device entry: k_dec_pk, then an affine first pass), or Jacobian partial sums with their flags, already
+// on the device (hbls_cluster_verify_aggregate: the shards' sums of the cluster's resident keys).
+struct VaKeys {
+  const uint8_t* dpk = nullptr;
+  const G1JEntry* sums = nullptr;
+  const uint8_t* sums_st = nullptr;
+};
+
+int va_pipeline(Dev& d, Ws& w, const VaKeys& keys, size_t np, const uint32_t* goff, size_t ng, const uint8_t* dsig,
+                const MsgEntry* hm, uint8_t* dst, hipStream_t s, const std::function<int()>& hash_fn) {
+  if (ng == 0) return 0;
+  if (np > 0xffffffffull || ng > 0x7fffffffull) return set_err("verify aggregate: too many keys");
+  VaPlan v;
+  va_plan(goff, ng, np, v);
+  const std::vector<uint32_t>& plan = v.plan;
+  const std::vector<size_t>& pass_n = v.pass_n;
+  const size_t sog_off = v.sog_off, iota_off = v.iota_off;
   uint32_t* dplan;  // in the workspace set (event-ordered), copied on the call's stream
   if (wsbuf(w, W_PLAN, plan.size(), &dplan)) return -1;
   HCHK(hipMemcpyAsync(dplan, plan.data(), plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, s));
 
-  G1AEntry *pts, *vapt;
-  uint8_t *mst, *sigst, *pv, *sta, *stb;
+  G1AEntry *pts = nullptr, *vapt;
+  uint8_t *mst = nullptr, *sigst, *pv, *sta, *stb;
   HmEntry* sigpt;
   G1JEntry *sa, *sb;
   LineEntry* lines;
   const size_t na = pass_n.empty() ? 1 : pass_n[0], nb = pass_n.size() > 1 ? pass_n[1] : 1;
-  if (wsbuf(w, W_VPK, np, &pts) || wsbuf(w, W_VPKST, np, &mst) || wsbuf(w, W_VSIG, ng, &sigpt) ||
+  if ((keys.dpk && (wsbuf(w, W_VPK, np, &pts) || wsbuf(w, W_VPKST, np, &mst))) || wsbuf(w, W_VSIG, ng, &sigpt) ||
       wsbuf(w, W_VSIGST, ng, &sigst) || wsbuf(w, W_FBLINES, ng * N_LINES, &lines) || wsbuf(w, W_SEGA, na, &sa) ||
       wsbuf(w, W_SEGSTA, na, &sta) || wsbuf(w, W_SEGB, nb, &sb) || wsbuf(w, W_SEGSTB, nb, &stb) ||
       wsbuf(w, W_VAPT, ng, &vapt) || wsbuf(w, W_VAPV, ng, &pv))
@@ -2773,19 +2815,12 @@ int va_pipeline(Dev& d, Ws& w, const uint8_t* dpk, size_t np, const uint32_t* go
   TIMED(d, "k_sig_lines", s1, launch_sig_lines(sigpt, (uint32_t)ng, lines, (uint32_t)ng, s1));
   HCHK(hipEventRecord(w.ev_side[1], s1));
   if (hash_fn && hash_fn()) return -1;
-  if (np) TIMED(d, "k_dec_pk", s0, launch_dec_pk(dpk, (uint32_t)np, pts, mst, s0));
-  const void* in = pts;
-  const uint8_t* in_st = mst;
-  G1JEntry* out = sa;
-  uint8_t* out_st = sta;
-  for (size_t k = 0; k < pass_n.size(); k++) {
-    out = (k & 1) ? sb : sa;
-    out_st = (k & 1) ? stb : sta;
-    TIMED(d, "k_seg_sum", s0,
-          launch_seg_sum(k == 0, in, in_st, dplan + pass_off[k], (uint32_t)pass_n[k], out, out_st, s0));
-    in = out;
-    in_st = out_st;
-  }
+  if (keys.dpk && np) TIMED(d, "k_dec_pk", s0, launch_dec_pk(keys.dpk, (uint32_t)np, pts, mst, s0));
+  G1JEntry* out;
+  uint8_t* out_st;
+  if (va_reduce(d, v, dplan, keys.dpk != nullptr, keys.dpk ? (const void*)pts : (const void*)keys.sums,
+                keys.dpk ? mst : keys.sums_st, sa, sta, sb, stb, s0, &out, &out_st))
+    return -1;
   HCHK(hipEventRecord(w.ev_side[0], s0));
   HCHK(hipStreamWaitEvent(s, w.ev_side[0], 0));
   HCHK(hipStreamWaitEvent(s, w.ev_side[1], 0));
@@ -3170,6 +3205,7 @@ struct Cluster {
   std::vector<ClusterShard> sh;
   std::atomic<uint64_t> stats[6] = {};  // hbls_cluster_stats
   std::atomic<uint64_t> check_stats[2] = {};  // hbls_cluster_check_stats
+  std::atomic<uint64_t> verify_stats[5] = {};  // hbls_cluster_verify_stats
   ~Cluster() {
     for (ClusterShard& s : sh) {
       if (!s.d) continue;
@@ -3994,7 +4030,9 @@ int hbls_verify_aggregate_batch(const uint8_t* pks, const uint32_t* grp_off, con
     void* hmp;  // the message table's buffer (hash_table fills the same one on the call's stream)
     if (ensure_buf(h.io[I_HM], ng * sizeof(MsgEntry), &hmp)) return -1;
     MsgEntry* hm = (MsgEntry*)hmp;
-    if (va_pipeline(d, w, dpk, np, goff.data(), ng, dsig, hm, dst, h.s,
+    VaKeys keys;
+    keys.dpk = dpk;
+    if (va_pipeline(d, w, keys, np, goff.data(), ng, dsig, hm, dst, h.s,
                     [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, &h); }))
       return -1;
     if (ws_release(w, h.s)) return -1;
@@ -4442,8 +4480,9 @@ int hbls_verify_aggregate_device(const uint8_t* pks, const uint32_t* grp_off, si
   for (size_t g = 0; g <= n_groups; g++) goff[g] = grp_off[g] - grp_off[0];
   std::lock_guard<std::mutex> lk(d->mu);
   Ws& w = ws_acquire(*d, s);
-  if (va_pipeline(*d, w, pks + 48ull * grp_off[0], goff[n_groups], goff.data(), n_groups, sigs, (const MsgEntry*)hm,
-                  status, s, nullptr))
+  VaKeys keys;
+  keys.dpk = pks + 48ull * grp_off[0];
+  if (va_pipeline(*d, w, keys, goff[n_groups], goff.data(), n_groups, sigs, (const MsgEntry*)hm, status, s, nullptr))
     return -1;
   return ws_release(w, s);
 }
@@ -4896,6 +4935,284 @@ int hbls_cluster_check_stats(uint64_t cluster, uint64_t* out, size_t n) {
   if (!cl) return set_err("hbls_cluster_check_stats: no such cluster (never opened, or closed)");
   if (!out || n > 2) return set_err("hbls_cluster_check_stats: out is null or n above 2");
   for (size_t k = 0; k < n; k++) out[k] = cl->check_stats[k].load();
+  return 0;
+}
+
+// Run fn(k) for every shard of a cluster concurrently (one host thread per shard beyond one), all joined
+// before this returns; the first failing shard's error is reported with its device.
+static int cluster_each_shard(const Cluster& cl, const std::string& who, const std::function<int(size_t)>& fn) {
+  const size_t nd = cl.sh.size();
+  std::vector<int> rc(nd, 0);
+  std::vector<std::string> errs(nd);
+  auto run = [&](size_t k) {
+    rc[k] = fn(k);
+    if (rc[k]) errs[k] = g_err;
+  };
+  if (nd == 1) {
+    run(0);
+  } else {
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
+    for (auto& x : th) x.join();
+  }
+  for (size_t k = 0; k < nd; k++)
+    if (rc[k]) return set_err(who + ": device " + std::to_string(cl.sh[k].d->ord) + ": " + errs[k]);
+  return 0;
+}
+
+// What hbls_cluster_verify_batch was called with
+struct ClusterVerifyArgs {
+  const uint32_t* group;
+  const int64_t* key_idx;
+  const uint8_t *sigs, *msgs;
+  const uint64_t* msg_off;
+  const uint32_t* msg_len;
+};
+
+// One shard of hbls_cluster_verify_batch: its items (caller indices, increasing), all of groups the shard
+// owns.  Phase one of a cluster duty's add (DutyShardAdd::verify_) with a message table that lives for
+// this call only: the plan (hduty.h duty_plan_shard), the upload, the hashing of the call's distinct
+// messages, then verify_pipeline with the shard's keys by (group, key index), entry 0 allowed.  Not
+// chunked, as a duty add is not.  The statuses go to hst at the items' caller indices; complete
+// (synchronised) when it returns.  The kernels only read the cluster.
+static int cluster_verify_shard(const Cluster& cl, const ClusterShard& cs, const ClusterVerifyArgs& a,
+                                const std::vector<uint32_t>& items, size_t gmax, uint8_t* hst) {
+  const size_t m = items.size();
+  if (!m) return 0;
+  Dev& d = *cs.d;
+  HcLease hcs(d);
+  Hc& h = *hcs.h[0];
+  DutyMsgTable tab;
+  DutyShardPlan p;
+  duty_plan_shard(a.msgs, a.msg_off, a.msg_len, a.group, a.key_idx, items, cs.gb, cs.ge, 0, gmax, tab, p);
+  const size_t nm = tab.size();
+  std::vector<uint8_t> hsig(96 * m), st(m);
+  std::vector<uint32_t> hcg(m);
+  std::vector<int64_t> hci(m);
+  for (size_t q = 0; q < m; q++) {
+    hcg[q] = a.group[p.order[q]];
+    hci[q] = a.key_idx[p.order[q]];
+    memcpy(&hsig[96 * q], a.sigs + 96ull * p.order[q], 96);
+  }
+  std::unique_lock<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  hipStream_t s = h.s;
+  uint8_t *dsig, *dmsg;
+  uint64_t* doff;
+  uint32_t *dlen, *dmidx, *dvgoff, *dcg;
+  int64_t* dci;
+  void *pst, *phm;
+  if (upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
+  PinnedUploads up;
+  up.add(I_DCGRP, hcg.data(), m, &dcg);
+  up.add(I_DCSHARE, hci.data(), m, &dci);
+  up.add(I_MSG, tab.t.bytes.data(), tab.t.bytes.size(), &dmsg);
+  up.add(I_OFF, tab.t.off.data(), nm, &doff);
+  up.add(I_LEN, tab.t.len.data(), nm, &dlen);
+  up.add(I_MIDX, p.midx.data(), m, &dmidx);
+  up.add(I_VGOFF, p.vgoff.data(), p.vgoff.size(), &dvgoff);
+  if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_HM], nm * sizeof(MsgEntry), &phm))
+    return -1;
+  MsgEntry* hm = (MsgEntry*)phm;
+  Ws& w = ws_acquire(d, s);
+  // the table is the call's own, so its lines are deferred where a host Verify defers them (verify_host)
+  const bool defer = defer_lines(p.n_vgroups(), nm);
+  if (hash_range(d, w, s, dmsg, doff, dlen, hm, 0, nm, !defer)) return -1;
+  VerifyCall vc;
+  vc.h_ready = w.ev_h;
+  vc.defer_hm = hm;
+  vc.defer_msgs = defer ? nm : 0;
+  vc.sigs = dsig;
+  vc.msg_idx = dmidx;
+  vc.hm = hm;
+  vc.n = m;
+  vc.grp_off = dvgoff;
+  vc.n_groups = p.n_vgroups();
+  vc.status = (uint8_t*)pst;
+  vc.s = s;
+  vc.device_entry = true;
+  vc.hm_ready = w.ev_side[2];
+  ClusterKeysArgs ck{};
+  ck.group = dcg;
+  ck.share_idx = dci;
+  ck.group_base = (uint32_t)cs.gb;
+  ck.n_groups = (uint32_t)(cs.ge - cs.gb);
+  ck.n_shares = cl.n_shares;
+  ck.n_keys = (uint32_t)cs.n_keys;
+  ck.any_entry = 1;
+  ck.ent = cs.ent;
+  ck.st = cs.st;
+  vc.cluster = &ck;
+  vc.cluster_wide = cs.wide;
+  if (verify_pipeline(d, w, vc)) return -1;
+  HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  if (ws_release(w, s)) return -1;
+  lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+  HCHK(hipMemcpyAsync(st.data(), pst, m, hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  for (size_t q = 0; q < m; q++) hst[p.order[q]] = st[q];
+  return 0;
+}
+
+int hbls_cluster_verify_batch(uint64_t cluster, const uint32_t* group, const int64_t* key_idx, const uint8_t* sigs,
+                              const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                              uint8_t* status) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_verify_batch: no such cluster (never opened, or closed)");
+  if (n >= 0xffffffffull) return set_err("hbls_cluster_verify_batch: too many items");
+  if (n && (!group || !key_idx || !sigs || !msg_off || !msg_len || !status))
+    return set_err("hbls_cluster_verify_batch: group, key_idx, sigs, msg_off, msg_len and status are required");
+  if (n && !msgs)
+    for (size_t i = 0; i < n; i++)
+      if (msg_len[i]) return set_err("hbls_cluster_verify_batch: msgs is required (an item has a message of non-zero length)");
+  // an item goes to the shard that owns its group; one that names no validator needs no device
+  const size_t nd = cl->sh.size();
+  std::vector<std::vector<uint32_t>> items(nd);
+  std::vector<uint8_t> hst(n, (uint8_t)ST_BAD_PUBKEY);
+  uint64_t named = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (group[i] >= cl->n_validators) continue;
+    const size_t k = duty_shard_of_group(group[i], cl->n_validators, nd);
+    items[k].push_back((uint32_t)i);
+    const ClusterShard& s = cl->sh[k];
+    named += cluster_key(group[i], key_idx[i], (uint32_t)s.gb, (uint32_t)(s.ge - s.gb), cl->n_shares, true) != CLUSTER_NO_KEY;
+  }
+  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
+  const ClusterVerifyArgs a{group, key_idx, sigs, msgs, msg_off, msg_len};
+  if (n && cluster_each_shard(*cl, "hbls_cluster_verify_batch",
+                              [&](size_t k) { return cluster_verify_shard(*cl, cl->sh[k], a, items[k], gmax, hst.data()); }))
+    return -1;
+  // the caller's array is written once every shard has succeeded; a failed call counts nothing
+  if (n) memcpy(status, hst.data(), n);
+  cl->verify_stats[0] += 1;
+  cl->verify_stats[1] += named;
+  cl->verify_stats[2] += n - named;
+  return 0;
+}
+
+// One shard of hbls_cluster_verify_aggregate, on its library stream: k_cluster_row_sum over the shard's
+// own rows, then the k_seg_sum<false> passes of one group down to one Jacobian point and one flag, which
+// come to the host (sum: 144 bytes); complete (synchronised) when it returns.  The kernels only read the
+// cluster.  What it allocates goes when it returns, whatever it returns.
+static int cluster_sum_shard(const Cluster& cl, const ClusterShard& s, uint64_t share_mask, uint32_t with_dv, G1JEntry* sum,
+                             uint8_t* flag) {
+  const size_t ng = s.ge - s.gb;
+  if (!ng) return 0;
+  Dev& d = *s.d;
+  const uint32_t goff[2] = {0, (uint32_t)ng};
+  VaPlan v;
+  va_plan(goff, 1, ng, v);
+  const size_t na = v.pass_n[0], nb = v.pass_n.size() > 1 ? v.pass_n[1] : 1;
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  struct Bufs {
+    void* p[7] = {};
+    ~Bufs() {
+      for (void* q : p)
+        if (q) (void)hipFree(q);
+    }
+  } b;
+  HCHK(hipMalloc(&b.p[0], ng * sizeof(G1JEntry)));
+  HCHK(hipMalloc(&b.p[1], ng));
+  HCHK(hipMalloc(&b.p[2], na * sizeof(G1JEntry)));
+  HCHK(hipMalloc(&b.p[3], na));
+  HCHK(hipMalloc(&b.p[4], nb * sizeof(G1JEntry)));
+  HCHK(hipMalloc(&b.p[5], nb));
+  HCHK(hipMalloc(&b.p[6], v.plan.size() * sizeof(uint32_t)));
+  HCHK(hipMemcpyAsync(b.p[6], v.plan.data(), v.plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  TIMED(d, "k_cluster_row_sum", d.stream,
+        launch_cluster_row_sum(s.ent, s.st, (uint32_t)ng, cl.n_shares, share_mask, with_dv, (G1JEntry*)b.p[0], (uint8_t*)b.p[1],
+                               d.stream));
+  G1JEntry* out;
+  uint8_t* out_st;
+  if (va_reduce(d, v, (const uint32_t*)b.p[6], false, b.p[0], (const uint8_t*)b.p[1], (G1JEntry*)b.p[2], (uint8_t*)b.p[3],
+                (G1JEntry*)b.p[4], (uint8_t*)b.p[5], d.stream, &out, &out_st))
+    return -1;
+  HCHK(hipMemcpyAsync(sum, out, sizeof(G1JEntry), hipMemcpyDeviceToHost, d.stream));  // the one group's sum: index 0
+  HCHK(hipMemcpyAsync(flag, out_st, 1, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));
+  return 0;
+}
+
+int hbls_cluster_verify_aggregate(uint64_t cluster, uint64_t share_mask, uint32_t with_dv, const uint8_t* sig,
+                                  const uint8_t* msg, uint32_t msg_len, uint8_t* status) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_verify_aggregate: no such cluster (never opened, or closed)");
+  if (!cluster_sel_valid(share_mask, with_dv, cl->n_shares))
+    return set_err("hbls_cluster_verify_aggregate: share_mask has a bit at or above the cluster's n_shares (" +
+                   std::to_string(cl->n_shares) + "), or with_dv is above 1");
+  if (!sig || !status || (msg_len && !msg)) return set_err("hbls_cluster_verify_aggregate: sig, status and msg are required");
+  // per shard: its rows' selected keys down to one point and one flag (an empty selection sums nothing)
+  const size_t nd = cl->sh.size();
+  const uint32_t per_row = cluster_sel_count(share_mask, with_dv);
+  std::vector<G1JEntry> hsum(nd);
+  std::vector<uint8_t> hflag(nd, 0);
+  if (per_row && cluster_each_shard(*cl, "hbls_cluster_verify_aggregate", [&](size_t k) {
+        return cluster_sum_shard(*cl, cl->sh[k], share_mask, with_dv, &hsum[k], &hflag[k]);
+      }))
+    return -1;
+  // across the shards: their points and flags, packed, to the first non-empty shard's device -- one more
+  // k_seg_sum<false> pass there (va_pipeline over Jacobian sums), then FastAggregateVerify's tail
+  std::vector<G1JEntry> sums;
+  std::vector<uint8_t> flags;
+  const ClusterShard* first = nullptr;
+  for (size_t k = 0; k < nd; k++) {
+    const ClusterShard& s = cl->sh[k];
+    if (s.ge == s.gb) continue;
+    if (!first) first = &s;
+    if (per_row) {
+      sums.push_back(hsum[k]);
+      flags.push_back(hflag[k]);
+    }
+  }
+  if (!first) first = &cl->sh[0];  // a cluster of no validator: the empty group on the first device
+  Dev& d = *first->d;
+  const size_t np = sums.size();
+  const uint32_t goff[2] = {0, (uint32_t)np};
+  MsgTable t;
+  t.idx.resize(1);
+  t.off.push_back(0);
+  t.len.push_back(msg_len);
+  t.bytes.assign(msg, msg + msg_len);
+  uint8_t st = 0;
+  {
+    HcLease hcs(d);
+    Hc& h = *hcs.h[0];
+    std::unique_lock<std::mutex> lk(d.mu);
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    G1JEntry* dsums;
+    uint8_t *dflags, *dsig;
+    void *pst, *hmp;
+    if (upload(d, I_OUT, sums.data(), np, &dsums, &h) || upload(d, I_HM2, flags.data(), np, &dflags, &h) ||
+        upload(d, I_SIG, sig, (size_t)96, &dsig, &h) || ensure_buf(h.io[I_STAT], 1, &pst) ||
+        ensure_buf(h.io[I_HM], sizeof(MsgEntry), &hmp))
+      return -1;
+    Ws& w = ws_acquire(d, h.s);
+    VaKeys keys;
+    keys.sums = dsums;
+    keys.sums_st = dflags;
+    if (va_pipeline(d, w, keys, np, goff, 1, dsig, (MsgEntry*)hmp, (uint8_t*)pst, h.s,
+                    [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, &h); }))
+      return -1;
+    if (ws_release(w, h.s)) return -1;
+    lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+    HCHK(hipMemcpyAsync(&st, pst, 1, hipMemcpyDeviceToHost, h.s));
+    HCHK(hipStreamSynchronize(h.s));
+  }
+  *status = st;
+  cl->verify_stats[3] += 1;
+  cl->verify_stats[4] += (uint64_t)per_row * cl->n_validators;
+  return 0;
+}
+
+int hbls_cluster_verify_stats(uint64_t cluster, uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_find(cluster);
+  if (!cl) return set_err("hbls_cluster_verify_stats: no such cluster (never opened, or closed)");
+  if (!out || n > 5) return set_err("hbls_cluster_verify_stats: out is null or n above 5");
+  for (size_t k = 0; k < n; k++) out[k] = cl->verify_stats[k].load();
   return 0;
 }
 

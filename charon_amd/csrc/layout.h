@@ -230,6 +230,9 @@ struct ClusterKeysArgs {
   const int64_t* share_idx;  // per item: the share index it names; null: the DV key of each group
   uint32_t n;
   uint32_t group_base, n_groups, n_shares, n_keys, tables;
+  // hbls_cluster_verify_batch: an item's index may be 0, its validator's DV key (cluster_key's dv with the
+  // item's own index).  0 on the duty paths: a duty partial that names share 0 has no key.
+  uint32_t any_entry;
   const G1AEntry* ent;
   const uint8_t* st;
   // out, per item: the key phase's entry and status, and (went nullable) the key's number when it has a
@@ -241,6 +244,10 @@ struct ClusterKeysArgs {
 void launch_cluster_keys(const ClusterKeysArgs& a, hipStream_t s);
 // the ladder tables of the good, finite ones of n keys, key i's at wide[15 i ..]
 void launch_cluster_wide(const G1AEntry* ent, const uint8_t* st, uint32_t n, G1WidePt* wide, hipStream_t s);
+// hbls_cluster_verify_aggregate (k_cluster_row_sum; the rule is clustersel.h's): per row of 1 + n_shares
+// resident entries the sum of its selected ones (Jacobian) and the OR of their statuses, read-only
+void launch_cluster_row_sum(const G1AEntry* ent, const uint8_t* st, uint32_t n_rows, uint32_t n_shares, uint64_t share_mask,
+                            uint32_t with_dv, G1JEntry* out, uint8_t* st_out, hipStream_t s);
 
 // hbls_cluster_check (lockcheck.hip k_lock_check / k_lock_fold; the rule and the plan are lockcheck.h's)
 // over one shard's n_rows rows of 1 + plan.n_shares resident entries with their statuses, read-only.

@@ -567,6 +567,41 @@ int hbls_duty_first_stats(uint64_t duty, uint64_t* out, size_t n);
  *   and writes nothing.
  * hbls_cluster_check_stats (n <= 2; counted on the host): out[0] checks that returned 0, out[1] rows
  *   those checks reported HBLS_NOT_VERIFIED.
+ * Cluster verifies: anything signed by a key of the lock is verified by naming the key, not by sending it
+ *   (cluster/lock.go:185 and :235-281 at every start, dkg/dkg.go:595, :684, :864, :948, the validator
+ *   API's own partials, exits under DV keys and pubshares).  Neither call reads or writes the learned key
+ *   cache, the host public-key cache or the decompressed-signature cache; both only read the cluster, are
+ *   blocking and thread-safe, and may run beside any duty or call on it, changing nothing those return.
+ * hbls_cluster_verify_batch: hbls_verify_batch whose keys come from the lock.  Item i is verified under
+ *   the key (group[i], key_idx[i]) names: key_idx 0 the validator's DV key, key_idx j in 1..n_shares its
+ *   pubshare of share index j.  An item that names no key -- group[i] >= n_validators, or a key_idx that
+ *   is negative, above n_shares, 2^32 + 1 or INT64_MIN: every comparison is on the full 64 bits -- gets
+ *   HBLS_BAD_PUBKEY.  The keys' ladder tables are used where the cluster has them.
+ *   DEFINING PROPERTY (the twin).  For any cluster and any call, status equals what hbls_verify_batch
+ *   writes for the same sigs and messages with pks[i] = the lock's 48 bytes for the named key, or 48 zero
+ *   bytes where the pair names no key.
+ *   Items go to the shard that owns their group (items that name no validator need no device).  One
+ *   shard's part of a call is one verification: it is not chunked, as a duty add is not.  n == 0 is valid
+ *   and writes nothing; an unknown handle or a NULL group, key_idx, sigs, msg_off, msg_len or status with
+ *   n > 0 (or NULL msgs with a message of non-zero length) is a call error that writes nothing.
+ * hbls_cluster_verify_aggregate: FastAggregateVerify of one signature over one message under the sum of
+ *   the selected keys of every row.  Bit j - 1 of share_mask selects the pubshare of share index j,
+ *   with_dv (0 or 1) the DV key; lock.go:185 and dkg.go:595 are every share and no DV key.
+ *   DEFINING PROPERTY (the twin).  *status equals what hbls_verify_aggregate_batch writes for one group
+ *   holding the selected keys' 48-byte forms in row-major order, the same signature and the same
+ *   message -- herumi's order of checks included: the signature's decoding first (HBLS_BAD_SIGNATURE),
+ *   then a selected key with a non-zero key_status (HBLS_BAD_PUBKEY), then "an empty group or an identity
+ *   signature never verifies" (HBLS_NOT_VERIFIED), then the pairing.  A selected key at infinity with
+ *   status 0 is the identity in the sum; an unselected bad key does not matter.
+ *   Call errors (-1, nothing written): a mask bit at or above n_shares, with_dv > 1, a NULL sig or status,
+ *   a NULL msg with msg_len > 0, an unknown handle.
+ *   Per shard, on its device, the selected entries of every row are summed straight from the resident
+ *   table (nothing is decompressed or copied out) and reduced to one point and one flag; these go through
+ *   the host to the first non-empty shard's device, where one more reduction pass and the tail of
+ *   hbls_verify_aggregate_batch run.
+ * hbls_cluster_verify_stats (n <= 5; counted on the host, for calls that returned 0): out[0] verify-batch
+ *   calls, out[1] items resolved to a key, out[2] items that named no key, out[3] aggregate calls, out[4]
+ *   keys summed by aggregate calls.  hbls_cluster_stats and hbls_cluster_check_stats are not touched.
  * Not covered: hbls_slot_select_batch and the device entry points take no cluster. */
 int hbls_cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_validators, uint32_t n_shares,
                       uint32_t ladder_tables, uint8_t* key_status, uint64_t* cluster);
@@ -576,6 +611,12 @@ int hbls_duty_open_cluster(uint64_t cluster, uint32_t threshold, uint32_t max_st
 int hbls_cluster_check(uint64_t cluster, uint32_t threshold, uint8_t* row_status, uint64_t* row_windows,
                        size_t* n_bad);
 int hbls_cluster_check_stats(uint64_t cluster, uint64_t* out, size_t n);
+int hbls_cluster_verify_batch(uint64_t cluster, const uint32_t* group, const int64_t* key_idx, const uint8_t* sigs,
+                              const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
+                              uint8_t* status);
+int hbls_cluster_verify_aggregate(uint64_t cluster, uint64_t share_mask, uint32_t with_dv, const uint8_t* sig,
+                                  const uint8_t* msg, uint32_t msg_len, uint8_t* status);
+int hbls_cluster_verify_stats(uint64_t cluster, uint64_t* out, size_t n);
 /* Bytes of the `hm` table entry per message. */
 size_t hbls_hm_entry_bytes(void);
 /* Measurement: with timing enabled (which also resets the record), every kernel launch of the
