@@ -23,6 +23,7 @@
 #include <sys/random.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <condition_variable>
@@ -315,6 +316,24 @@ std::atomic<size_t> g_single_max{SINGLE_MAX_DEFAULT};
 struct DevBuf {
   void* p = nullptr;
   size_t cap = 0;
+};
+
+// hipMalloc'ed buffers that go when this does.  Like every hipMalloc and hipFree of the handle layer it
+// lives under the device lock, with the device current: declare it behind the lock guard.
+struct DevBufs {
+  std::vector<void*> p;
+  DevBufs(std::initializer_list<void*> own = {}) : p(own) {}  // own: takes over what was allocated elsewhere
+  DevBufs(const DevBufs&) = delete;
+  ~DevBufs() {
+    for (void* q : p)
+      if (q) (void)hipFree(q);
+  }
+  template <class T>
+  int alloc(T** out, size_t bytes) {
+    HCHK(hipMalloc((void**)out, bytes));
+    p.push_back(*out);
+    return 0;
+  }
 };
 
 // workspace buffers of one set
@@ -2011,6 +2030,44 @@ struct HcLease {
   }
 };
 
+// The shard runner of every call that works per shard (fan_out_k, duty_add, the cluster calls): fn(k) for
+// every k < nd, on the calling thread when nd == 1 and otherwise on one host thread per shard, all joined
+// before this returns.  Returns the first failing k with that thread's error text in *err, or nd.
+size_t run_shards(size_t nd, const std::function<int(size_t)>& fn, std::string* err) {
+  std::vector<int> rc(nd, 0);
+  std::vector<std::string> errs(nd);
+  auto run = [&](size_t k) {
+    rc[k] = fn(k);
+    if (rc[k]) errs[k] = g_err;
+  };
+  if (nd == 1) {
+    run(0);
+  } else {
+    std::vector<std::thread> th;
+    for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
+    for (auto& t : th) t.join();
+  }
+  for (size_t k = 0; k < nd; k++)
+    if (rc[k]) {
+      *err = errs[k];
+      return k;
+    }
+  return nd;
+}
+
+// A failing shard's error, reported with its device: "who: device N: err" ("device N: err" without a who)
+int shard_err(const std::string& who, const Dev& d, const std::string& err) {
+  return set_err((who.empty() ? "" : who + ": ") + "device " + std::to_string(d.ord) + ": " + err);
+}
+
+// run_shards over the shards of a handle (a duty's, a cluster's), the first failing shard's error reported with its device
+template <class Shard>
+int each_shard(const std::string& who, const std::vector<Shard>& sh, const std::function<int(size_t)>& fn) {
+  std::string err;
+  const size_t bad = run_shards(sh.size(), fn, &err);
+  return bad == sh.size() ? 0 : shard_err(who, *sh[bad].d, err);
+}
+
 // Run fn(dev, shard) for each device's shard of n_units concurrently (one host thread per extra
 // device); a failing shard's error is reported with its device.  fn locks the device itself.
 // fan_out_k: fn also learns which shard it runs, k of nd.
@@ -2020,20 +2077,9 @@ int fan_out_k(size_t n_units, const ShardKFn& fn) {
   const std::vector<Dev*> ds = devs();
   const size_t nd = std::min(ds.size(), std::max<size_t>(n_units, 1));
   if (nd <= 1) return fn(*ds[0], 0, 1, 0, n_units);
-  std::vector<int> rc(nd, 0);
-  std::vector<std::string> errs(nd);
-  std::vector<std::thread> th;
-  for (size_t k = 0; k < nd; k++) {
-    const size_t b = n_units * k / nd, e = n_units * (k + 1) / nd;
-    th.emplace_back([&, k, b, e]() {
-      rc[k] = fn(*ds[k], k, nd, b, e);
-      if (rc[k]) errs[k] = g_err;
-    });
-  }
-  for (auto& t : th) t.join();
-  for (size_t k = 0; k < nd; k++)
-    if (rc[k]) return set_err("device " + std::to_string(ds[k]->ord) + ": " + errs[k]);
-  return 0;
+  std::string err;
+  const size_t bad = run_shards(nd, [&](size_t k) { return fn(*ds[k], k, nd, n_units * k / nd, n_units * (k + 1) / nd); }, &err);
+  return bad == nd ? 0 : shard_err("", *ds[bad], err);
 }
 int fan_out(size_t n_units, const ShardFn& fn) {
   return fan_out_k(n_units, [&fn](Dev& d, size_t, size_t, size_t b, size_t e) -> int { return fn(d, b, e); });
@@ -3211,14 +3257,420 @@ struct Cluster {
       if (!s.d) continue;
       std::lock_guard<std::mutex> lk(s.d->mu);
       if (hipSetDevice(s.d->ord) != hipSuccess) continue;
-      for (void* p : {(void*)s.ent, (void*)s.st, (void*)s.wide})
-        if (p) (void)hipFree(p);
+      DevBufs own({s.ent, s.st, s.wide});  // freed at the end of this round, under lk
     }
   }
 };
-std::mutex g_cluster_mu;
-std::unordered_map<uint64_t, std::shared_ptr<Cluster>> g_clusters;
-uint64_t g_cluster_next = 1;
+
+// The open handles of one kind (duties, clusters): numbered from 1, a number never issued twice
+template <class T>
+struct HandleTable {
+  std::mutex mu;
+  std::unordered_map<uint64_t, std::shared_ptr<T>> map;
+  uint64_t next = 1;
+  uint64_t add(std::shared_ptr<T> p) {
+    std::lock_guard<std::mutex> l(mu);
+    map[next] = std::move(p);
+    return next++;
+  }
+  std::shared_ptr<T> find(uint64_t handle, bool erase = false) {
+    std::lock_guard<std::mutex> l(mu);
+    auto it = map.find(handle);
+    if (it == map.end()) return nullptr;
+    std::shared_ptr<T> p = it->second;
+    if (erase) map.erase(it);
+    return p;
+  }
+  std::shared_ptr<T> take(uint64_t handle) { return find(handle, true); }  // found: no longer a handle
+};
+HandleTable<Cluster> g_clusters;
+
+// take: hbls_cluster_close (the handle's last use)
+std::shared_ptr<Cluster> cluster_get(const std::string& who, uint64_t handle, bool take = false) {
+  std::shared_ptr<Cluster> cl = take ? g_clusters.take(handle) : g_clusters.find(handle);
+  if (!cl) set_err(who + ": no such cluster (never opened, or closed)");
+  return cl;
+}
+
+// The shard's keys for k_cluster_keys over items named by group and share index, device arrays (share_idx
+// null: the groups' DV keys); any_entry: index 0 names the DV key (cluster.h cluster_key)
+ClusterKeysArgs cluster_keys_args(const ClusterShard& cs, uint32_t n_shares, const uint32_t* group, const int64_t* share_idx,
+                                  bool any_entry) {
+  ClusterKeysArgs ck{};
+  ck.group = group;
+  ck.share_idx = share_idx;
+  ck.group_base = (uint32_t)cs.gb;
+  ck.n_groups = (uint32_t)(cs.ge - cs.gb);
+  ck.n_shares = n_shares;
+  ck.n_keys = (uint32_t)cs.n_keys;
+  ck.any_entry = any_entry ? 1 : 0;
+  ck.ent = cs.ent;
+  ck.st = cs.st;
+  return ck;
+}
+
+// A shard's items as its plan orders them, like everything the verification reads per item: their signatures
+// and, where the keys are a cluster's (group non-null), the groups and key indices that name them
+void gather_plan_order(const std::vector<uint32_t>& order, const uint32_t* group, const int64_t* key_idx, const uint8_t* sigs,
+                       std::vector<uint32_t>& hcg, std::vector<int64_t>& hci, std::vector<uint8_t>& hsig) {
+  const size_t m = order.size();
+  hcg.resize(group ? m : 0);
+  hci.resize(group ? m : 0);
+  hsig.resize(96 * m);
+  for (size_t q = 0; q < m; q++) {
+    if (group) {
+      hcg[q] = group[order[q]];
+      hci[q] = key_idx[order[q]];
+    }
+    memcpy(&hsig[96 * q], sigs + 96ull * order[q], 96);
+  }
+}
+
+// msgs may be null only where no item has a message of non-zero length
+bool msgs_missing(const uint8_t* msgs, const uint32_t* msg_len, size_t n) {
+  if (msgs) return false;
+  for (size_t i = 0; i < n; i++)
+    if (msg_len[i]) return true;
+  return false;
+}
+
+// The stats calls of a handle read the first n of one of its N counters: the check of out and n, and the copy
+// (a cluster's counters are atomic; a duty's are plain, copied under its lock)
+int counters_args(const std::string& who, const uint64_t* out, size_t n, size_t N) {
+  return !out || n > N ? set_err(who + ": out is null or n above " + std::to_string(N)) : 0;
+}
+template <class C>
+void counters_copy(const C* stats, uint64_t* out, size_t n) {
+  for (size_t k = 0; k < n; k++) out[k] = stats[k];
+}
+
+// hbls_cluster_stats, hbls_cluster_check_stats and hbls_cluster_verify_stats
+template <size_t N>
+int cluster_counters(const std::string& who, uint64_t cluster, std::atomic<uint64_t> (Cluster::*ctr)[N], uint64_t* out, size_t n) {
+  if (ensure_init()) return -1;
+  std::shared_ptr<Cluster> cl = cluster_get(who, cluster);
+  if (!cl || counters_args(who, out, n, N)) return -1;
+  counters_copy((*cl).*ctr, out, n);
+  return 0;
+}
+
+// One shard of hbls_cluster_open: its rows' compressed keys up, the decompression and membership test of
+// hbls_decompress_pubkeys_device into the resident table, the ladder tables, the statuses back; complete
+// (synchronised) when it returns.  What it allocates for the cluster stays in s (on failure too: it goes
+// with the cluster); its staging buffer goes when it returns, under the lock it holds.
+int cluster_fill_shard(ClusterShard& s, const uint8_t* dv_pks, const uint8_t* pubshares, uint32_t n_shares, bool tables,
+                       uint8_t* hst) {
+  Dev& d = *s.d;
+  const size_t ng = s.ge - s.gb, row = 1 + (size_t)n_shares, nk = ng * row;
+  s.n_keys = nk;
+  if (!nk) return 0;
+  std::vector<uint8_t> keys(48 * nk);
+  for (size_t g = 0; g < ng; g++) {
+    memcpy(&keys[48 * g * row], dv_pks + 48 * (s.gb + g), 48);
+    memcpy(&keys[48 * (g * row + 1)], pubshares + 48 * (s.gb + g) * n_shares, 48 * (size_t)n_shares);
+  }
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  DevBufs staging;
+  uint8_t* tmp;
+  HCHK(hipMalloc((void**)&s.ent, nk * sizeof(G1AEntry)));
+  HCHK(hipMalloc((void**)&s.st, nk));
+  if (tables) HCHK(hipMalloc((void**)&s.wide, nk * KEY_WIDE_PTS * sizeof(G1WidePt)));
+  if (staging.alloc(&tmp, 48 * nk)) return -1;
+  HCHK(hipMemcpyAsync(tmp, keys.data(), 48 * nk, hipMemcpyHostToDevice, d.stream));
+  TIMED(d, "k_dec_pk", d.stream, launch_dec_pk(tmp, (uint32_t)nk, s.ent, s.st, d.stream));
+  if (tables) TIMED(d, "k_cluster_wide", d.stream, launch_cluster_wide(s.ent, s.st, (uint32_t)nk, s.wide, d.stream));
+  HCHK(hipMemcpyAsync(hst, s.st, nk, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));  // complete before any stream's kernel reads them: the cluster is immutable from here
+  return 0;
+}
+
+// A checked hbls_cluster_open: the shards one after the other, then the handle
+int cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_validators, uint32_t n_shares, bool tables,
+                 uint8_t* key_status, uint64_t* handle) {
+  auto cl = std::make_shared<Cluster>();  // (whatever a failing shard leaves allocated goes with it: nothing stays)
+  cl->n_validators = n_validators;
+  cl->n_shares = n_shares;
+  cl->tables = tables;
+  const std::vector<Dev*> ds = devs();
+  const size_t nd = slot_shards(ds.size(), n_validators), row = 1 + (size_t)n_shares;
+  cl->sh.resize(nd);
+  std::vector<uint8_t> hst(n_validators * row);
+  for (size_t k = 0; k < nd; k++) {
+    ClusterShard& s = cl->sh[k];
+    s.d = ds[k];
+    s.gb = n_validators * k / nd;
+    s.ge = n_validators * (k + 1) / nd;
+    if (cluster_fill_shard(s, dv_pks, pubshares, n_shares, tables, hst.data() + s.gb * row))
+      return shard_err("hbls_cluster_open", *s.d, g_err);
+  }
+  uint64_t bad = 0, built = 0;
+  for (size_t g = 0; g < n_validators; g++)
+    for (size_t j = 0; j < row; j++) {
+      const uint8_t st = hst[g * row + j];
+      const uint8_t* key = j ? pubshares + 48 * (g * n_shares + j - 1) : dv_pks + 48 * g;
+      bad += st ? 1 : 0;
+      built += (tables && !st && !(key[0] & 0x40)) ? 1 : 0;  // good and finite (the compressed form's infinity bit)
+    }
+  if (key_status && !hst.empty()) memcpy(key_status, hst.data(), hst.size());
+  cl->stats[0] = hst.size();
+  cl->stats[1] = bad;
+  cl->stats[2] = built;
+  *handle = g_clusters.add(cl);
+  return 0;
+}
+
+// One shard of hbls_cluster_check: k_lock_check and k_lock_fold over the shard's own rows on its library
+// stream, the rows' statuses and window masks into the caller's host arrays (the shard's part of them);
+// complete (synchronised) when it returns.  The kernels only read the cluster.  What it allocates goes
+// when it returns, whatever it returns.
+int cluster_check_shard(const ClusterShard& s, const LockPlan& plan, uint8_t* hstatus, uint64_t* hwindows) {
+  const size_t ng = s.ge - s.gb;
+  if (!ng) return 0;
+  Dev& d = *s.d;
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  DevBufs b;
+  uint8_t *win_st, *row_st;
+  uint64_t* row_win;
+  if (b.alloc(&win_st, ng * plan.windows) || b.alloc(&row_st, ng) || b.alloc(&row_win, ng * sizeof(uint64_t))) return -1;
+  HCHK(hipMemsetAsync(row_win, 0, ng * sizeof(uint64_t), d.stream));  // a row with a bad-status key: no window
+  TIMED(d, "k_lock_check", d.stream, launch_lock_check(s.ent, s.st, (uint32_t)ng, plan, win_st, row_st, row_win, d.stream));
+  HCHK(hipMemcpyAsync(hstatus, row_st, ng, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipMemcpyAsync(hwindows, row_win, ng * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));
+  return 0;
+}
+
+// A checked hbls_cluster_check: the shards one after the other
+int cluster_check(Cluster& cl, const LockPlan& plan, uint8_t* row_status, uint64_t* row_windows, size_t* n_bad) {
+  // the shards' results gather here: the caller's arrays are written once every shard has succeeded
+  std::vector<uint8_t> hst(cl.n_validators);
+  std::vector<uint64_t> hwin(cl.n_validators);
+  for (const ClusterShard& s : cl.sh)
+    if (cluster_check_shard(s, plan, hst.data() + s.gb, hwin.data() + s.gb)) return shard_err("hbls_cluster_check", *s.d, g_err);
+  uint64_t bad = 0, inconsistent = 0;
+  for (uint8_t st : hst) {
+    bad += st ? 1 : 0;
+    inconsistent += st == ST_NOT_VERIFIED ? 1 : 0;
+  }
+  if (!hst.empty()) memcpy(row_status, hst.data(), hst.size());
+  if (row_windows && !hwin.empty()) memcpy(row_windows, hwin.data(), hwin.size() * sizeof(uint64_t));
+  if (n_bad) *n_bad = (size_t)bad;
+  cl.check_stats[0] += 1;
+  cl.check_stats[1] += inconsistent;
+  return 0;
+}
+
+// What hbls_cluster_verify_batch was called with
+struct ClusterVerifyArgs {
+  const uint32_t* group;
+  const int64_t* key_idx;
+  const uint8_t *sigs, *msgs;
+  const uint64_t* msg_off;
+  const uint32_t* msg_len;
+  size_t n;
+  uint8_t* status;
+};
+
+// One shard of hbls_cluster_verify_batch: its items (caller indices, increasing), all of groups the shard
+// owns.  Phase one of a cluster duty's add (DutyShardAdd::verify_) with a message table that lives for
+// this call only: the plan (hduty.h duty_plan_shard), the upload, the hashing of the call's distinct
+// messages, then verify_pipeline with the shard's keys by (group, key index), entry 0 allowed.  Not
+// chunked, as a duty add is not.  The statuses go to hst at the items' caller indices; complete
+// (synchronised) when it returns.  The kernels only read the cluster.
+int cluster_verify_shard(const Cluster& cl, const ClusterShard& cs, const ClusterVerifyArgs& a, const std::vector<uint32_t>& items,
+                         size_t gmax, uint8_t* hst) {
+  const size_t m = items.size();
+  if (!m) return 0;
+  Dev& d = *cs.d;
+  HcLease hcs(d);
+  Hc& h = *hcs.h[0];
+  DutyMsgTable tab;
+  DutyShardPlan p;
+  duty_plan_shard(a.msgs, a.msg_off, a.msg_len, a.group, a.key_idx, items, cs.gb, cs.ge, 0, gmax, tab, p);
+  const size_t nm = tab.size();
+  std::vector<uint8_t> hsig, st(m);
+  std::vector<uint32_t> hcg;
+  std::vector<int64_t> hci;
+  gather_plan_order(p.order, a.group, a.key_idx, a.sigs, hcg, hci, hsig);
+  std::unique_lock<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  hipStream_t s = h.s;
+  uint8_t *dsig, *dmsg;
+  uint64_t* doff;
+  uint32_t *dlen, *dmidx, *dvgoff, *dcg;
+  int64_t* dci;
+  void *pst, *phm;
+  if (upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
+  PinnedUploads up;
+  up.add(I_DCGRP, hcg.data(), m, &dcg);
+  up.add(I_DCSHARE, hci.data(), m, &dci);
+  up.add(I_MSG, tab.t.bytes.data(), tab.t.bytes.size(), &dmsg);
+  up.add(I_OFF, tab.t.off.data(), nm, &doff);
+  up.add(I_LEN, tab.t.len.data(), nm, &dlen);
+  up.add(I_MIDX, p.midx.data(), m, &dmidx);
+  up.add(I_VGOFF, p.vgoff.data(), p.vgoff.size(), &dvgoff);
+  if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_HM], nm * sizeof(MsgEntry), &phm))
+    return -1;
+  MsgEntry* hm = (MsgEntry*)phm;
+  Ws& w = ws_acquire(d, s);
+  // the table is the call's own, so its lines are deferred where a host Verify defers them (verify_host)
+  const bool defer = defer_lines(p.n_vgroups(), nm);
+  if (hash_range(d, w, s, dmsg, doff, dlen, hm, 0, nm, !defer)) return -1;
+  VerifyCall vc;
+  vc.h_ready = w.ev_h;
+  vc.defer_hm = hm;
+  vc.defer_msgs = defer ? nm : 0;
+  vc.sigs = dsig;
+  vc.msg_idx = dmidx;
+  vc.hm = hm;
+  vc.n = m;
+  vc.grp_off = dvgoff;
+  vc.n_groups = p.n_vgroups();
+  vc.status = (uint8_t*)pst;
+  vc.s = s;
+  vc.device_entry = true;
+  vc.hm_ready = w.ev_side[2];
+  const ClusterKeysArgs ck = cluster_keys_args(cs, cl.n_shares, dcg, dci, true);
+  vc.cluster = &ck;
+  vc.cluster_wide = cs.wide;
+  if (verify_pipeline(d, w, vc)) return -1;
+  HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
+  if (ws_release(w, s)) return -1;
+  lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+  HCHK(hipMemcpyAsync(st.data(), pst, m, hipMemcpyDeviceToHost, s));
+  HCHK(hipStreamSynchronize(s));
+  for (size_t q = 0; q < m; q++) hst[p.order[q]] = st[q];
+  return 0;
+}
+
+// A checked hbls_cluster_verify_batch over the cluster's shards
+int cluster_verify_batch(Cluster& cl, const ClusterVerifyArgs& a) {
+  // an item goes to the shard that owns its group; one that names no validator needs no device
+  const size_t n = a.n, nd = cl.sh.size();
+  std::vector<std::vector<uint32_t>> items(nd);
+  std::vector<uint8_t> hst(n, (uint8_t)ST_BAD_PUBKEY);
+  uint64_t named = 0;
+  for (size_t i = 0; i < n; i++) {
+    if (a.group[i] >= cl.n_validators) continue;
+    const size_t k = duty_shard_of_group(a.group[i], cl.n_validators, nd);
+    items[k].push_back((uint32_t)i);
+    const ClusterShard& s = cl.sh[k];
+    named += cluster_key(a.group[i], a.key_idx[i], (uint32_t)s.gb, (uint32_t)(s.ge - s.gb), cl.n_shares, true) != CLUSTER_NO_KEY;
+  }
+  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
+  if (n && each_shard("hbls_cluster_verify_batch", cl.sh,
+                      [&](size_t k) { return cluster_verify_shard(cl, cl.sh[k], a, items[k], gmax, hst.data()); }))
+    return -1;
+  // the caller's array is written once every shard has succeeded; a failed call counts nothing
+  if (n) memcpy(a.status, hst.data(), n);
+  cl.verify_stats[0] += 1;
+  cl.verify_stats[1] += named;
+  cl.verify_stats[2] += n - named;
+  return 0;
+}
+
+// One shard of hbls_cluster_verify_aggregate, on its library stream: k_cluster_row_sum over the shard's
+// own rows, then the k_seg_sum<false> passes of one group down to one Jacobian point and one flag, which
+// come to the host (sum: 144 bytes); complete (synchronised) when it returns.  The kernels only read the
+// cluster.  What it allocates goes when it returns, whatever it returns.
+int cluster_sum_shard(const Cluster& cl, const ClusterShard& s, uint64_t share_mask, uint32_t with_dv, G1JEntry* sum,
+                      uint8_t* flag) {
+  const size_t ng = s.ge - s.gb;
+  if (!ng) return 0;
+  Dev& d = *s.d;
+  const uint32_t goff[2] = {0, (uint32_t)ng};
+  VaPlan v;
+  va_plan(goff, 1, ng, v);
+  const size_t na = v.pass_n[0], nb = v.pass_n.size() > 1 ? v.pass_n[1] : 1;
+  std::lock_guard<std::mutex> lk(d.mu);
+  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+  DevBufs b;
+  G1JEntry *rows, *sa, *sb;
+  uint8_t *rows_st, *sa_st, *sb_st;
+  uint32_t* dplan;
+  if (b.alloc(&rows, ng * sizeof(G1JEntry)) || b.alloc(&rows_st, ng) || b.alloc(&sa, na * sizeof(G1JEntry)) ||
+      b.alloc(&sa_st, na) || b.alloc(&sb, nb * sizeof(G1JEntry)) || b.alloc(&sb_st, nb) ||
+      b.alloc(&dplan, v.plan.size() * sizeof(uint32_t)))
+    return -1;
+  HCHK(hipMemcpyAsync(dplan, v.plan.data(), v.plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
+  TIMED(d, "k_cluster_row_sum", d.stream,
+        launch_cluster_row_sum(s.ent, s.st, (uint32_t)ng, cl.n_shares, share_mask, with_dv, rows, rows_st, d.stream));
+  G1JEntry* out;
+  uint8_t* out_st;
+  if (va_reduce(d, v, dplan, false, rows, rows_st, sa, sa_st, sb, sb_st, d.stream, &out, &out_st)) return -1;
+  HCHK(hipMemcpyAsync(sum, out, sizeof(G1JEntry), hipMemcpyDeviceToHost, d.stream));  // the one group's sum: index 0
+  HCHK(hipMemcpyAsync(flag, out_st, 1, hipMemcpyDeviceToHost, d.stream));
+  HCHK(hipStreamSynchronize(d.stream));
+  return 0;
+}
+
+// A checked hbls_cluster_verify_aggregate: the shards' sums, then the cross-shard tail
+int cluster_verify_aggregate(Cluster& cl, uint64_t share_mask, uint32_t with_dv, const uint8_t* sig, const uint8_t* msg,
+                             uint32_t msg_len, uint8_t* status) {
+  // per shard: its rows' selected keys down to one point and one flag (an empty selection sums nothing)
+  const size_t nd = cl.sh.size();
+  const uint32_t per_row = cluster_sel_count(share_mask, with_dv);
+  std::vector<G1JEntry> hsum(nd);
+  std::vector<uint8_t> hflag(nd, 0);
+  if (per_row && each_shard("hbls_cluster_verify_aggregate", cl.sh, [&](size_t k) {
+        return cluster_sum_shard(cl, cl.sh[k], share_mask, with_dv, &hsum[k], &hflag[k]);
+      }))
+    return -1;
+  // across the shards: their points and flags, packed, to the first non-empty shard's device -- one more
+  // k_seg_sum<false> pass there (va_pipeline over Jacobian sums), then FastAggregateVerify's tail
+  std::vector<G1JEntry> sums;
+  std::vector<uint8_t> flags;
+  const ClusterShard* first = nullptr;
+  for (size_t k = 0; k < nd; k++) {
+    const ClusterShard& s = cl.sh[k];
+    if (s.ge == s.gb) continue;
+    if (!first) first = &s;
+    if (per_row) {
+      sums.push_back(hsum[k]);
+      flags.push_back(hflag[k]);
+    }
+  }
+  if (!first) first = &cl.sh[0];  // a cluster of no validator: the empty group on the first device
+  Dev& d = *first->d;
+  const size_t np = sums.size();
+  const uint32_t goff[2] = {0, (uint32_t)np};
+  MsgTable t;
+  t.idx.resize(1);
+  t.off.push_back(0);
+  t.len.push_back(msg_len);
+  t.bytes.assign(msg, msg + msg_len);
+  uint8_t st = 0;
+  {
+    HcLease hcs(d);
+    Hc& h = *hcs.h[0];
+    std::unique_lock<std::mutex> lk(d.mu);
+    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
+    G1JEntry* dsums;
+    uint8_t *dflags, *dsig;
+    void *pst, *hmp;
+    if (upload(d, I_OUT, sums.data(), np, &dsums, &h) || upload(d, I_HM2, flags.data(), np, &dflags, &h) ||
+        upload(d, I_SIG, sig, (size_t)96, &dsig, &h) || ensure_buf(h.io[I_STAT], 1, &pst) ||
+        ensure_buf(h.io[I_HM], sizeof(MsgEntry), &hmp))
+      return -1;
+    Ws& w = ws_acquire(d, h.s);
+    VaKeys keys;
+    keys.sums = dsums;
+    keys.sums_st = dflags;
+    if (va_pipeline(d, w, keys, np, goff, 1, dsig, (MsgEntry*)hmp, (uint8_t*)pst, h.s,
+                    [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, &h); }))
+      return -1;
+    if (ws_release(w, h.s)) return -1;
+    lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
+    HCHK(hipMemcpyAsync(&st, pst, 1, hipMemcpyDeviceToHost, h.s));
+    HCHK(hipStreamSynchronize(h.s));
+  }
+  *status = st;
+  cl.verify_stats[3] += 1;
+  cl.verify_stats[4] += (uint64_t)per_row * cl.n_validators;
+  return 0;
+}
 
 struct DutyShard {
   Dev* d = nullptr;
@@ -3261,23 +3713,20 @@ struct Duty {
   uint64_t set_stats[3] = {};  // hbls_duty_set_stats: sets seen, sets rejected, verified partials of rejected sets
   uint64_t first_stats[2] = {};  // hbls_duty_first_stats: partials through hbls_duty_add_sets_first, those reported UNCHECKED
 };
-std::mutex g_duty_mu;
-std::unordered_map<uint64_t, std::shared_ptr<Duty>> g_duties;
-uint64_t g_duty_next = 1;
+HandleTable<Duty> g_duties;
 
-std::shared_ptr<Duty> duty_find(uint64_t handle) {
-  std::lock_guard<std::mutex> l(g_duty_mu);
-  auto it = g_duties.find(handle);
-  return it == g_duties.end() ? nullptr : it->second;
+// take: hbls_duty_close (the handle's last use)
+std::shared_ptr<Duty> duty_get(const std::string& who, uint64_t handle, bool take = false) {
+  std::shared_ptr<Duty> du = take ? g_duties.take(handle) : g_duties.find(handle);
+  if (!du) set_err(who + ": no such duty (never opened, or closed)");
+  return du;
 }
 
 void duty_free_shard(DutyShard& s) {
   if (!s.d) return;
   std::lock_guard<std::mutex> lk(s.d->mu);
   if (hipSetDevice(s.d->ord) != hipSuccess) return;
-  for (void* p : {(void*)s.hm, (void*)s.store, (void*)s.store_st, (void*)s.rec_idx, (void*)s.rec_msg, (void*)s.rec_serial,
-                  (void*)s.count, (void*)s.fired, (void*)s.dvpk, (void*)s.selctr})
-    if (p) (void)hipFree(p);
+  DevBufs own({s.hm, s.store, s.store_st, s.rec_idx, s.rec_msg, s.rec_serial, s.count, s.fired, s.dvpk, s.selctr});  // freed on return
   s = DutyShard{};
 }
 
@@ -3322,16 +3771,14 @@ int duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32
     du->sh[k].gb = cl ? cl->sh[k].gb : n_groups * k / nd;
     du->sh[k].ge = cl ? cl->sh[k].ge : n_groups * (k + 1) / nd;
     du->sh[k].cs = cl ? &cl->sh[k] : nullptr;
-    const int ord = du->sh[k].d->ord;
     if (duty_alloc_shard(du->sh[k], dv_pks, max_stored)) {
+      const Dev& d = *du->sh[k].d;
       const std::string err = g_err;
       for (size_t j = 0; j <= k; j++) duty_free_shard(du->sh[j]);  // nothing is left behind
-      return set_err(who + ": device " + std::to_string(ord) + ": " + err);
+      return shard_err(who, d, err);
     }
   }
-  std::lock_guard<std::mutex> l(g_duty_mu);
-  *handle = g_duty_next++;
-  g_duties[*handle] = du;
+  *handle = g_duties.add(du);
   return 0;
 }
 
@@ -3437,17 +3884,6 @@ struct DutyShardAdd {
   Ws* w = nullptr;  // the verification's workspace set, until it is handed back
   std::vector<uint32_t> set_first;  // the sets' first failures as this shard saw them (one shard: the call's)
 
-  // a cluster duty: the shard's keys for k_cluster_keys over items named by group (share: null, their DV keys)
-  void cluster_args_(ClusterKeysArgs& ck, const uint32_t* group, const int64_t* share) const {
-    ck.group = group;
-    ck.share_idx = share;
-    ck.group_base = (uint32_t)sh.gb;
-    ck.n_groups = (uint32_t)ng;
-    ck.n_shares = du.cl->n_shares;
-    ck.n_keys = (uint32_t)sh.cs->n_keys;
-    ck.ent = sh.cs->ent;
-    ck.st = sh.cs->st;
-  }
   int verify_(bool split);
   int store_(const uint32_t* merged);
   int gate_(const uint32_t* merged), store_rule_(), download_(), aggregate_fired_(), download_fired_();  // its steps
@@ -3489,19 +3925,13 @@ int DutyShardAdd::verify_(bool two_phases) {
   // the keys: the caller's 48 bytes per partial, or (a cluster duty) each partial's group and share index
   // for k_cluster_keys -- as the plan orders them, like everything the verification reads per item
   const ClusterShard* const cs = sh.cs;
-  std::vector<uint8_t> hpk(cs ? 0 : 48 * m), hsig(96 * m);
-  std::vector<uint32_t> hcg(cs ? m : 0);
-  std::vector<int64_t> hci(cs ? m : 0);
-  for (size_t q = 0; q < m; q++) {
-    if (cs) {
-      hcg[q] = a.group[p.order[q]];
-      hci[q] = a.share_idx[p.order[q]];
-    } else {
-      memcpy(&hpk[48 * q], a.pks + 48ull * p.order[q], 48);
-    }
-    memcpy(&hsig[96 * q], a.sigs + 96ull * p.order[q], 96);
-  }
-  if (cs) {  // hbls_cluster_stats: the rule the kernel applies, on the host; duty_add counts it once the add has succeeded
+  std::vector<uint8_t> hpk(cs ? 0 : 48 * m), hsig;
+  std::vector<uint32_t> hcg;
+  std::vector<int64_t> hci;
+  gather_plan_order(p.order, cs ? a.group : nullptr, a.share_idx, a.sigs, hcg, hci, hsig);
+  if (!cs) {
+    for (size_t q = 0; q < m; q++) memcpy(&hpk[48 * q], a.pks + 48ull * p.order[q], 48);
+  } else {  // hbls_cluster_stats: the rule the kernel applies, on the host; duty_add counts it once the add has succeeded
     for (size_t q = 0; q < m; q++)
       out.n_named += cluster_key(hcg[q], hci[q], (uint32_t)sh.gb, (uint32_t)ng, du.cl->n_shares) != CLUSTER_NO_KEY ? 1 : 0;
     out.n_nokey = m - out.n_named;
@@ -3580,7 +4010,7 @@ int DutyShardAdd::verify_(bool two_phases) {
   vc.hm_ready = w.ev_side[2];
   ClusterKeysArgs ck{};
   if (cs) {
-    cluster_args_(ck, dcg, dci);
+    ck = cluster_keys_args(*cs, du.cl->n_shares, dcg, dci, false);
     vc.cluster = &ck;
     vc.cluster_wide = cs->wide;
   }
@@ -3783,7 +4213,7 @@ int DutyShardAdd::aggregate_fired_() {
   v2.hm = sh.hm;
   ClusterKeysArgs ck{};
   if (sh.cs) {  // a cluster duty: the DV keys from the cluster by fired group id (no bytes were gathered: pdv is null)
-    cluster_args_(ck, (const uint32_t*)pfg, nullptr);
+    ck = cluster_keys_args(*sh.cs, du.cl->n_shares, (const uint32_t*)pfg, nullptr, false);
     v2.cluster = &ck;
     v2.cluster_wide = sh.cs->wide;
     out.n_dv = nf;
@@ -3824,27 +4254,11 @@ int duty_add(Duty& du, const DutyAddArgs& a) {
   std::vector<DutyShardAdd> adds;
   adds.reserve(nd);
   for (size_t k = 0; k < nd; k++) adds.emplace_back(du, du.sh[k], a, items[k], gmax, outs[k]);
-  std::vector<int> rc(nd, 0);
-  std::vector<std::string> errs(nd);
-  // every shard runs fn concurrently (one host thread per shard beyond one), all joined before this returns
+  // every shard runs fn (run_shards: concurrently, all joined before this returns)
   auto each = [&](const std::function<int(size_t)>& fn) {
-    auto run = [&](size_t k) {
-      rc[k] = fn(k);
-      if (rc[k]) errs[k] = g_err;
-    };
-    if (nd == 1) {
-      run(0);
-    } else {
-      std::vector<std::thread> th;
-      for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
-      for (auto& x : th) x.join();
-    }
-    for (size_t k = 0; k < nd; k++)
-      if (rc[k]) {
-        du.broken = true;  // a shard may have stored what another did not verify: the duty's state is no longer one stream's
-        return set_err(who + ": device " + std::to_string(du.sh[k].d->ord) + ": " + errs[k]);
-      }
-    return 0;
+    const int rc = each_shard(who, du.sh, fn);
+    if (rc) du.broken = true;  // a shard may have stored what another did not verify: the duty's state is no longer one stream's
+    return rc;
   };
   std::vector<uint32_t> merged(n_sets, DUTY_NONE);
   if (!sets || nd == 1) {  // one stream segment per shard
@@ -3930,13 +4344,76 @@ int duty_state(Duty& du, uint32_t* stored_count, uint8_t* fired_flag) {
 template <size_t N>
 int duty_counters(const std::string& who, uint64_t duty, uint64_t (Duty::*ctr)[N], uint64_t* out, size_t n) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err(who + ": no such duty (never opened, or closed)");
-  if (!out || n > N) return set_err(who + ": out is null or n above " + std::to_string(N));
+  std::shared_ptr<Duty> du = duty_get(who, duty);
+  if (!du || counters_args(who, out, n, N)) return -1;
   std::lock_guard<std::mutex> l(du->mu);
   if (du->closed) return set_err(who + ": the duty is closed");
-  for (size_t k = 0; k < n; k++) out[k] = ((*du).*ctr)[k];
+  counters_copy((*du).*ctr, out, n);
   return 0;
+}
+
+// A checked hbls_duty_open / hbls_duty_open_cluster begins: the handle's place, the threshold, max_stored
+int duty_open_check(const std::string& who, const uint64_t* duty, uint32_t threshold, uint32_t max_stored) {
+  if (!duty) return set_err(who + ": duty is required");
+  if (threshold < 1 || threshold > (uint32_t)TA_SMALL_MAX)
+    return set_err(who + ": threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
+  if (max_stored < 1 || max_stored > DUTY_MAX_STORED)
+    return set_err(who + ": max_stored must be in 1.." + std::to_string(DUTY_MAX_STORED));
+  return 0;
+}
+
+// hbls_key_learn_stats, hbls_key_wide_stats and hbls_subgroup_batch_stats: for each device of the mask (at
+// most max_devices), under its lock and behind everything enqueued so far, its counter struct C (ctr; with
+// `optional`, zeros while it is not allocated) as the row fill(dev, counters) of out, `stride` counters long
+template <class C, size_t stride, class Fill>
+int device_counters(const std::string& who, DevBuf Dev::*ctr, bool optional, uint64_t* out, size_t max_devices,
+                    size_t* n_devices, Fill fill) {
+  if (ensure_init()) return -1;
+  if (!out || !n_devices) return set_err(who + ": null arguments");
+  size_t k = 0;
+  for (Dev* d : devs()) {
+    if (k == max_devices) break;
+    std::lock_guard<std::mutex> lk(d->mu);
+    HCHK(hipSetDevice(d->ord));
+    C c{};
+    if (!optional || (d->*ctr).p) {
+      if (drain_lib_streams(*d)) return -1;
+      HCHK(hipMemcpy(&c, (d->*ctr).p, sizeof(c), hipMemcpyDeviceToHost));
+    }
+    const std::array<uint64_t, stride> row = fill(*d, c);
+    std::copy(row.begin(), row.end(), out + stride * k++);
+  }
+  *n_devices = k;
+  return 0;
+}
+
+// Signing roots (roots.hip).  mode 0: data = 128-byte SSZ AttestationData; 1: data = 32-byte
+// object roots.  Host buffers; dom_idx nullable.
+int roots_host(int mode, const uint8_t* data, size_t n, const uint8_t* domains, size_t n_domains, const uint32_t* dom_idx,
+               uint8_t* roots) {
+  if (n_domains == 0) return set_err("signing roots: no domain");
+  if (dom_idx)
+    for (size_t i = 0; i < n; i++)
+      if (dom_idx[i] >= n_domains) return set_err("signing roots: domain index out of range");
+  const size_t item = mode == 0 ? 128 : 32;
+  return for_each_device(n, [&](Dev& d, size_t b, size_t e) -> int {
+    const size_t m = e - b;
+    uint8_t *dd, *ddom;
+    uint32_t* didx = nullptr;
+    if (upload(d, I_SIG, data + item * b, m * item, &dd) || upload(d, I_PK, domains, n_domains * 32, &ddom)) return -1;
+    if (dom_idx && upload(d, I_MIDX, dom_idx + b, m, &didx)) return -1;
+    void* out;
+    if (ensure_buf(d.io[I_OUT], m * 32, &out)) return -1;
+    if (mode == 0)
+      TIMED(d, "k_attestation_roots", d.stream,
+            launch_attestation_roots(dd, (uint32_t)m, ddom, (uint32_t)n_domains, didx, (uint8_t*)out, d.stream));
+    else
+      TIMED(d, "k_signing_roots", d.stream,
+            launch_signing_roots(dd, (uint32_t)m, ddom, (uint32_t)n_domains, didx, (uint8_t*)out, d.stream));
+    HCHK(hipMemcpyAsync(roots + 32 * b, out, m * 32, hipMemcpyDeviceToHost, d.stream));
+    HCHK(hipStreamSynchronize(d.stream));
+    return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------------------
@@ -4039,35 +4516,6 @@ int hbls_verify_aggregate_batch(const uint8_t* pks, const uint32_t* grp_off, con
     lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
     HCHK(hipMemcpyAsync(status + gb, dst, ng, hipMemcpyDeviceToHost, h.s));
     HCHK(hipStreamSynchronize(h.s));
-    return 0;
-  });
-}
-
-// Signing roots (roots.hip).  mode 0: data = 128-byte SSZ AttestationData; 1: data = 32-byte
-// object roots.  Host buffers; dom_idx nullable.
-static int roots_host(int mode, const uint8_t* data, size_t n, const uint8_t* domains, size_t n_domains,
-                      const uint32_t* dom_idx, uint8_t* roots) {
-  if (n_domains == 0) return set_err("signing roots: no domain");
-  if (dom_idx)
-    for (size_t i = 0; i < n; i++)
-      if (dom_idx[i] >= n_domains) return set_err("signing roots: domain index out of range");
-  const size_t item = mode == 0 ? 128 : 32;
-  return for_each_device(n, [&](Dev& d, size_t b, size_t e) -> int {
-    const size_t m = e - b;
-    uint8_t *dd, *ddom;
-    uint32_t* didx = nullptr;
-    if (upload(d, I_SIG, data + item * b, m * item, &dd) || upload(d, I_PK, domains, n_domains * 32, &ddom)) return -1;
-    if (dom_idx && upload(d, I_MIDX, dom_idx + b, m, &didx)) return -1;
-    void* out;
-    if (ensure_buf(d.io[I_OUT], m * 32, &out)) return -1;
-    if (mode == 0)
-      TIMED(d, "k_attestation_roots", d.stream,
-            launch_attestation_roots(dd, (uint32_t)m, ddom, (uint32_t)n_domains, didx, (uint8_t*)out, d.stream));
-    else
-      TIMED(d, "k_signing_roots", d.stream,
-            launch_signing_roots(dd, (uint32_t)m, ddom, (uint32_t)n_domains, didx, (uint8_t*)out, d.stream));
-    HCHK(hipMemcpyAsync(roots + 32 * b, out, m * 32, hipMemcpyDeviceToHost, d.stream));
-    HCHK(hipStreamSynchronize(d.stream));
     return 0;
   });
 }
@@ -4336,78 +4784,31 @@ size_t hbls_pubkey_cache_size(void) {
 }
 
 int hbls_key_learn_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
-  if (ensure_init()) return -1;
-  if (!out || !n_devices) return set_err("hbls_key_learn_stats: null arguments");
-  size_t k = 0;
-  for (Dev* d : devs()) {
-    if (k == max_devices) break;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HCHK(hipSetDevice(d->ord));
-    KeyLearnCtr c{};
-    if (d->kl_ctr.p) {  // the counters of everything enqueued so far
-      if (drain_lib_streams(*d)) return -1;
-      HCHK(hipMemcpy(&c, d->kl_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
-    }
-    out[4 * k + 0] = d->kl_cap ? std::min<uint64_t>(c.size, d->kl_cap) : 0;
-    out[4 * k + 1] = g_key_learn.load();
-    out[4 * k + 2] = c.hits;
-    out[4 * k + 3] = c.misses;
-    k++;
-  }
-  *n_devices = k;
-  return 0;
+  return device_counters<KeyLearnCtr, 4>("hbls_key_learn_stats", &Dev::kl_ctr, true, out, max_devices, n_devices,
+                                         [](const Dev& d, const KeyLearnCtr& c) -> std::array<uint64_t, 4> {
+                                           return {d.kl_cap ? std::min<uint64_t>(c.size, d.kl_cap) : 0, g_key_learn.load(), c.hits, c.misses};
+                                         });
 }
 
 // The ladder tables of the learned keys, per device of the mask and cumulative: out[5 k + 0] tables
 // built, + 1 / + 2 chunks of the chunked combination's key side combined through tables / without,
 // + 3 / + 4 per-item key-side ladders through tables / without.  Waits like hbls_key_learn_stats.
 int hbls_key_wide_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
-  if (ensure_init()) return -1;
-  if (!out || !n_devices) return set_err("hbls_key_wide_stats: null arguments");
-  size_t k = 0;
-  for (Dev* d : devs()) {
-    if (k == max_devices) break;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HCHK(hipSetDevice(d->ord));
-    KeyLearnCtr c{};
-    if (d->kl_ctr.p) {
-      if (drain_lib_streams(*d)) return -1;
-      HCHK(hipMemcpy(&c, d->kl_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
-    }
-    out[5 * k + 0] = c.wide_built;
-    out[5 * k + 1] = c.wide_chunks;
-    out[5 * k + 2] = c.narrow_chunks;
-    out[5 * k + 3] = c.wide_items;
-    out[5 * k + 4] = c.narrow_items;
-    k++;
-  }
-  *n_devices = k;
-  return 0;
+  return device_counters<KeyLearnCtr, 5>("hbls_key_wide_stats", &Dev::kl_ctr, true, out, max_devices, n_devices,
+                                         [](const Dev&, const KeyLearnCtr& c) -> std::array<uint64_t, 5> {
+                                           return {c.wide_built, c.wide_chunks, c.narrow_chunks, c.wide_items, c.narrow_items};
+                                         });
 }
 
 // The batched subgroup test, per device of the mask and cumulative: out[4 k + 0] batched tests run,
 // + 1 batched tests that failed, + 2 signatures that went through the per-item ladders of calls
 // large enough for the test, + 3 calls that skipped the test by the adaptive history.  Waits like
-// hbls_key_wide_stats.
+// hbls_key_wide_stats; its counters are allocated with the device, so there is no unallocated case.
 int hbls_subgroup_batch_stats(uint64_t* out, size_t max_devices, size_t* n_devices) {
-  if (ensure_init()) return -1;
-  if (!out || !n_devices) return set_err("hbls_subgroup_batch_stats: null arguments");
-  size_t k = 0;
-  for (Dev* d : devs()) {
-    if (k == max_devices) break;
-    std::lock_guard<std::mutex> lk(d->mu);
-    HCHK(hipSetDevice(d->ord));
-    SubgCtr c{};
-    if (drain_lib_streams(*d)) return -1;
-    HCHK(hipMemcpy(&c, d->sg_ctr.p, sizeof(c), hipMemcpyDeviceToHost));
-    out[4 * k + 0] = c.run;
-    out[4 * k + 1] = c.failed;
-    out[4 * k + 2] = c.laddered;
-    out[4 * k + 3] = c.skipped;
-    k++;
-  }
-  *n_devices = k;
-  return 0;
+  return device_counters<SubgCtr, 4>("hbls_subgroup_batch_stats", &Dev::sg_ctr, false, out, max_devices, n_devices,
+                                     [](const Dev&, const SubgCtr& c) -> std::array<uint64_t, 4> {
+                                       return {c.run, c.failed, c.laddered, c.skipped};
+                                     });
 }
 
 // Test switch of the in-process multi-device split: every device of the mask is driven through
@@ -4602,9 +5003,7 @@ int hbls_slot_select_batch(const uint8_t* pks, const uint8_t* sigs, const uint8_
     return set_err("hbls_slot_select_batch: too many items");
   if (n && (!pks || !sigs || !msg_off || !msg_len || !vstatus))
     return set_err("hbls_slot_select_batch: pks, sigs, msg_off, msg_len and vstatus are required");
-  if (n && !msgs)
-    for (size_t i = 0; i < n; i++)
-      if (msg_len[i]) return set_err("hbls_slot_select_batch: msgs is required");
+  if (msgs_missing(msgs, msg_len, n)) return set_err("hbls_slot_select_batch: msgs is required");
   if (n_groups && (!grp_off || !dv_pks || !chosen || !ta_count || !ta_out || !ta_status || !agg_vstatus))
     return set_err("hbls_slot_select_batch: grp_off, dv_pks, chosen, ta_count, ta_out, ta_status and agg_vstatus are required");
   static const uint32_t no_groups[1] = {0};
@@ -4642,12 +5041,7 @@ int hbls_slot_select_stats(uint64_t* out, size_t n) {
 }
 
 int hbls_duty_open(const uint8_t* dv_pks, size_t n_groups, uint32_t threshold, uint32_t max_stored, uint64_t* duty) {
-  if (ensure_init()) return -1;
-  if (!duty) return set_err("hbls_duty_open: duty is required");
-  if (threshold < 1 || threshold > (uint32_t)TA_SMALL_MAX)
-    return set_err("hbls_duty_open: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
-  if (max_stored < 1 || max_stored > DUTY_MAX_STORED)
-    return set_err("hbls_duty_open: max_stored must be in 1.." + std::to_string(DUTY_MAX_STORED));
+  if (ensure_init() || duty_open_check("hbls_duty_open", duty, threshold, max_stored)) return -1;
   if (n_groups && !dv_pks) return set_err("hbls_duty_open: dv_pks is required");
   if (n_groups >= 0xffffffffull / DUTY_MAX_STORED) return set_err("hbls_duty_open: too many groups");
   return duty_open(dv_pks, n_groups, threshold, max_stored, duty);
@@ -4659,8 +5053,8 @@ static int duty_add_entry(uint64_t duty, DutyAddArgs a, DutySetCall* sets) {
   const std::string who = a.who;
   const size_t n = a.n;
   if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err(who + ": no such duty (never opened, or closed)");
+  std::shared_ptr<Duty> du = duty_get(who, duty);
+  if (!du) return -1;
   std::lock_guard<std::mutex> l(du->mu);
   if (du->closed) return set_err(who + ": the duty is closed");
   if (du->broken) return set_err(who + ": an earlier add failed on a device; close the duty");
@@ -4677,9 +5071,7 @@ static int duty_add_entry(uint64_t duty, DutyAddArgs a, DutySetCall* sets) {
       return set_err(who + ": sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
   } else if (n && (!a.pks || !a.sigs || !a.msg_off || !a.msg_len || !a.group || !a.share_idx || !a.vstatus || !a.stored))
     return set_err(who + ": pks, sigs, msg_off, msg_len, group, share_idx, vstatus and stored are required");
-  if (!a.msgs)
-    for (size_t i = 0; i < n; i++)
-      if (a.msg_len[i]) return set_err(who + ": msgs is required");
+  if (msgs_missing(a.msgs, a.msg_len, n)) return set_err(who + ": msgs is required");
   if (std::min(n, du->n_groups) && (!a.fired || !a.chosen || !a.ta_out || !a.ta_status || !a.agg_vstatus))
     return set_err(who + ": fired, chosen, ta_out, ta_status and agg_vstatus are required");
   *a.first_serial = du->next_serial;
@@ -4734,8 +5126,8 @@ int hbls_duty_set_stats(uint64_t duty, uint64_t* out, size_t n) {
 
 int hbls_duty_state(uint64_t duty, uint32_t* stored_count, uint8_t* fired_flag) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du = duty_find(duty);
-  if (!du) return set_err("hbls_duty_state: no such duty (never opened, or closed)");
+  std::shared_ptr<Duty> du = duty_get("hbls_duty_state", duty);
+  if (!du) return -1;
   std::lock_guard<std::mutex> l(du->mu);
   if (du->closed) return set_err("hbls_duty_state: the duty is closed");
   if (du->n_groups && (!stored_count || !fired_flag)) return set_err("hbls_duty_state: stored_count and fired_flag are required");
@@ -4748,46 +5140,12 @@ int hbls_duty_stats(uint64_t duty, uint64_t* out, size_t n) {
 
 int hbls_duty_close(uint64_t duty) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Duty> du;
-  {
-    std::lock_guard<std::mutex> l(g_duty_mu);
-    auto it = g_duties.find(duty);
-    if (it == g_duties.end()) return set_err("hbls_duty_close: no such duty (never opened, or closed)");
-    du = it->second;
-    g_duties.erase(it);
-  }
+  std::shared_ptr<Duty> du = duty_get("hbls_duty_close", duty, true);
+  if (!du) return -1;
   std::lock_guard<std::mutex> l(du->mu);  // behind the duty's call in flight, if any
   du->closed = true;
   for (DutyShard& s : du->sh) duty_free_shard(s);
   du->cl.reset();  // a cluster duty: the last duty of a closed cluster frees the keys (no device lock is held here)
-  return 0;
-}
-
-// One shard of hbls_cluster_open: its rows' compressed keys up, the decompression and membership test of
-// hbls_decompress_pubkeys_device into the resident table, the ladder tables, the statuses back; complete
-// (synchronised) when it returns.  Leaves what it allocated in s for the caller to free on failure.
-static int cluster_fill_shard(ClusterShard& s, const uint8_t* dv_pks, const uint8_t* pubshares, uint32_t n_shares,
-                              bool tables, uint8_t* hst, uint8_t** tmp) {
-  Dev& d = *s.d;
-  const size_t ng = s.ge - s.gb, row = 1 + (size_t)n_shares, nk = ng * row;
-  s.n_keys = nk;
-  if (!nk) return 0;
-  std::vector<uint8_t> keys(48 * nk);
-  for (size_t g = 0; g < ng; g++) {
-    memcpy(&keys[48 * g * row], dv_pks + 48 * (s.gb + g), 48);
-    memcpy(&keys[48 * (g * row + 1)], pubshares + 48 * (s.gb + g) * n_shares, 48 * (size_t)n_shares);
-  }
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-  HCHK(hipMalloc((void**)&s.ent, nk * sizeof(G1AEntry)));
-  HCHK(hipMalloc((void**)&s.st, nk));
-  if (tables) HCHK(hipMalloc((void**)&s.wide, nk * KEY_WIDE_PTS * sizeof(G1WidePt)));
-  HCHK(hipMalloc((void**)tmp, 48 * nk));
-  HCHK(hipMemcpyAsync(*tmp, keys.data(), 48 * nk, hipMemcpyHostToDevice, d.stream));
-  TIMED(d, "k_dec_pk", d.stream, launch_dec_pk(*tmp, (uint32_t)nk, s.ent, s.st, d.stream));
-  if (tables) TIMED(d, "k_cluster_wide", d.stream, launch_cluster_wide(s.ent, s.st, (uint32_t)nk, s.wide, d.stream));
-  HCHK(hipMemcpyAsync(hst, s.st, nk, hipMemcpyDeviceToHost, d.stream));
-  HCHK(hipStreamSynchronize(d.stream));  // complete before any stream's kernel reads them: the cluster is immutable from here
   return 0;
 }
 
@@ -4802,429 +5160,67 @@ int hbls_cluster_open(const uint8_t* dv_pks, const uint8_t* pubshares, size_t n_
   // n_validators (1 + n_shares) < 2^32 - 1: a key's number is a uint32 entry number of the ladder-table
   // path (KeyWideRef::ent), and KEY_WIDE_NONE is no key's
   if (n_validators > 0xfffffffeull / (1 + (uint64_t)n_shares)) return set_err("hbls_cluster_open: too many keys");
-  auto cl = std::make_shared<Cluster>();  // (whatever a failing shard leaves allocated goes with it: nothing stays)
-  cl->n_validators = n_validators;
-  cl->n_shares = n_shares;
-  cl->tables = ladder_tables != 0;
-  const std::vector<Dev*> ds = devs();
-  const size_t nd = slot_shards(ds.size(), n_validators), row = 1 + (size_t)n_shares;
-  cl->sh.resize(nd);
-  std::vector<uint8_t> hst(n_validators * row);
-  for (size_t k = 0; k < nd; k++) {
-    ClusterShard& s = cl->sh[k];
-    s.d = ds[k];
-    s.gb = n_validators * k / nd;
-    s.ge = n_validators * (k + 1) / nd;
-    uint8_t* tmp = nullptr;
-    const int rc = cluster_fill_shard(s, dv_pks, pubshares, n_shares, cl->tables, hst.data() + s.gb * row, &tmp);
-    const std::string err = rc ? g_err : "";
-    if (tmp) {
-      std::lock_guard<std::mutex> lk(s.d->mu);
-      if (hipSetDevice(s.d->ord) == hipSuccess) (void)hipFree(tmp);
-    }
-    if (rc) return set_err("hbls_cluster_open: device " + std::to_string(ds[k]->ord) + ": " + err);
-  }
-  uint64_t bad = 0, built = 0;
-  for (size_t g = 0; g < n_validators; g++)
-    for (size_t j = 0; j < row; j++) {
-      const uint8_t st = hst[g * row + j];
-      const uint8_t* key = j ? pubshares + 48 * (g * n_shares + j - 1) : dv_pks + 48 * g;
-      bad += st ? 1 : 0;
-      built += (cl->tables && !st && !(key[0] & 0x40)) ? 1 : 0;  // good and finite (the compressed form's infinity bit)
-    }
-  if (key_status && !hst.empty()) memcpy(key_status, hst.data(), hst.size());
-  cl->stats[0] = hst.size();
-  cl->stats[1] = bad;
-  cl->stats[2] = built;
-  std::lock_guard<std::mutex> l(g_cluster_mu);
-  *cluster = g_cluster_next++;
-  g_clusters[*cluster] = cl;
-  return 0;
-}
-
-static std::shared_ptr<Cluster> cluster_find(uint64_t handle) {
-  std::lock_guard<std::mutex> l(g_cluster_mu);
-  auto it = g_clusters.find(handle);
-  return it == g_clusters.end() ? nullptr : it->second;
+  return cluster_open(dv_pks, pubshares, n_validators, n_shares, ladder_tables != 0, key_status, cluster);
 }
 
 int hbls_cluster_close(uint64_t cluster) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl;
-  {
-    std::lock_guard<std::mutex> l(g_cluster_mu);
-    auto it = g_clusters.find(cluster);
-    if (it == g_clusters.end()) return set_err("hbls_cluster_close: no such cluster (never opened, or closed)");
-    cl = it->second;
-    g_clusters.erase(it);
-  }
-  return 0;  // (cl goes here, with no lock held: the keys with it unless a duty still holds them)
+  return cluster_get("hbls_cluster_close", cluster, true) ? 0 : -1;  // (the keys go here unless a duty still holds them)
 }
 
 int hbls_cluster_stats(uint64_t cluster, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_stats: no such cluster (never opened, or closed)");
-  if (!out || n > 6) return set_err("hbls_cluster_stats: out is null or n above 6");
-  for (size_t k = 0; k < n; k++) out[k] = cl->stats[k].load();
-  return 0;
-}
-
-// One shard of hbls_cluster_check: k_lock_check and k_lock_fold over the shard's own rows on its library
-// stream, the rows' statuses and window masks into the caller's host arrays (the shard's part of them);
-// complete (synchronised) when it returns.  The kernels only read the cluster.  What it allocates goes
-// when it returns, whatever it returns.
-static int cluster_check_shard(const ClusterShard& s, const LockPlan& plan, uint8_t* hstatus, uint64_t* hwindows) {
-  const size_t ng = s.ge - s.gb;
-  if (!ng) return 0;
-  Dev& d = *s.d;
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-  struct Bufs {
-    void* p[3] = {};
-    ~Bufs() {
-      for (void* q : p)
-        if (q) (void)hipFree(q);
-    }
-  } b;
-  HCHK(hipMalloc(&b.p[0], ng * plan.windows));
-  HCHK(hipMalloc(&b.p[1], ng));
-  HCHK(hipMalloc(&b.p[2], ng * sizeof(uint64_t)));
-  HCHK(hipMemsetAsync(b.p[2], 0, ng * sizeof(uint64_t), d.stream));  // a row with a bad-status key: no window
-  TIMED(d, "k_lock_check", d.stream,
-        launch_lock_check(s.ent, s.st, (uint32_t)ng, plan, (uint8_t*)b.p[0], (uint8_t*)b.p[1], (uint64_t*)b.p[2], d.stream));
-  HCHK(hipMemcpyAsync(hstatus, b.p[1], ng, hipMemcpyDeviceToHost, d.stream));
-  HCHK(hipMemcpyAsync(hwindows, b.p[2], ng * sizeof(uint64_t), hipMemcpyDeviceToHost, d.stream));
-  HCHK(hipStreamSynchronize(d.stream));
-  return 0;
+  return cluster_counters("hbls_cluster_stats", cluster, &Cluster::stats, out, n);
 }
 
 int hbls_cluster_check(uint64_t cluster, uint32_t threshold, uint8_t* row_status, uint64_t* row_windows, size_t* n_bad) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_check: no such cluster (never opened, or closed)");
+  std::shared_ptr<Cluster> cl = cluster_get("hbls_cluster_check", cluster);
+  if (!cl) return -1;
   LockPlan plan;
   if (!lock_plan(cl->n_shares, threshold, plan))
     return set_err("hbls_cluster_check: threshold must be in 1.." + std::to_string(cl->n_shares) + " (the cluster's n_shares)");
   if (cl->n_validators && !row_status) return set_err("hbls_cluster_check: row_status is required");
-  // the shards' results gather here: the caller's arrays are written once every shard has succeeded
-  std::vector<uint8_t> hst(cl->n_validators);
-  std::vector<uint64_t> hwin(cl->n_validators);
-  for (const ClusterShard& s : cl->sh) {
-    if (cluster_check_shard(s, plan, hst.data() + s.gb, hwin.data() + s.gb)) {
-      const std::string err = g_err;
-      return set_err("hbls_cluster_check: device " + std::to_string(s.d->ord) + ": " + err);
-    }
-  }
-  uint64_t bad = 0, inconsistent = 0;
-  for (uint8_t st : hst) {
-    bad += st ? 1 : 0;
-    inconsistent += st == ST_NOT_VERIFIED ? 1 : 0;
-  }
-  if (!hst.empty()) memcpy(row_status, hst.data(), hst.size());
-  if (row_windows && !hwin.empty()) memcpy(row_windows, hwin.data(), hwin.size() * sizeof(uint64_t));
-  if (n_bad) *n_bad = (size_t)bad;
-  cl->check_stats[0] += 1;
-  cl->check_stats[1] += inconsistent;
-  return 0;
+  return cluster_check(*cl, plan, row_status, row_windows, n_bad);
 }
 
 int hbls_cluster_check_stats(uint64_t cluster, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_check_stats: no such cluster (never opened, or closed)");
-  if (!out || n > 2) return set_err("hbls_cluster_check_stats: out is null or n above 2");
-  for (size_t k = 0; k < n; k++) out[k] = cl->check_stats[k].load();
-  return 0;
-}
-
-// Run fn(k) for every shard of a cluster concurrently (one host thread per shard beyond one), all joined
-// before this returns; the first failing shard's error is reported with its device.
-static int cluster_each_shard(const Cluster& cl, const std::string& who, const std::function<int(size_t)>& fn) {
-  const size_t nd = cl.sh.size();
-  std::vector<int> rc(nd, 0);
-  std::vector<std::string> errs(nd);
-  auto run = [&](size_t k) {
-    rc[k] = fn(k);
-    if (rc[k]) errs[k] = g_err;
-  };
-  if (nd == 1) {
-    run(0);
-  } else {
-    std::vector<std::thread> th;
-    for (size_t k = 0; k < nd; k++) th.emplace_back(run, k);
-    for (auto& x : th) x.join();
-  }
-  for (size_t k = 0; k < nd; k++)
-    if (rc[k]) return set_err(who + ": device " + std::to_string(cl.sh[k].d->ord) + ": " + errs[k]);
-  return 0;
-}
-
-// What hbls_cluster_verify_batch was called with
-struct ClusterVerifyArgs {
-  const uint32_t* group;
-  const int64_t* key_idx;
-  const uint8_t *sigs, *msgs;
-  const uint64_t* msg_off;
-  const uint32_t* msg_len;
-};
-
-// One shard of hbls_cluster_verify_batch: its items (caller indices, increasing), all of groups the shard
-// owns.  Phase one of a cluster duty's add (DutyShardAdd::verify_) with a message table that lives for
-// this call only: the plan (hduty.h duty_plan_shard), the upload, the hashing of the call's distinct
-// messages, then verify_pipeline with the shard's keys by (group, key index), entry 0 allowed.  Not
-// chunked, as a duty add is not.  The statuses go to hst at the items' caller indices; complete
-// (synchronised) when it returns.  The kernels only read the cluster.
-static int cluster_verify_shard(const Cluster& cl, const ClusterShard& cs, const ClusterVerifyArgs& a,
-                                const std::vector<uint32_t>& items, size_t gmax, uint8_t* hst) {
-  const size_t m = items.size();
-  if (!m) return 0;
-  Dev& d = *cs.d;
-  HcLease hcs(d);
-  Hc& h = *hcs.h[0];
-  DutyMsgTable tab;
-  DutyShardPlan p;
-  duty_plan_shard(a.msgs, a.msg_off, a.msg_len, a.group, a.key_idx, items, cs.gb, cs.ge, 0, gmax, tab, p);
-  const size_t nm = tab.size();
-  std::vector<uint8_t> hsig(96 * m), st(m);
-  std::vector<uint32_t> hcg(m);
-  std::vector<int64_t> hci(m);
-  for (size_t q = 0; q < m; q++) {
-    hcg[q] = a.group[p.order[q]];
-    hci[q] = a.key_idx[p.order[q]];
-    memcpy(&hsig[96 * q], a.sigs + 96ull * p.order[q], 96);
-  }
-  std::unique_lock<std::mutex> lk(d.mu);
-  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-  hipStream_t s = h.s;
-  uint8_t *dsig, *dmsg;
-  uint64_t* doff;
-  uint32_t *dlen, *dmidx, *dvgoff, *dcg;
-  int64_t* dci;
-  void *pst, *phm;
-  if (upload(d, I_SIG, hsig.data(), hsig.size(), &dsig, &h)) return -1;
-  PinnedUploads up;
-  up.add(I_DCGRP, hcg.data(), m, &dcg);
-  up.add(I_DCSHARE, hci.data(), m, &dci);
-  up.add(I_MSG, tab.t.bytes.data(), tab.t.bytes.size(), &dmsg);
-  up.add(I_OFF, tab.t.off.data(), nm, &doff);
-  up.add(I_LEN, tab.t.len.data(), nm, &dlen);
-  up.add(I_MIDX, p.midx.data(), m, &dmidx);
-  up.add(I_VGOFF, p.vgoff.data(), p.vgoff.size(), &dvgoff);
-  if (upload_pinned(d, h, up) || ensure_buf(h.io[I_STAT], m, &pst) || ensure_buf(h.io[I_HM], nm * sizeof(MsgEntry), &phm))
-    return -1;
-  MsgEntry* hm = (MsgEntry*)phm;
-  Ws& w = ws_acquire(d, s);
-  // the table is the call's own, so its lines are deferred where a host Verify defers them (verify_host)
-  const bool defer = defer_lines(p.n_vgroups(), nm);
-  if (hash_range(d, w, s, dmsg, doff, dlen, hm, 0, nm, !defer)) return -1;
-  VerifyCall vc;
-  vc.h_ready = w.ev_h;
-  vc.defer_hm = hm;
-  vc.defer_msgs = defer ? nm : 0;
-  vc.sigs = dsig;
-  vc.msg_idx = dmidx;
-  vc.hm = hm;
-  vc.n = m;
-  vc.grp_off = dvgoff;
-  vc.n_groups = p.n_vgroups();
-  vc.status = (uint8_t*)pst;
-  vc.s = s;
-  vc.device_entry = true;
-  vc.hm_ready = w.ev_side[2];
-  ClusterKeysArgs ck{};
-  ck.group = dcg;
-  ck.share_idx = dci;
-  ck.group_base = (uint32_t)cs.gb;
-  ck.n_groups = (uint32_t)(cs.ge - cs.gb);
-  ck.n_shares = cl.n_shares;
-  ck.n_keys = (uint32_t)cs.n_keys;
-  ck.any_entry = 1;
-  ck.ent = cs.ent;
-  ck.st = cs.st;
-  vc.cluster = &ck;
-  vc.cluster_wide = cs.wide;
-  if (verify_pipeline(d, w, vc)) return -1;
-  HCHK(hipStreamWaitEvent(s, w.ev_side[2], 0));
-  if (ws_release(w, s)) return -1;
-  lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
-  HCHK(hipMemcpyAsync(st.data(), pst, m, hipMemcpyDeviceToHost, s));
-  HCHK(hipStreamSynchronize(s));
-  for (size_t q = 0; q < m; q++) hst[p.order[q]] = st[q];
-  return 0;
+  return cluster_counters("hbls_cluster_check_stats", cluster, &Cluster::check_stats, out, n);
 }
 
 int hbls_cluster_verify_batch(uint64_t cluster, const uint32_t* group, const int64_t* key_idx, const uint8_t* sigs,
                               const uint8_t* msgs, const uint64_t* msg_off, const uint32_t* msg_len, size_t n,
                               uint8_t* status) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_verify_batch: no such cluster (never opened, or closed)");
+  std::shared_ptr<Cluster> cl = cluster_get("hbls_cluster_verify_batch", cluster);
+  if (!cl) return -1;
   if (n >= 0xffffffffull) return set_err("hbls_cluster_verify_batch: too many items");
   if (n && (!group || !key_idx || !sigs || !msg_off || !msg_len || !status))
     return set_err("hbls_cluster_verify_batch: group, key_idx, sigs, msg_off, msg_len and status are required");
-  if (n && !msgs)
-    for (size_t i = 0; i < n; i++)
-      if (msg_len[i]) return set_err("hbls_cluster_verify_batch: msgs is required (an item has a message of non-zero length)");
-  // an item goes to the shard that owns its group; one that names no validator needs no device
-  const size_t nd = cl->sh.size();
-  std::vector<std::vector<uint32_t>> items(nd);
-  std::vector<uint8_t> hst(n, (uint8_t)ST_BAD_PUBKEY);
-  uint64_t named = 0;
-  for (size_t i = 0; i < n; i++) {
-    if (group[i] >= cl->n_validators) continue;
-    const size_t k = duty_shard_of_group(group[i], cl->n_validators, nd);
-    items[k].push_back((uint32_t)i);
-    const ClusterShard& s = cl->sh[k];
-    named += cluster_key(group[i], key_idx[i], (uint32_t)s.gb, (uint32_t)(s.ge - s.gb), cl->n_shares, true) != CLUSTER_NO_KEY;
-  }
-  const size_t gmax = call_gmax(n, g_single_max.load(), g_fe_batch_min.load(), g_gmax.load());
-  const ClusterVerifyArgs a{group, key_idx, sigs, msgs, msg_off, msg_len};
-  if (n && cluster_each_shard(*cl, "hbls_cluster_verify_batch",
-                              [&](size_t k) { return cluster_verify_shard(*cl, cl->sh[k], a, items[k], gmax, hst.data()); }))
-    return -1;
-  // the caller's array is written once every shard has succeeded; a failed call counts nothing
-  if (n) memcpy(status, hst.data(), n);
-  cl->verify_stats[0] += 1;
-  cl->verify_stats[1] += named;
-  cl->verify_stats[2] += n - named;
-  return 0;
-}
-
-// One shard of hbls_cluster_verify_aggregate, on its library stream: k_cluster_row_sum over the shard's
-// own rows, then the k_seg_sum<false> passes of one group down to one Jacobian point and one flag, which
-// come to the host (sum: 144 bytes); complete (synchronised) when it returns.  The kernels only read the
-// cluster.  What it allocates goes when it returns, whatever it returns.
-static int cluster_sum_shard(const Cluster& cl, const ClusterShard& s, uint64_t share_mask, uint32_t with_dv, G1JEntry* sum,
-                             uint8_t* flag) {
-  const size_t ng = s.ge - s.gb;
-  if (!ng) return 0;
-  Dev& d = *s.d;
-  const uint32_t goff[2] = {0, (uint32_t)ng};
-  VaPlan v;
-  va_plan(goff, 1, ng, v);
-  const size_t na = v.pass_n[0], nb = v.pass_n.size() > 1 ? v.pass_n[1] : 1;
-  std::lock_guard<std::mutex> lk(d.mu);
-  if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-  struct Bufs {
-    void* p[7] = {};
-    ~Bufs() {
-      for (void* q : p)
-        if (q) (void)hipFree(q);
-    }
-  } b;
-  HCHK(hipMalloc(&b.p[0], ng * sizeof(G1JEntry)));
-  HCHK(hipMalloc(&b.p[1], ng));
-  HCHK(hipMalloc(&b.p[2], na * sizeof(G1JEntry)));
-  HCHK(hipMalloc(&b.p[3], na));
-  HCHK(hipMalloc(&b.p[4], nb * sizeof(G1JEntry)));
-  HCHK(hipMalloc(&b.p[5], nb));
-  HCHK(hipMalloc(&b.p[6], v.plan.size() * sizeof(uint32_t)));
-  HCHK(hipMemcpyAsync(b.p[6], v.plan.data(), v.plan.size() * sizeof(uint32_t), hipMemcpyHostToDevice, d.stream));
-  TIMED(d, "k_cluster_row_sum", d.stream,
-        launch_cluster_row_sum(s.ent, s.st, (uint32_t)ng, cl.n_shares, share_mask, with_dv, (G1JEntry*)b.p[0], (uint8_t*)b.p[1],
-                               d.stream));
-  G1JEntry* out;
-  uint8_t* out_st;
-  if (va_reduce(d, v, (const uint32_t*)b.p[6], false, b.p[0], (const uint8_t*)b.p[1], (G1JEntry*)b.p[2], (uint8_t*)b.p[3],
-                (G1JEntry*)b.p[4], (uint8_t*)b.p[5], d.stream, &out, &out_st))
-    return -1;
-  HCHK(hipMemcpyAsync(sum, out, sizeof(G1JEntry), hipMemcpyDeviceToHost, d.stream));  // the one group's sum: index 0
-  HCHK(hipMemcpyAsync(flag, out_st, 1, hipMemcpyDeviceToHost, d.stream));
-  HCHK(hipStreamSynchronize(d.stream));
-  return 0;
+  if (msgs_missing(msgs, msg_len, n))
+    return set_err("hbls_cluster_verify_batch: msgs is required (an item has a message of non-zero length)");
+  return cluster_verify_batch(*cl, {group, key_idx, sigs, msgs, msg_off, msg_len, n, status});
 }
 
 int hbls_cluster_verify_aggregate(uint64_t cluster, uint64_t share_mask, uint32_t with_dv, const uint8_t* sig,
                                   const uint8_t* msg, uint32_t msg_len, uint8_t* status) {
   if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_verify_aggregate: no such cluster (never opened, or closed)");
+  std::shared_ptr<Cluster> cl = cluster_get("hbls_cluster_verify_aggregate", cluster);
+  if (!cl) return -1;
   if (!cluster_sel_valid(share_mask, with_dv, cl->n_shares))
     return set_err("hbls_cluster_verify_aggregate: share_mask has a bit at or above the cluster's n_shares (" +
                    std::to_string(cl->n_shares) + "), or with_dv is above 1");
   if (!sig || !status || (msg_len && !msg)) return set_err("hbls_cluster_verify_aggregate: sig, status and msg are required");
-  // per shard: its rows' selected keys down to one point and one flag (an empty selection sums nothing)
-  const size_t nd = cl->sh.size();
-  const uint32_t per_row = cluster_sel_count(share_mask, with_dv);
-  std::vector<G1JEntry> hsum(nd);
-  std::vector<uint8_t> hflag(nd, 0);
-  if (per_row && cluster_each_shard(*cl, "hbls_cluster_verify_aggregate", [&](size_t k) {
-        return cluster_sum_shard(*cl, cl->sh[k], share_mask, with_dv, &hsum[k], &hflag[k]);
-      }))
-    return -1;
-  // across the shards: their points and flags, packed, to the first non-empty shard's device -- one more
-  // k_seg_sum<false> pass there (va_pipeline over Jacobian sums), then FastAggregateVerify's tail
-  std::vector<G1JEntry> sums;
-  std::vector<uint8_t> flags;
-  const ClusterShard* first = nullptr;
-  for (size_t k = 0; k < nd; k++) {
-    const ClusterShard& s = cl->sh[k];
-    if (s.ge == s.gb) continue;
-    if (!first) first = &s;
-    if (per_row) {
-      sums.push_back(hsum[k]);
-      flags.push_back(hflag[k]);
-    }
-  }
-  if (!first) first = &cl->sh[0];  // a cluster of no validator: the empty group on the first device
-  Dev& d = *first->d;
-  const size_t np = sums.size();
-  const uint32_t goff[2] = {0, (uint32_t)np};
-  MsgTable t;
-  t.idx.resize(1);
-  t.off.push_back(0);
-  t.len.push_back(msg_len);
-  t.bytes.assign(msg, msg + msg_len);
-  uint8_t st = 0;
-  {
-    HcLease hcs(d);
-    Hc& h = *hcs.h[0];
-    std::unique_lock<std::mutex> lk(d.mu);
-    if (hipSetDevice(d.ord) != hipSuccess) return set_err("hipSetDevice failed");
-    G1JEntry* dsums;
-    uint8_t *dflags, *dsig;
-    void *pst, *hmp;
-    if (upload(d, I_OUT, sums.data(), np, &dsums, &h) || upload(d, I_HM2, flags.data(), np, &dflags, &h) ||
-        upload(d, I_SIG, sig, (size_t)96, &dsig, &h) || ensure_buf(h.io[I_STAT], 1, &pst) ||
-        ensure_buf(h.io[I_HM], sizeof(MsgEntry), &hmp))
-      return -1;
-    Ws& w = ws_acquire(d, h.s);
-    VaKeys keys;
-    keys.sums = dsums;
-    keys.sums_st = dflags;
-    if (va_pipeline(d, w, keys, np, goff, 1, dsig, (MsgEntry*)hmp, (uint8_t*)pst, h.s,
-                    [&]() -> int { MsgEntry* hx; return hash_table(d, t, &hx, true, &h); }))
-      return -1;
-    if (ws_release(w, h.s)) return -1;
-    lk.unlock();  // enqueued: other callers may enqueue while this one waits for its stream
-    HCHK(hipMemcpyAsync(&st, pst, 1, hipMemcpyDeviceToHost, h.s));
-    HCHK(hipStreamSynchronize(h.s));
-  }
-  *status = st;
-  cl->verify_stats[3] += 1;
-  cl->verify_stats[4] += (uint64_t)per_row * cl->n_validators;
-  return 0;
+  return cluster_verify_aggregate(*cl, share_mask, with_dv, sig, msg, msg_len, status);
 }
 
 int hbls_cluster_verify_stats(uint64_t cluster, uint64_t* out, size_t n) {
-  if (ensure_init()) return -1;
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_cluster_verify_stats: no such cluster (never opened, or closed)");
-  if (!out || n > 5) return set_err("hbls_cluster_verify_stats: out is null or n above 5");
-  for (size_t k = 0; k < n; k++) out[k] = cl->verify_stats[k].load();
-  return 0;
+  return cluster_counters("hbls_cluster_verify_stats", cluster, &Cluster::verify_stats, out, n);
 }
 
 int hbls_duty_open_cluster(uint64_t cluster, uint32_t threshold, uint32_t max_stored, uint64_t* duty) {
-  if (ensure_init()) return -1;
-  if (!duty) return set_err("hbls_duty_open_cluster: duty is required");
-  if (threshold < 1 || threshold > (uint32_t)TA_SMALL_MAX)
-    return set_err("hbls_duty_open_cluster: threshold must be in 1.." + std::to_string(TA_SMALL_MAX));
-  if (max_stored < 1 || max_stored > DUTY_MAX_STORED)
-    return set_err("hbls_duty_open_cluster: max_stored must be in 1.." + std::to_string(DUTY_MAX_STORED));
-  std::shared_ptr<Cluster> cl = cluster_find(cluster);
-  if (!cl) return set_err("hbls_duty_open_cluster: no such cluster (never opened, or closed)");
+  if (ensure_init() || duty_open_check("hbls_duty_open_cluster", duty, threshold, max_stored)) return -1;
+  std::shared_ptr<Cluster> cl = cluster_get("hbls_duty_open_cluster", cluster);
+  if (!cl) return -1;
   if (cl->n_validators >= 0xffffffffull / DUTY_MAX_STORED) return set_err("hbls_duty_open_cluster: too many groups");
   return duty_open(nullptr, cl->n_validators, threshold, max_stored, duty, cl);
 }

@@ -132,6 +132,10 @@ def secret(lock, g, j):
 
 @pytest.fixture(scope="module")
 def signed(hipbls, lock):
+    return make_signed(hipbls, lock)
+
+
+def make_signed(hipbls, lock):
     """{(g, j, m): the signature of M[m] under key (g, j) of the lock} for every pair over two messages"""
     keys = [(g, j, m) for m in (0, 1) for g in range(V) for j in range(N + 1)]
     sigs = hipbls.sign_batch([secret(lock, g, j) for g, j, _ in keys], [M[m] for _, _, m in keys])
@@ -492,7 +496,38 @@ def test_call_errors_write_nothing(L, lock, signed):
     assert err(cl.aggregate(1, 0, sig, M[0], handle=closed)) == "hbls_cluster_verify_aggregate: " + NONE
 
 
-# ---- 7: the Python layer
+# ---- 7: the kernels each call enqueues, in order, against tests/golden/cluster_traces.json
+def test_launch_traces(L, hipbls, lock, signed):
+    """The fixture was recorded by tests/golden/make_cluster_traces.py with the library of the commit before the
+    handle layer's shard runner, buffer owner, handle table and counter reader became one each; a change that
+    is not meant to alter the launch sequences must reproduce them.  Name by name, except the two-shard
+    traces (SORTED there): their shard threads race, so those compare as sorted lists."""
+    import json
+    golden = os.path.join(ROOT, "tests", "golden")
+    if golden not in sys.path:
+        sys.path.insert(0, golden)
+    import make_cluster_traces as mc
+    with open(mc.PATH) as f:
+        want = json.load(f)["traces"]
+    assert set(want) == {t for c in mc.CASES for t in mc.TRACES[c]} and mc.SORTED <= set(want)
+    got = mc.run_cases(mc.Ctx(L, hipbls, lock, signed))
+    assert set(got) == set(want)
+    for name, names in got.items():
+        assert names, name
+        a, b = (sorted(names), sorted(want[name])) if name in mc.SORTED else (names, want[name])
+        diff = next((f"launch {k}: {x} (recorded: {y})" for k, (x, y) in enumerate(zip(a, b)) if x != y),
+                    f"{len(a)} launches (recorded: {len(b)})")
+        assert a == b, (name, diff)
+    # the cases do take different paths
+    assert "k_cluster_wide" in got["cluster_open_tables1"] and "k_cluster_wide" not in got["cluster_open_tables0"]
+    assert got["cluster_check"].count("k_lock_check") == 1
+    assert "k_cluster_row_sum" in got["cluster_verify_aggregate_all"]
+    assert "k_cluster_row_sum" not in got["cluster_verify_aggregate_empty"]
+    assert got["cluster_verify_aggregate_split2"].count("k_cluster_row_sum") == 2
+    assert "k_duty_gather" in got[f"cluster_duty_add_{T}"] and "k_duty_gather" not in got["cluster_duty_add_1"]
+
+
+# ---- 8: the Python layer
 def test_callers_cluster(hipbls, kats):
     from charon_amd import callers
     from charon_amd.tbls import TblsError

@@ -42,6 +42,10 @@ def L(hipbls):
 
 @pytest.fixture(scope="module")
 def lock(hipbls):
+    return make_lock(hipbls)
+
+
+def make_lock(hipbls):
     """Per validator: the secret, its N share secrets, the DV key and the N pubshares, by the library's own split"""
     secrets, shares = [], []
     for v in range(V):

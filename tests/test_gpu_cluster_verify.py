@@ -32,6 +32,7 @@ IDS = ['test_reference_locks',
        'test_shards[3]',
        'test_verifies_only_read',
        'test_call_errors_write_nothing',
+       'test_launch_traces',
        'test_callers_cluster']
 
 
